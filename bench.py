@@ -11,9 +11,14 @@ ranks (BASELINE.json: "SOCP n=100, batch=4096, 1->8 GPU batch shard", `--config 
 `--config C5 --batch 16384 --scaling strong`).  The step includes the all-gather of primal/dual (every rank evaluates the same loss on the gathered tensor:
 parallel.py's loss="replicated" contract, no collective in the backward); the JSON line carries the exchange on its own (`allgather_ms`) and every rank's own
 step time (`ms_per_step_per_rank`).
-`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (re-exec under
+`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (a child process
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); under an external launcher
 (the driver's torchrun line) RANK / LOCAL_RANK / WORLD_SIZE are read from the environment.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON line (metric, value, unit, ms_per_step, ...).  `--full` adds
+everything else measured around the headline: per-kernel HIP-event times and the rooflines built on them, the dispatch-order
+comparisons, the README-recommended solver settings and the asynchronous forward, the all-gather on its own (N > 1), the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (primal, dual, and the gradients of q_eval / A_eval) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -213,6 +218,27 @@ def sq_limiter(kernel_short):
     return None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """`--dump-outputs`: arrays = [(name, tensor, batch axis)] -> path/<name>.npy in float64.  Arrays are written whole, smallest first, while
+    they fit their share of DUMP_BUDGET_BYTES; a larger one keeps the instances of a fixed seeded sample of its batch axis (the same sample for
+    every array of that batch size), so that two builds given the same arguments can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    host = sorted(((name, t.detach().to("cpu", torch.float64).numpy(), ax) for name, t, ax in arrays), key=lambda e: e[1].nbytes)
+    left = DUMP_BUDGET_BYTES
+    for i, (name, a, ax) in enumerate(host):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            B = a.shape[ax]
+            k = max(1, share // (a.nbytes // B))
+            keep = np.sort(np.random.default_rng(seed).choice(B, size=k, replace=False))
+            a = np.take(a, keep, axis=ax)
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+
+
 def shard_sizes(total, world):
     """contiguous shards of a batch of `total` instances (parallel.shard_bounds)"""
     from cvxpylayers_amd.parallel import shard_bounds
@@ -310,6 +336,11 @@ def main():
                          "acceleration every 10 iterations (the engine keeps a one-pair history, the CPU oracle the full lookback: same iteration "
                          "counts within 2.5 %%, profiles/r02/aa_memory.json); 0 = plain iteration.")
     ap.add_argument("--dry-run-ranks", type=int, default=0, help="N > 0: exercise the multi-rank launch / gather plumbing with N CPU ranks over gloo (no GPU, no solver)")
+    ap.add_argument("--full", action="store_true", help="also measure what surrounds the headline: per-kernel times and rooflines, dispatch-order comparisons, "
+                                                         "--extras, the all-gather on its own (N > 1) and the CPU baseline (unless --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (primal, dual, grad_q_eval, "
+                                                                        "grad_A_eval) as DIR/<name>.npy, float64, at most 64 MiB in all (a fixed seeded sample of "
+                                                                        "the instances of an array that does not fit)")
     args = ap.parse_args()
 
     if args.dry_run_ranks > 0:
@@ -318,15 +349,16 @@ def main():
         else:
             return dry_run_ranks(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # launched bare: create the N ranks (one process per GPU) and let rank 0 of that job print the JSON line
+        # launched bare: create the N ranks (one process per GPU) in a child launcher and let rank 0 of that job print the JSON line
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.run(cmd).returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: reporting n_gpus={world}", file=sys.stderr)
@@ -354,6 +386,7 @@ def main():
     eng = ctx.engine(dev)
     step_no = [0]
     last_info = [None] * K_rot          # the most recent `info` of every slot (iteration counts of ALL rotating batches enter the flop count)
+    last_out = [None]                   # (slot, primal, dual) of the most recent step: --dump-outputs
 
     def step(fixed=None):
         slot = (step_no[0] % K_rot) if fixed is None else fixed
@@ -366,13 +399,15 @@ def main():
             primal, dual = gather_solution(primal, dual, sizes if args.scaling == "strong" else None)      # one fused RCCL all-gather per step (ragged shards are padded)
         primal.sum().backward()
         last_info[slot] = info
+        last_out[0] = (slot, primal, dual)
         return info
 
     # clock ramp: a run as short as the driver's (--steps 20 --warmup 5: 60 ms of GPU work) would be timed on a GPU that has not reached its steady clocks yet (docs/ROUND_NOTES_r3_r4.md: short measurements right
     # after process start see the ramp).  Untimed steps until 0.3 s have passed, in ADDITION to the W warm-up steps of the contract; reported as `prewarm_steps`.
+    # Whole rotations only, so that the batch of every later step (the dumped one included) depends on --warmup / --steps alone.
     prewarm_steps = 0
     t_pw = time.perf_counter()
-    while (time.perf_counter() - t_pw < 0.3) if world == 1 else (prewarm_steps < 100):      # (several ranks: a FIXED count -- every step holds a collective, the ranks must agree on their number)
+    while ((time.perf_counter() - t_pw < 0.3) if world == 1 else (prewarm_steps < 100)) or prewarm_steps % K_rot:      # (several ranks: a FIXED count -- every step holds a collective, the ranks must agree on their number)
         info = step(); prewarm_steps += 1
         if prewarm_steps % 8 == 0:
             torch.cuda.synchronize()
@@ -382,8 +417,9 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    eng.set_profiling(2)          # HIP events around the FORWARD launches of the timed region only (the roofline kernel); the other kernels' averages come from a few extra steps below:
-    eng.reset_profile()           # every bracketed launch costs two event records of host time in front of it, and the adjoint's sit in the gap in which the GPU waits for the host
+    if args.full:
+        eng.set_profiling(2)      # HIP events around the FORWARD launches of the timed region only (the roofline kernel); the other kernels' averages come from a few extra steps below:
+        eng.reset_profile()       # every bracketed launch costs two event records of host time in front of it, and the adjoint's sit in the gap in which the GPU waits for the host
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -398,15 +434,20 @@ def main():
         dist.all_gather(tall, torch.tensor([dt], dtype=torch.float64, device=dev))
         per_rank_ms = [1e3 * float(t.item()) / args.steps for t in tall]
         dt = max(float(t.item()) for t in tall)          # the MAX over ranks is the job's time
-    fwd_ms, nf = eng.profile(0)
-    eng.set_profiling(12)         # adjoint + layout launches: bracketed on a few untimed steps
-    eng.reset_profile()
-    for _ in range(max(8, min(args.steps, 40))):
-        step()
-    torch.cuda.synchronize()
-    bwd_ms, nb = eng.profile(1)
-    lay_ms, nl = eng.profile(2)
-    eng.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        slot, primal, dual = last_out[0]
+        A_t, q_t = batches[slot]
+        dump_outputs(args.dump_outputs, [("primal", primal, 0), ("dual", dual, 0), ("grad_q_eval", q_t.grad, 1), ("grad_A_eval", A_t.grad, 1)])
+    if args.full:
+        fwd_ms, nf = eng.profile(0)
+        eng.set_profiling(12)     # adjoint + layout launches: bracketed on a few untimed steps
+        eng.reset_profile()
+        for _ in range(max(8, min(args.steps, 40))):
+            step()
+        torch.cuda.synchronize()
+        bwd_ms, nb = eng.profile(1)
+        lay_ms, nl = eng.profile(2)
+        eng.set_profiling(False)
     # Two more timings of the same step, outside the headline (one rank only): `index_order` = the rotation with the dispatch history switched off, `replay` = ONE
     # batch re-solved every step with the history on (the previous call's iteration counts and largest adjoint system are then exact: what rounds 1-4 reported).
     def timed(ns, fixed=None):
@@ -418,7 +459,7 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t1) * 1e3 / ns
     other_ms = replay_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         ns_other = max(8, min(args.steps, 40))
         eng.set_dispatch_history(not args.dispatch_history)
         other_ms = timed(ns_other)
@@ -430,7 +471,7 @@ def main():
     # caller waives the raise-from-forward contract, the plugin then never waits for the device (failure masking happens on the device): what the one contractual
     # host round trip of the default path costs.
     extras = {}
-    if world == 1 and args.extras:
+    if world == 1 and args.full and args.extras:
         def timed_with(sa, ns):
             def st():
                 A_t, q_t = batches[step_no[0] % K_rot]; step_no[0] += 1
@@ -460,7 +501,7 @@ def main():
                                    "note": "raise_on_error=False waives the reference's raise-from-forward contract: no host round trip in forward (failed instances are masked on the "
                                            "device, the outcome is reported by the next call); the difference to ms_per_step_default_same_loop is what that round trip costs"}
     allgather_ms = None
-    if world > 1:         # the exchange step on its own: one fused RCCL all-gather of (B, n + m) rows per step (HIP events on this stream)
+    if world > 1 and args.full:         # the exchange step on its own: one fused RCCL all-gather of (B, n + m) rows per step (HIP events on this stream)
         with torch.no_grad():
             pr = torch.zeros((B, n), dtype=torch.float64, device=dev); du = torch.zeros((B, tpl.m), dtype=torch.float64, device=dev)
             gsz = sizes if args.scaling == "strong" else None
@@ -477,18 +518,9 @@ def main():
         ms_per_step = 1e3 * dt / args.steps
         value = sum(sizes) * args.steps / dt
         m, nnzA = tpl.m, tpl.nnzA
-        cfgname = args.config
         slots = [li for li in last_info if li is not None]
         iters = torch.stack([li["iters"] for li in slots]).cpu().numpy().astype(np.float64)          # (slots visited, B)
         solved = float(np.mean([float((li["status"] == 1).float().mean().item()) for li in slots]))
-        # algorithmic HBM bytes per instance: forward 8(nnzA+m+n) read + 8(n+2m) written
-        fwd_bytes = 8 * (nnzA + m + n) + 8 * (n + 2 * m)
-        bwd_bytes = 8 * (nnzA + 2 * n + 3 * m) + 8 * (nnzA + m + n)
-        ach = fwd_bytes * B / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic("k_fwd")
-        # algorithmic fp64 flops of the forward kernel: setup m n^2 + n^3/3, per iteration 4 nnzA + 2 n^2 + 10(n+m)
-        flops = B * (m * n * n + n ** 3 / 3.0) + float(iters.sum(axis=1).mean()) * (4 * nnzA + 2 * n * n + 10 * (n + m))
-        vtf = flops / (fwd_ms * 1e-3) / 1e12 if fwd_ms > 0 else 0.0
         out = {
             "metric": ("forward+backward problems/sec, batch=4096 n=50 m=100 SOC" if (args.config == "M" and B == 4096) else
                        f"forward+backward problems/sec, batch={B} n={n} m={m} config {args.config}"), "value": value, "unit": "problems/s",
@@ -501,38 +533,48 @@ def main():
                                    "; step = plugin forward (layout pass + solve + status) + backward (adjoint VJP of sum(x))",
                        "batch_per_gpu": B, "rotating_batches": K_rot, "parallelism": f"batch-shard x{world}", "acceleration_lookback": int(args.accel),
                        "solved_fraction": solved, "mean_iters": float(iters.mean())},
-            "roofline": {"bound": "valu-issue/latency", "kernel": "forward (k_fwd2 / k_forward_rt / k_forward): the longest kernel of the step",
-                         "achieved": vtf, "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s", "frac": vtf / FP64_VALU_PEAK_TF,
-                         "traffic": traffic, "traffic_source": traffic_src, "algorithmic_flops_per_launch": flops,
-                         "note": "the binding roof is what the SQ counters say (`limiter`): the fp64 vector pipe's issue rate and the latency of dependent chains / barriers / LDS, "
-                                 "so achieved / peak are algorithmic fp64 flops against the fp64 VALU peak.  The iteration lives in LDS and registers and HBM is touched once by "
-                                 "construction: the HBM side is kept under `hbm` (algorithmic bytes / kernel time against 8 TB/s) and `traffic` (PMC bytes per launch)",
-                         "limiter": sq_limiter("k_fwd"),
-                         "hbm": {"achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": fwd_bytes * B,
-                                 "traffic_over_algorithmic": (traffic / (fwd_bytes * B)) if traffic else None}},
-            "kernels_ms": {"k_forward": fwd_ms, "k_backward": bwd_ms, "k_transpose": lay_ms, "launches": [nf, nb, nl],
-                           "bwd_algorithmic_GBps": bwd_bytes * B / (bwd_ms * 1e-3) / 1e9 if bwd_ms > 0 else 0.0},
-            "host_gap_ms": ms_per_step - (fwd_ms + bwd_ms + 2 * lay_ms) if args.config != "C5" else None,
             "iters": {"mean": float(iters.mean()), "max": float(iters.max())},
-            "dispatch": {"history": bool(args.dispatch_history), "ms_per_step_rotating_with_history": ms_per_step if args.dispatch_history else other_ms,
-                         "ms_per_step_rotating_index_order": other_ms if args.dispatch_history else ms_per_step,
-                         "ms_per_step_replay_one_batch": replay_ms,
-                         "note": "the plugin records every call's iteration counts and dispatches the next call's workgroups longest-first ONLY when the history has been predictive "
-                                 "(>= 70 % of the instances in the same check interval as the call before: decided on the device); the adjoint's first tile is sized by the previous call's "
-                                 "largest system.  `value` is measured on rotating batches: the history does not predict there and the index order runs; `replay` re-solves one batch "
-                                 "(history exact, applied from the third call on) and is reported for comparison with rounds 1-4 only"},
-            "launch": eng.launch_info(),
+            "full": bool(args.full),
         }
-        out["roofline"]["backward"] = adjoint_roofline(eng, slots, tpl, cones, B, bwd_ms, bwd_bytes)
         out["ms_per_step_per_rank"] = per_rank_ms
-        out.update(extras)
-        if allgather_ms is not None:
-            out["allgather_ms"] = allgather_ms
-            out["allgather_bytes_per_rank"] = 8 * B * (n + m)
-            out["allgather_share_of_step"] = allgather_ms / ms_per_step
-        if not args.no_cpu and world == 1 and args.config != "C5":          # (the CPU leg draws dense instances of problems.CONFIGS: not config 5's shared-A portfolio)
-            out["cpu_baseline"] = cpu_baseline(n, cones, solver_args, args.cpu_sample, seed=0)
-            out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+        if args.full:
+            # algorithmic HBM bytes per instance: forward 8(nnzA+m+n) read + 8(n+2m) written
+            fwd_bytes = 8 * (nnzA + m + n) + 8 * (n + 2 * m)
+            bwd_bytes = 8 * (nnzA + 2 * n + 3 * m) + 8 * (nnzA + m + n)
+            ach = fwd_bytes * B / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
+            traffic, traffic_src = pmc_traffic("k_fwd")
+            # algorithmic fp64 flops of the forward kernel: setup m n^2 + n^3/3, per iteration 4 nnzA + 2 n^2 + 10(n+m)
+            flops = B * (m * n * n + n ** 3 / 3.0) + float(iters.sum(axis=1).mean()) * (4 * nnzA + 2 * n * n + 10 * (n + m))
+            vtf = flops / (fwd_ms * 1e-3) / 1e12 if fwd_ms > 0 else 0.0
+            out["roofline"] = {"bound": "valu-issue/latency", "kernel": "forward (k_fwd2 / k_forward_rt / k_forward): the longest kernel of the step",
+                               "achieved": vtf, "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s", "frac": vtf / FP64_VALU_PEAK_TF,
+                               "traffic": traffic, "traffic_source": traffic_src, "algorithmic_flops_per_launch": flops,
+                               "note": "the binding roof is what the SQ counters say (`limiter`): the fp64 vector pipe's issue rate and the latency of dependent chains / barriers / LDS, "
+                                       "so achieved / peak are algorithmic fp64 flops against the fp64 VALU peak.  The iteration lives in LDS and registers and HBM is touched once by "
+                                       "construction: the HBM side is kept under `hbm` (algorithmic bytes / kernel time against 8 TB/s) and `traffic` (PMC bytes per launch)",
+                               "limiter": sq_limiter("k_fwd"),
+                               "hbm": {"achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": fwd_bytes * B,
+                                       "traffic_over_algorithmic": (traffic / (fwd_bytes * B)) if traffic else None}}
+            out["kernels_ms"] = {"k_forward": fwd_ms, "k_backward": bwd_ms, "k_transpose": lay_ms, "launches": [nf, nb, nl],
+                                 "bwd_algorithmic_GBps": bwd_bytes * B / (bwd_ms * 1e-3) / 1e9 if bwd_ms > 0 else 0.0}
+            out["host_gap_ms"] = ms_per_step - (fwd_ms + bwd_ms + 2 * lay_ms) if args.config != "C5" else None
+            out["dispatch"] = {"history": bool(args.dispatch_history), "ms_per_step_rotating_with_history": ms_per_step if args.dispatch_history else other_ms,
+                               "ms_per_step_rotating_index_order": other_ms if args.dispatch_history else ms_per_step,
+                               "ms_per_step_replay_one_batch": replay_ms,
+                               "note": "the plugin records every call's iteration counts and dispatches the next call's workgroups longest-first ONLY when the history has been predictive "
+                                       "(>= 70 % of the instances in the same check interval as the call before: decided on the device); the adjoint's first tile is sized by the previous call's "
+                                       "largest system.  `value` is measured on rotating batches: the history does not predict there and the index order runs; `replay` re-solves one batch "
+                                       "(history exact, applied from the third call on) and is reported for comparison with rounds 1-4 only"}
+            out["launch"] = eng.launch_info()
+            out["roofline"]["backward"] = adjoint_roofline(eng, slots, tpl, cones, B, bwd_ms, bwd_bytes)
+            out.update(extras)
+            if allgather_ms is not None:
+                out["allgather_ms"] = allgather_ms
+                out["allgather_bytes_per_rank"] = 8 * B * (n + m)
+                out["allgather_share_of_step"] = allgather_ms / ms_per_step
+            if not args.no_cpu and world == 1 and args.config != "C5":          # (the CPU leg draws dense instances of problems.CONFIGS: not config 5's shared-A portfolio)
+                out["cpu_baseline"] = cpu_baseline(n, cones, solver_args, args.cpu_sample, seed=0)
+                out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

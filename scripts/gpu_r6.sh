@@ -19,23 +19,23 @@ if has tests; then
 fi
 if has bench; then
   echo "== bench $BENCH_ARGS" | tee -a "$OUT/summary.txt"
-  timeout 400 python bench.py $BENCH_ARGS 2>"$OUT/bench.err" | tee "$OUT/bench.json" | cut -c1-700 | tee -a "$OUT/summary.txt"
+  timeout 400 python bench.py --full $BENCH_ARGS 2>"$OUT/bench.err" | tee "$OUT/bench.json" | cut -c1-700 | tee -a "$OUT/summary.txt"
 fi
 if has prof; then
   echo "== rocprofv3 kernel-trace stats" | tee -a "$OUT/summary.txt"
-  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- python "$OLDPWD/bench.py" --no-cpu $BENCH_ARGS > "$OUT/prof.log" 2>&1)
+  (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- python "$OLDPWD/bench.py" --full --no-cpu $BENCH_ARGS > "$OUT/prof.log" 2>&1)
   find "$OUT/prof" -name "*kernel_stats.csv" | head -1 | xargs -r head -12 | tee -a "$OUT/summary.txt"
 fi
 if has pmc; then
   echo "== pmc FETCH_SIZE / WRITE_SIZE (separate passes)" | tee -a "$OUT/summary.txt"
-  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o p --output-format csv -- python "$OLDPWD/bench.py" --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/pmc_fetch.log" 2>&1)
-  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o p --output-format csv -- python "$OLDPWD/bench.py" --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/pmc_write.log" 2>&1)
+  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o p --output-format csv -- python "$OLDPWD/bench.py" --full --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/pmc_fetch.log" 2>&1)
+  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o p --output-format csv -- python "$OLDPWD/bench.py" --full --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/pmc_write.log" 2>&1)
   python scripts/pmc_summary.py "$OUT" 2>&1 | tee -a "$OUT/summary.txt"
 fi
 if has sq; then
   echo "== SQ counters (two passes over bench.py --steps 2)" | tee -a "$OUT/summary.txt"
-  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT -d "$OUT/sq1" -o p --output-format csv -- python "$OLDPWD/bench.py" --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/sq1.log" 2>&1)
-  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_INSTS_SALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE -d "$OUT/sq2" -o p --output-format csv -- python "$OLDPWD/bench.py" --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/sq2.log" 2>&1)
+  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT -d "$OUT/sq1" -o p --output-format csv -- python "$OLDPWD/bench.py" --full --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/sq1.log" 2>&1)
+  (cd /tmp && timeout 240 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_INSTS_SALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE -d "$OUT/sq2" -o p --output-format csv -- python "$OLDPWD/bench.py" --full --no-cpu --steps 2 --warmup 1 $BENCH_ARGS > "$OUT/sq2.log" 2>&1)
   python scripts/sq_summary.py "$OUT" 2>&1 | tee -a "$OUT/summary.txt"
 fi
 if has list; then

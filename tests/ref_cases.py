@@ -108,3 +108,47 @@ CASES = {
     "sdp_sym_primal_psd_dual": case_sdp_symmetric_primal_and_psd_dual,
     "metric_shape": case_metric_shape,
 }
+
+
+# ------------------------------------------------------------------------------------------------ seeded inputs of the convention checks
+# Fed to the reference's functions by tests/golden/make_refglue.py (answers recorded in tests/golden/refglue_conventions.npz) and to
+# this repository's by tests/test_ref_glue.py.
+FLATTENING_CASES = ["ridge_mixed", "ridge_batched_matrix_param", "matrix_variable", "metric_shape"]
+RECOVERY_CASES = ["sdp_sym_primal_psd_dual", "matrix_variable", "metric_shape", "ridge_unbatched"]
+
+
+def diffcp_matrices_inputs():
+    """Boundary values for _build_diffcp_matrices / _compute_gradients (diffcp_if.py:46-96): a 9 x 7 template with a random
+    pattern, B = 3 seeded A_eval / q_eval, and the seeded adjoint (dA, db, dc) the stubbed derivative returns."""
+    rng = np.random.default_rng(0)
+    n, cones = 7, {"z": 2, "l": 3, "q": [4]}
+    pattern = rng.random((9, n)) < 0.6; pattern[0, :] = True
+    bpat = rng.random(9) < 0.7; bpat[0] = True
+    tpl = P.dense_template(n, cones, pattern=pattern, b_pattern=bpat)
+    B = 3
+    A_eval = rng.standard_normal((tpl.nnz_aug, B)); q_eval = rng.standard_normal((n + 1, B))
+    dA_d = rng.standard_normal((B, tpl.m, n)); db = rng.standard_normal((B, tpl.m)); dc = rng.standard_normal((B, n))
+    return dict(tpl=tpl, n=n, B=B, A_eval=A_eval, q_eval=q_eval, dA=dA_d, db=db, dc=dc)
+
+
+def recovery_inputs(tpl):
+    """[(batch, primal (B, n), dual (B, m))] for the unbatched and a batch-of-4 call of the variable recovery."""
+    rng = np.random.default_rng(1)
+    n = tpl.A_structure[2][1] - 1; m = tpl.A_structure[2][0]
+    out = []
+    for batch in ((), (4,)):
+        B = batch[0] if batch else 1
+        out.append((batch, rng.standard_normal((B, n)), rng.standard_normal((B, m))))
+    return out
+
+
+def bad_ridge_params(tpl):
+    """Parameter lists that validate_params must refuse (wrong count, shapes, batch sizes), for the ridge_mixed template."""
+    import torch
+    mF, n = tpl.param_shapes[0]
+    return [[torch.zeros(mF, n)], [torch.zeros(mF, n), torch.zeros(mF + 1)], [torch.zeros(2, 2, mF, n), torch.zeros(mF)],
+            [torch.zeros(2, mF, n), torch.zeros(3, mF)], [torch.zeros(2, mF, n + 1), torch.zeros(2, mF)]]
+
+
+SOLVER_ARGS_LAYER = {"eps": 1e-6, "max_iters": 1234}     # layer-level solver_args of the merge check
+SOLVER_ARGS_CALL = {"eps": 1e-9}                          # call-level solver_args of the merge check
