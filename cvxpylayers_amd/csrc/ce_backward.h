@@ -627,7 +627,7 @@ __global__ void __launch_bounds__(512) k_parammap_lds(int rows, int cols, const 
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const int r = r0 + u * NT;
-                const double a = v[u] * pl[c[u]];
+                const double a = t1[u] > t0[u] ? v[u] * pl[c[u]] : 0.0;      // (select: 0 * pl[0] would be NaN for a non-finite parameter 0)
                 if (r < rows) { if (!ACC) o[r] = a; else if (t1[u] > t0[u]) o[r] += a; }
             }
         } else {

@@ -90,7 +90,7 @@ struct ce_engine {
     int ns_variant = -1; size_t ns_lds = 0;       // search-free null-space adjoint (ce_backward_ns.h), -1: not applicable
     // two-tile plan of the register-tiled adjoint: a smaller tile serves the instances it holds, the worst-case tile re-runs the ones it flagged.  The smaller
     // tile is chosen from the LARGEST system of the previous call of the same batch size (nk_*: device maximum, copied to pinned memory behind the launch)
-    bool two_tile = false; int fast_forced = -1;
+    bool two_tile = false; int fast_forced = -1; int last_fast = -1;      // last_fast: first tile of the last two-tile call (-1: none; ce_get_plan)
     int *d_nkmax = nullptr, *h_nkmax = nullptr; hipEvent_t nk_ev = nullptr; bool nk_pending = false, nk_have = false, nk_zeroed = false; int nk_last = 0, nk_B = 0;
     // re-solve of rank-deficient adjoint systems by LSQR (ce_set_adjoint_resolve): fix[0] = number of listed instances, fix[1 ...] = the instances the elimination
     // kernels flagged (appended on the device); diffcp's LSQR rule
@@ -479,8 +479,13 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
         // hence the history instead of an a-priori guess (config 3: half of the instances have a fully active cone, NK up to 170 of 200 -- no smaller tile).
         // CE_BWD_TWO_TILE=0 disables; CE_BWD_FAST_VARIANT=v forces the first tile (tests).
         const char *tt = getenv("CE_BWD_TWO_TILE"), *fv = getenv("CE_BWD_FAST_VARIANT");
-        h->two_tile = h->bwd_mode == 3 && plain && h->nnz_p == 0 && h->brt_variant > 0 && !(tt && !strcmp(tt, "0"));
         h->fast_forced = fv ? atoi(fv) : -1;
+        // a first tile must differ from the worst-case tile in TI / TJ alone (ce_vjp_qp): without such a tile (worst case v4 or v5) the plan has nothing to offer
+        bool first_tile = h->brt_variant > 0 && h->fast_forced >= 0 && h->fast_forced < h->brt_variant;
+        for (int v = 0; v < h->brt_variant && !first_tile; v++)
+            first_tile = BRT_VARIANTS[v][2] == BRT_VARIANTS[h->brt_variant][2] && BRT_VARIANTS[v][3] == BRT_VARIANTS[h->brt_variant][3] &&
+                         T.n <= BGC * BRT_VARIANTS[v][2] && bwd_rt_lds_bytes(T, BRT_VARIANTS[v][0], BRT_VARIANTS[v][1], BRT_VARIANTS[v][3]) <= LDS_LIMIT;
+        h->two_tile = h->bwd_mode == 3 && plain && h->nnz_p == 0 && first_tile && !(tt && !strcmp(tt, "0"));
     }
     // Search-free null-space adjoint (ce_backward_ns.h): plain cones, linear objective, 4 ceil(n / 4) + 1 columns in the variant's tiles.  It serves ce_vjp calls
     // whose LSQR re-solve is armed (rank-deficient instances are detected, flagged and handed to LSQR, not resolved by the elimination).  CE_BWD_NS=0 disables.
@@ -712,6 +717,7 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         ba.sdqk = sdq_k; ba.sdqb = sdq_b; ba.adj = adj_status; ba.P = P_vals; ba.nnz_p = h->nnz_p; ba.pmap = h->d_pmap; ba.prow = h->d_prow; ba.pcol = h->d_pcol;
         ba.p_tri = h->p_tri; ba.dP = dP_vals; ba.gA = gA; ba.gK = gK;
         int lrc;
+        h->last_fast = -1;
         if (do_fix && h->ns_variant >= 0) {
             ba.T.lda = T.n;
             lrc = ce_launch_bwd_ns(h->ns_variant, B, h->ns_lds, st, ba);
@@ -729,12 +735,16 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
                 const int need = (h->nk_have && !h->nk_pending && h->nk_B == B) ? h->nk_last + 8 : (1 << 30);
                 for (int v = (h->fast_forced >= 0 ? h->fast_forced : 0); v < h->brt_variant; v++) {
                     const int TI = BRT_VARIANTS[v][0], TJ = BRT_VARIANTS[v][1], TH = BRT_VARIANTS[v][2], BGR = BRT_VARIANTS[v][3];
+                    // (a first tile with another H tile or row-residue count than the worst-case tile sums in another order: its gradients differ in the last bits
+                    //  from the single-tile plan's, so only tiles that differ in TI / TJ alone qualify -- unless forced)
+                    if (h->fast_forced < 0 && (TH != BRT_VARIANTS[h->brt_variant][2] || BGR != BRT_VARIANTS[h->brt_variant][3])) continue;
                     if ((h->fast_forced >= 0 || (need <= BGC * TJ - 1 && need <= BGR * TI)) && T.n <= BGC * TH && bwd_rt_lds_bytes(T, TI, TJ, BGR) <= LDS_LIMIT) { fast = v; fast_lds = bwd_rt_lds_bytes(T, TI, TJ, BGR); break; }
                 }
                 if (!h->nk_zeroed) { HIPCHK(hipMemsetAsync(h->d_nkmax, 0, sizeof(int), st)); h->nk_zeroed = true; }      // (first call; afterwards the counter is reset behind the read-back)
                 ba.nk_max = h->d_nkmax;
             }
             if (fast >= 0) {
+                h->last_fast = fast;
                 ba.nonfinal = 1;      // (an instance this tile does not hold is the retry launch's business, not yet the list's)
                 lrc = ce_launch_bwd_rt_plain(fast, B, fast_lds, st, ba);
                 ba.retry = 1; ba.nonfinal = 0;
@@ -1195,6 +1205,14 @@ int ce_get_launch_info(ce_handle h, int *fl, int *bl, int *fm, int *bm) {
     if (!h) return CE_E_BADARG;
     if (fl) *fl = (int)h->fwd_lds; if (bl) *bl = (int)h->bwd_lds; if (fm) *fm = h->fwd_mode; if (bm) *bm = h->bwd_mode;
     return CE_OK;
+}
+int ce_get_plan(ce_handle h, int *out, int n_out) {
+    if (!h) { g_err = "null argument"; return CE_E_BADARG; }
+    const int v[] = {h->fwd_mode, h->f2_variant, h->rt_variant, h->wl ? 1 : 0, h->aa_ok ? 1 : 0, h->T.gen_blocked_f, h->qp_native ? 1 : 0,
+                     h->bwd_mode, h->brt_variant, h->two_tile ? 1 : 0, h->ns_variant, h->T.gen_blocked_b, h->sp_r, h->sp_RP, h->last_fast};
+    const int cnt = (int)(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; out && i < cnt && i < n_out; i++) out[i] = v[i];
+    return cnt;
 }
 
 }  // extern "C"

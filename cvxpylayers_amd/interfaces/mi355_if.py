@@ -474,6 +474,18 @@ class ConeEngine:
         _lib.lib().ce_get_launch_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         return dict(fwd_lds_bytes=a.value, bwd_lds_bytes=b.value, fwd_mode=c.value, bwd_mode=d.value)
 
+    PLAN_FIELDS = ("fwd_mode", "f2_variant", "rt_variant", "wl", "aa_ok", "gen_blocked_f", "qp_native",
+                   "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_r", "sp_RP", "last_fast")
+
+    def plan(self):
+        """The whole launch plan (include/cone_engine.h ce_get_plan) as a dict keyed by PLAN_FIELDS."""
+        L = _lib.lib()
+        cnt = L.ce_get_plan(self._h, None, 0)
+        _lib.check(min(cnt, 0), "ce_get_plan")
+        buf = (C.c_int * cnt)()
+        L.ce_get_plan(self._h, buf, cnt)
+        return dict(zip(self.PLAN_FIELDS, list(buf)))
+
 
 
 class QuadEpigraph:

@@ -91,8 +91,8 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 11
+ * layout, an entry point's signature or the meaning of an argument changes (12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+#define CE_ABI_VERSION 12
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -317,6 +317,25 @@ int ce_reset_profile(ce_handle h);
  * LDS operand streams).
  * bwd_mode: 0..2 size-generic kernel, 3 k_backward_rt. */
 int ce_get_launch_info(ce_handle h, int *fwd_lds_bytes, int *bwd_lds_bytes, int *fwd_mode, int *bwd_mode);
+/* The whole launch plan of the handle, for tests: writes min(n_out, count) ints to out (may be NULL) and returns count (CE_E_BADARG for a null handle).
+ * Order (fixed; later ABI versions only append):
+ *    0 fwd_mode       as ce_get_launch_info
+ *    1 f2_variant     k_fwd2 register-tile variant 0..4 (-1: not k_fwd2)
+ *    2 rt_variant     k_forward_rt variant 0..2 (-1: none; k_fwd2 may serve the template while this is set)
+ *    3 wl             1: k_fwd2 rows packed so that every cone is wave-local
+ *    4 aa_ok          1: k_fwd2 carries the Anderson-acceleration vectors in LDS
+ *    5 gen_blocked_f  1: the size-generic forward inverts its global-memory G by column panels
+ *    6 qp_native      1: the quadratic objective runs inside the kernels
+ *    7 bwd_mode       as ce_get_launch_info
+ *    8 brt_variant    k_backward_rt variant 0..6 (-1: none)
+ *    9 two_tile       1: calls with adj_status run the two-tile plan of k_backward_rt
+ *   10 ns_variant     as ce_adjoint_ns_variant
+ *   11 gen_blocked_b  1: the size-generic backward eliminates its global-memory K by column panels
+ *   12 sp_r           dense rows (two or more entries) of the A part, when at most 64 (shared-A kernels; else 0)
+ *   13 sp_RP          their padding 16 / 32 / 64 (0: more than 64 dense rows, the batch-GEMM path of the constant-A interface)
+ *   14 last_fast      first tile of the last ce_vjp call when it ran the two-tile plan (-1: the call ran one tile / none yet)
+ * The plan is fixed by ce_create (environment switches included), except last_fast. */
+int ce_get_plan(ce_handle h, int *out, int n_out);
 
 #ifdef __cplusplus
 }
