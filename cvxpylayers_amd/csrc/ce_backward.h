@@ -6,6 +6,17 @@
 // row kinds after classifying DPi_{K*}(v), v = y - s
 enum { RK_EQ = 0, RK_FREE = 1, RK_SOCB = 2, RK_MIX = 3 };   // RK_MIX: rotated PSD row with 0 < DPi eigenvalue < 1
 
+// bytes of k_backward<a_lds, k_lds>'s dynamic LDS: the carve at the top of the kernel, term by term (panel: T.gen_blocked_b, the panels of the blocked elimination)
+__host__ __device__ inline size_t bwd_lds_bytes(const DevT &T, bool a_lds, bool k_lds, int nkcap, int ldk, bool panel = false) {
+    const int n = T.n, m = T.m, PB = imax(NT, imax(n, m)), nqs = imax(T.nq, 1);
+    size_t d = 0;
+    if (a_lds) d += (size_t)m * T.lda;
+    if (k_lds) d += (size_t)nkcap * ldk;
+    d += 5 * (size_t)m + 2 * (size_t)n + 2 * (size_t)nqs * n + 6 * nqs + PB + NW * 8 + bwd_cone_scratch_doubles(T.ns, T.maxs, m, T.nep + T.np, NW);
+    if (!k_lds && panel) d += generic_lu_panel_doubles(nkcap);
+    const size_t ints = 2 * (size_t)m + 2 * nqs + 2 * (size_t)nkcap + 4;      // (perm + colrow)
+    return d * 8 + ints * 4 + 16;
+}
 template <bool A_LDS, bool K_LDS>
 __global__ void __launch_bounds__(NT)
 k_backward(DevT T, int nkcap, int ldk, const double *__restrict__ Avals, const double *__restrict__ xg,

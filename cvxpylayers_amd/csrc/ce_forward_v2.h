@@ -38,11 +38,45 @@ struct F2 {
     static_assert(CHT <= 16 && CHA <= 16 && CHG <= 16, "DPP butterflies stay inside a row of 16 lanes");
 };
 
+// The launch geometry of one variant as plain numbers, for the host's planning table (cone_engine.hip builds one per row of ce_variants.h)
+struct F2Geom { int CHT, T1, CHA, T2, CHG, TG, NTH, MP, NPa, NPg, NP, VP, O_G, LDP; };
+template <int CHT, int T1, int CHA, int T2, int CHG, int TG, int NTH>
+constexpr F2Geom f2_geom() { using L = F2<CHT, T1, CHA, T2, CHG, TG, NTH / 64>; return {CHT, T1, CHA, T2, CHG, TG, NTH, L::MP, L::NPa, L::NPg, L::NP, L::VP, L::O_G, L::LDP}; }
+// leading dimension of G in LDS: smallest even ld >= NPg for which the 16 lanes of an LDS group (CHG segments x 16/CHG rows)
+// read 16 distinct 16-byte bank groups with ds_read_b128
+__host__ __device__ inline int f2_pick_ldg(int CHG, int TG) {
+    const int NPg = CHG * TG;
+    for (int ld = NPg; ld < NPg + 64; ld += 2) {
+        bool used[16] = {false}; bool ok = true;
+        for (int lane = 0; lane < 16 && ok; lane++) {
+            const int jg = lane / CHG, cg = lane % CHG;
+            const int g = ((jg * ld + TG * cg) / 2) % 16;
+            if (used[g]) ok = false; used[g] = true;
+        }
+        if (ok) return ld;
+    }
+    return NPg;
+}
+// whether a template fits the tiles of variant g of k_fwd2; then also ldg and the bytes of the kernel's dynamic LDS without the Anderson-acceleration tail
+// (5 VP more doubles).  The carve: F2's fixed part up to O_G, the SOC row info (2 int arrays = MP doubles), the G region (k_fwd2's gsz), the PSD / triple
+// scratch, P-hat g_x (has_p: the quadratic-objective kind)
+__host__ __device__ inline bool f2_fits(const DevT &T, const F2Geom &g, bool has_p, int *ldg, size_t *bytes) {
+    if ((T.n + 2) * g.CHT > g.NTH || T.m * g.CHA > g.NTH || T.n * g.CHG > g.NTH) return false;   // two extra column groups carry phi
+    if (T.m > g.MP || T.n > g.NPa || T.n > g.NPg || T.n + T.m + 1 > g.NTH) return false;
+    if (T.maxq > SOC_SMALL && T.nq > g.NP) return false;
+    *ldg = f2_pick_ldg(g.CHG, g.TG);
+    if ((size_t)T.n * *ldg < (size_t)g.NPa) return false;
+    size_t gsz = (size_t)T.n * *ldg;                                    // G itself, one 4-row panel of the S formation, the exchange buffers of the blocked inversion
+    if (gsz < (size_t)4 * g.LDP) gsz = (size_t)4 * g.LDP;
+    if (gsz < (size_t)16 * g.NP) gsz = (size_t)16 * g.NP;
+    *bytes = ((size_t)g.O_G + g.MP + gsz + fwd_cone_scratch_doubles(T.ns, T.maxs, T.nep + T.np) + (has_p ? g.NP : 0)) * 8;
+    return true;
+}
+
 // structural zeros of a gathered tile (index -1: the load went through a clamped index, i.e. read entry 0 of THIS instance's values): multiplied by a 0 / 1 mask.
-// The selecting form (-DF2_MASK_MUL=0; ADVICE round 5: a non-finite entry 0 then stays in its own slot instead of turning the tile's structural zeros into NaN)
-// costs two v_cndmask per entry against one v_mul_f64: k_fwd2 1.526 against 1.498 ms, the step 2.18-2.22 against 2.11-2.16 ms on the same box
-// (profiles/r06/o_ab_gather_mask_select_slower.log).  An instance whose entry 0 is not finite has no solution either way -- the mask only decides which of ITS
-// slots carry the NaN -- so the faster form stays.
+// The selecting form (-DF2_MASK_MUL=0) costs two v_cndmask per entry against one v_mul_f64: k_fwd2 1.526 against 1.498 ms, the step 2.18-2.22 against
+// 2.11-2.16 ms on the same box (profiles/r06/o_ab_gather_mask_select_slower.log).  The two forms compute the same tile: gather_tile clears the non-finite
+// bits of the clamped load before the mask is applied, so a non-finite entry 0 does not reach the structural zeros in either form -- and the faster one stays.
 #ifndef F2_MASK_MUL
 #define F2_MASK_MUL 1
 #endif
@@ -403,7 +437,7 @@ k_fwd2(DevT T, ce_settings S, const double *__restrict__ Avals, const double *__
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = T.n, m = T.m, l = n + m + 1, ldg = T.ldg, nq = T.nq, z = T.z;
     const int gsz = max(max(n * ldg, 4 * L::LDP), 16 * NP);        // doubles of the G region: G itself, one 4-row panel of the S formation, the exchange
-                                                                   // buffers of the blocked inversion (cone_engine.hip f2_fits sizes it the same way)
+                                                                   // buffers of the blocked inversion (f2_fits above sizes it the same way)
     const double *const vals = Avals + (size_t)inst * T.nnz_aug;
 
 #ifdef CE_TIMING

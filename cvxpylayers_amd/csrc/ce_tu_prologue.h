@@ -14,3 +14,7 @@
 
 #include "cone_engine.h"
 #include "ce_types.h"
+
+// raise the dynamic-LDS limit of one kernel
+template <class K>
+inline hipError_t ce_set_max_lds(K *kernel, int bytes) { return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }

@@ -48,16 +48,15 @@ struct CeBwdArgs {
     int nonfinal;               // k_backward_rt: 1 = first launch of a two-tile plan (an instance this tile does not hold is not listed: the retry launch serves it)
 };
 
-// launchers (one per kernel object file): 0 on success, -1 unknown variant
+// launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
+// instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
 int ce_launch_fwd2_psd(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);     // + PSD / exponential / power cones
 int ce_launch_fwd2_qp(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);      // quadratic objective inside the kernel
 int ce_launch_fwd_rt(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
-int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones), variants {2|256, 4|256, 7|512}
-size_t ce_bwd_ns_lds_bytes(int n, int m, int nq, int variant);
-hipError_t ce_setattr_bwd_ns(int bytes);
+int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // raise the dynamic-LDS limit of every kernel of the family
@@ -68,4 +67,5 @@ hipError_t ce_setattr_fwd_rt(int bytes);
 hipError_t ce_setattr_fwd_generic(int bytes);
 hipError_t ce_setattr_bwd_rt_plain(int bytes);
 hipError_t ce_setattr_bwd_rt_psd(int bytes);
+hipError_t ce_setattr_bwd_ns(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);

@@ -156,7 +156,7 @@ def _data(fam, v, B, seed):
     return n, m, cones, pat, pstruct, A, b, c, Pm
 
 
-# k_backward_rt tiles {TI, TJ, TH, BGR} (cone_engine.hip BRT_VARIANTS)
+# k_backward_rt tiles {TI, TJ, TH, BGR} (csrc/ce_variants.h CE_BRT_VARIANTS)
 BRT = [(4, 4, 4, 16), (5, 5, 4, 16), (6, 6, 4, 16), (7, 7, 4, 16), (7, 7, 7, 16), (5, 9, 7, 32), (7, 13, 7, 32)]
 
 
