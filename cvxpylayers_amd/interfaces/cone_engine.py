@@ -1,0 +1,362 @@
+"""ConeEngine: one ce_handle (one template, one device) behind the C ABI of include/cone_engine.h."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import warnings
+from contextlib import contextmanager
+from functools import partial
+
+import numpy as np
+import torch
+
+from cvxpylayers_amd import _lib
+from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox
+from cvxpylayers_amd.interfaces.solver_args import _warn_once, unpack_rule
+
+
+def _launch_summary(h, device, vec, out):
+    """ce_status_summary of `vec` into the pinned 4-int row `out`, on the current stream of `device`"""
+    stream = torch.cuda.current_stream(device)
+    _lib.check(_lib.lib().ce_status_summary(h, int(vec.numel()), vec.data_ptr(), out.data_ptr(), C.c_void_p(stream.cuda_stream)), "ce_status_summary")
+
+
+def _synchronize(device, all_streams: bool = False):
+    if all_streams:
+        torch.cuda.synchronize(device)
+    else:
+        torch.cuda.current_stream(device).synchronize()
+
+
+class ConeEngine:
+    """Owns one ce_handle (one template, one device)."""
+
+    def __init__(self, indices, indptr, n, m, cone_dict, device: torch.device, p_structure=None, A_is_constant=None):
+        self._h = None                    # (first: __del__ runs on a half-built engine too)
+        L = _lib.lib()
+        self.device = device
+        self.A_is_constant = A_is_constant          # structural answer of MI355_ctx (parameter map), when the layer supplied it; None: decided per call from the values
+        # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
+        self.last_path = None                 # "per_instance" / "const_a"
+        self.last_acceleration = False        # Anderson acceleration ran
+        self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
+        self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint
+        self.dispatch_history = False         # (the library's default; set_dispatch_history)
+        self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
+        self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
+        self._aa_warned = False
+        self._zero_cache = {}                 # zeros_like_cached
+        self._resolve_rule = None             # (atol, btol, iter_lim) last handed to ce_set_adjoint_resolve
+        self._ca_cache = None                 # const_a: what is derived from the shared matrix alone (equilibration, row split)
+        self.n, self.m = int(n), int(m)
+        self._indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self._indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        self.nnz_aug = int(self._indptr[-1])
+        self.nnzA = int(self._indptr[self.n])
+        self.cone_dict = {k: (list(v) if isinstance(v, (list, tuple, np.ndarray)) else v) for k, v in dict(cone_dict).items()}
+        q = np.ascontiguousarray(cone_dict.get("q", []), dtype=np.int32)
+        s = np.ascontiguousarray(cone_dict.get("s", []), dtype=np.int32)
+        t = _lib.CeTemplate()
+        t.n, t.m, t.nnz_aug = self.n, self.m, self.nnz_aug
+        t.indices = self._indices.ctypes.data_as(C.POINTER(C.c_int))
+        t.indptr = self._indptr.ctypes.data_as(C.POINTER(C.c_int))
+        t.z, t.l = int(cone_dict.get("z", 0)), int(cone_dict.get("l", 0))
+        t.nq, t.q = len(q), q.ctypes.data_as(C.POINTER(C.c_int))
+        t.ns, t.s = len(s), s.ctypes.data_as(C.POINTER(C.c_int))
+        self._pw = np.ascontiguousarray(cone_dict.get("p", []), dtype=np.float64)
+        t.nep, t.np = int(cone_dict.get("ep", 0)), len(self._pw)
+        t.p = self._pw.ctypes.data_as(C.POINTER(C.c_double))
+        self.nnz_p = 0
+        if p_structure is not None:       # quadratic objective: CSC structure of P (n x n)
+            self._p_idx = np.ascontiguousarray(p_structure[0], dtype=np.int32)
+            self._p_ptr = np.ascontiguousarray(p_structure[1], dtype=np.int32)
+            self.nnz_p = int(self._p_ptr[-1])
+            t.nnz_p = self.nnz_p
+            t.p_indices = self._p_idx.ctypes.data_as(C.POINTER(C.c_int))
+            t.p_indptr = self._p_ptr.ctypes.data_as(C.POINTER(C.c_int))
+        h = C.c_void_p()
+        rc = L.ce_create(C.byref(t), device.index or 0, C.byref(h))
+        if rc == -2:
+            raise NotImplementedError(L.ce_last_error().decode())
+        _lib.check(rc, "ce_create")
+        self._h = h
+        self.qp_native = bool(self.nnz_p) and bool(L.ce_qp_native(h))     # P runs inside the kernels (else: epigraph form upstream)
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()          # fixed by ce_create (plan_engine)
+        L.ce_get_launch_info(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        self._launch_info = dict(fwd_lds_bytes=a.value, bwd_lds_bytes=b.value, fwd_mode=c.value, bwd_mode=d.value)
+        # outcome reporting (outcome_mailbox.py); bound to the handle and the device, not to self: no reference cycle keeps a dropped engine's buffers alive
+        self.mailbox = OutcomeMailbox(partial(_launch_summary, h, device), partial(_synchronize, device))
+
+    def set_dispatch_history(self, on: bool):
+        """Longest-first dispatch from the previous call's iteration counts (include/cone_engine.h ce_set_dispatch_history): a scheduling hint, results are
+        bit-identical either way."""
+        _lib.check(_lib.lib().ce_set_dispatch_history(self._h, int(bool(on))), "ce_set_dispatch_history")
+        self.dispatch_history = bool(on)
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().ce_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def to_batch_major(self, A_eval: torch.Tensor) -> torch.Tensor:
+        """(nnz_aug, B) in any layout -> (B, nnz_aug) contiguous fp64 (zero-copy when it already is)."""
+        K, B = A_eval.shape
+        if A_eval.dtype != torch.float64:
+            A_eval = A_eval.double()
+        if B == 0:
+            return A_eval.new_empty((0, K))
+        if A_eval.stride(0) == 1 and (A_eval.stride(1) == K or B == 1):
+            return A_eval.t()
+        if not A_eval.is_contiguous():
+            A_eval = A_eval.contiguous()
+        out = torch.empty((B, K), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.lib().ce_transpose(self._h, K, B, A_eval.data_ptr(), out.data_ptr(), self._stream()), "ce_transpose")
+        return out
+
+    def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None):
+        """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
+        warm = (x, y, s) of shapes (B, n), (B, m), (B, m): initial point (instances with non-finite entries start cold)."""
+        B = A_bm.shape[0]
+        dev = self.device
+        if B == 0:        # empty batch: nothing to launch (the C ABI refuses B <= 0)
+            f64 = dict(dtype=torch.float64, device=dev)
+            self.last_path = "per_instance"
+            return (torch.empty((0, self.n), **f64), torch.empty((0, self.m), **f64), torch.empty((0, self.m), **f64),
+                    torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0, 3), **f64))
+        if warm is not None:
+            if tuple(warm[0].shape) != (B, self.n) or tuple(warm[1].shape) != (B, self.m) or tuple(warm[2].shape) != (B, self.m):
+                raise ValueError(f"warm start: expected x {(B, self.n)}, y {(B, self.m)}, s {(B, self.m)}, got "
+                                 f"{tuple(warm[0].shape)}, {tuple(warm[1].shape)}, {tuple(warm[2].shape)}")
+        if P_bm is not None and not self.qp_native:
+            raise RuntimeError("quadratic objective on an engine without native P support (use the epigraph form)")
+        # direct engine users (tests, probes): vjp() without q_eval may use the objective of the most recent solve() -- but only for the SAME value buffer
+        # (the plugin always passes q_eval explicitly; a q paired with another call's A would silently change the full adjoint system: ADVICE round 5)
+        self._last_q, self._last_q_key = q_eval.detach(), (A_bm.data_ptr(), B)
+        if P_bm is None and self._use_const_a(A_bm):
+            from cvxpylayers_amd.interfaces.const_a import solve_const_a
+            self.last_path = "const_a"
+            return solve_const_a(self, A_bm, q_eval, settings, warm=warm)      # (notes itself whether its kernel honours the acceleration)
+        self.last_path = "per_instance"
+        self._note_acceleration(settings, honoured=bool(_lib.lib().ce_acceleration_available(self._h)), path="size-generic forward kernels")
+        if warm is not None:       # the engine reads the initial point from the output buffers (ce_settings.warm_start)
+            x, y, s = (t.detach().to(device=dev, dtype=torch.float64).clone().contiguous() for t in warm)
+            settings.warm_start = 1
+        else:
+            x = torch.empty((B, self.n), dtype=torch.float64, device=dev)
+            y = torch.empty((B, self.m), dtype=torch.float64, device=dev)
+            s = torch.empty((B, self.m), dtype=torch.float64, device=dev)
+            settings.warm_start = 0
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        resid = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        if P_bm is not None:
+            rc = _lib.lib().ce_solve_qp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
+                                        q_eval.stride(1), P_bm.data_ptr(), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                        iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
+        else:
+            rc = _lib.lib().ce_solve(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
+                                     q_eval.stride(1), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                     iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
+        _lib.check(rc, "ce_solve")
+        return x, y, s, iters, status, resid
+
+    def _recent_q(self, A_bm):
+        return self._last_q if (self._last_q is not None and self._last_q_key == (A_bm.data_ptr(), A_bm.shape[0])) else None
+
+    def zeros_like_cached(self, t: torch.Tensor) -> torch.Tensor:
+        """A read-only zero tensor of t's shape on this engine's device, allocated once per shape (the cotangent of an output the loss does not use)."""
+        cache = self._zero_cache
+        key = tuple(t.shape)
+        z = cache.get(key)
+        if z is None:
+            if len(cache) > 8:
+                cache.clear()
+            z = cache[key] = torch.zeros(key, dtype=torch.float64, device=self.device)
+        return z
+
+    # outcome reporting: delegates to the mailbox (kept for direct engine users)
+    def enqueue_summary(self, vec: torch.Tensor, slot: int):
+        self.mailbox.enqueue(vec, slot)
+
+    def ensure_summary(self, slot: int):
+        self.mailbox.ensure(slot)
+
+    def read_summaries(self):
+        return self.mailbox.read()
+
+    def status_summary(self, status: torch.Tensor) -> tuple[int, int]:
+        """(min status, number of Solved/Inaccurate) of a status vector on this engine's device: one launch + a 12-byte pinned copy + one stream sync."""
+        if status.numel() == 0:
+            return 1, 0
+        with torch.cuda.device(self.device):
+            self.mailbox.enqueue(status, 0)
+            r = self.mailbox.read()
+        return int(r[0][0]), int(r[0][1])
+
+    def _note_acceleration(self, settings, honoured: bool, path: str):
+        """Records whether this solve ran with Anderson acceleration (`last_acceleration`, surfaced as info["acceleration"]) and warns
+        ONCE per engine when a positive acceleration_lookback -- explicit or the SCS default -- is not honoured by the selected path."""
+        self.last_acceleration = bool(settings.acceleration_lookback > 0 and honoured)
+        if settings.acceleration_lookback > 0 and not honoured and not self._aa_warned:
+            self._aa_warned = True
+            warnings.warn(f"MI355 solver: acceleration_lookback={settings.acceleration_lookback} is not implemented on the {path}; "
+                          "iterating without Anderson acceleration (pass acceleration_lookback=0 to silence this)")
+
+    def _use_const_a(self, A_bm) -> bool:
+        """The batch-GEMM path pays off when the instance is too large for the register / LDS-resident kernels (those are
+        faster for small instances even when A is shared).  CE_CONST_A=1 forces it whenever A is batch-invariant, =0 disables it."""
+        from cvxpylayers_amd.interfaces.const_a import is_constant_A
+        env = os.environ.get("CE_CONST_A")
+        if env == "0" or A_bm.shape[0] < 2:
+            return False
+        if env != "1" and self._launch_info["fwd_mode"] not in (1, 2):
+            return False
+        if self.A_is_constant is not None:
+            return bool(self.A_is_constant)
+        return is_constant_A(A_bm, self.nnzA)
+
+    def vjp(self, A_bm, x, y, s, dx, dy, batch_minor_out: bool = False, P_bm=None, path: str | None = None, lsqr: tuple | None = None, q_eval=None):
+        """Returns dA (nnz_aug, B), dq (n+1, B), adj_status (B,).  dA is a transposed view of a batch-major buffer (the
+        engine-native layout, no extra pass) unless batch_minor_out: then it is (nnz_aug, B) contiguous -- the layout of a
+        reference-style A_eval, so that autograd can accumulate it into the leaf without a strided copy (one engine layout pass).
+        path: the path ("per_instance" / "const_a") of the forward call being differentiated, as recorded by the caller right
+        after solve() -- the autograd node keeps it, so interleaved forward calls of one layer cannot redirect a pending backward.
+        None (direct engine users with one solve in flight): the path of the most recent solve().
+        lsqr: (atol, btol, iter_lim[, system]) of the shared-A LSQR adjoint (lsqr_rule); None = diffcp's 1e-8 / 1e-8 / 2 (n + m + 1) on the full system.  Ignored by the direct eliminations.
+        q_eval: the forward call's (n+1, B) objective values; the shared-A LSQR adjoint then solves diffcp's full (n + m + 1) system (const_a.vjp_const_a)."""
+        B = A_bm.shape[0]
+        dev = self.device
+        if B == 0:
+            return (torch.empty((self.nnz_aug, 0), dtype=torch.float64, device=dev), torch.empty((self.n + 1, 0), dtype=torch.float64, device=dev),
+                    torch.empty((0,), dtype=torch.int32, device=dev))
+        if path is None:
+            path = self.last_path
+        if path == "const_a" and (self._launch_info["bwd_mode"] in (1, 2) or os.environ.get("CE_CONST_A") == "1"):
+            from cvxpylayers_amd.interfaces.const_a import vjp_const_a      # shared A: batched LSQR with GEMMs over the batch
+            if q_eval is None:          # direct engine users: the objective of the most recent solve() of this very value buffer, else the reduced system
+                q_eval = self._recent_q(A_bm)
+            atol, btol, lim, system, method = unpack_rule(lsqr, self.n, self.m)
+            if system == "reduced":
+                q_eval = None
+            with self._lsqr_variant(method):
+                return vjp_const_a(self, A_bm, x, y, s, dx, dy, batch_minor_out=batch_minor_out, atol=atol, btol=btol, iter_lim=lim, q_eval=q_eval)
+        if path == "per_instance_lsqr":      # solver_args mode="lsqr" on a per-instance-A template: diffcp's LSQR instead of the direct elimination
+            if P_bm is not None:
+                raise ValueError("MI355 solver: mode='lsqr' is not available with a quadratic objective inside the kernels (CE_QP_EPIGRAPH=1 brings the problem to cone form)")
+            atol, btol, lim, system, method = unpack_rule(lsqr, self.n, self.m)
+            if q_eval is None and system != "reduced":
+                q_eval = self._recent_q(A_bm)
+            with self._lsqr_variant(method):
+                out = self._vjp_lsqr(A_bm, x, y, s, dx, dy, batch_minor_out, atol, btol, lim, None if system == "reduced" else q_eval)
+            if out is not None:
+                return out
+            path = "per_instance"          # (the LSQR vectors of one instance exceed LDS: warned once, the direct elimination + re-solve serves the call)
+        dq = torch.empty((self.n + 1, B), dtype=torch.float64, device=dev)
+        adj = torch.empty((B,), dtype=torch.int32, device=dev)
+        # rank-deficient instances are re-solved on the device by diffcp's LSQR when the call's q_eval is at hand (ce_vjp); path "per_instance_dense" (solver_args
+        # mode="dense") keeps the elimination's basic solution
+        resolve = P_bm is None and q_eval is not None and path != "per_instance_dense"          # (q_eval must be given explicitly here: without it, the elimination alone)
+        qd, q_args = self._q_args(q_eval if resolve else None)
+        if resolve:
+            rule = unpack_rule(lsqr, self.n, self.m)[:4]
+            if rule[:3] != self._resolve_rule:
+                _lib.check(_lib.lib().ce_set_adjoint_resolve(self._h, 1, float(rule[0]), float(rule[1]), 1e8, int(rule[2])), "ce_set_adjoint_resolve")
+                self._resolve_rule = rule[:3]
+        if batch_minor_out:
+            dA = torch.empty((self.nnz_aug, B), dtype=torch.float64, device=dev)
+            sk, sb = B, 1
+        else:
+            dA = torch.empty((B, self.nnz_aug), dtype=torch.float64, device=dev)
+            sk, sb = 1, self.nnz_aug
+        if P_bm is not None:      # quadratic objective: also dP (B, nnz_p) batch-major
+            dP = torch.empty((B, self.nnz_p), dtype=torch.float64, device=dev)
+            rc = _lib.lib().ce_vjp_qp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, P_bm.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                      s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
+                                      dq.data_ptr(), B, 1, dP.data_ptr(), adj.data_ptr(), self._stream())
+            _lib.check(rc, "ce_vjp_qp")
+            return (dA if batch_minor_out else dA.t()), dq, adj, dP
+        rc = _lib.lib().ce_vjp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(),
+                               s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
+                               dq.data_ptr(), B, 1, adj.data_ptr(), self._stream())
+        _lib.check(rc, "ce_vjp")
+        return (dA if batch_minor_out else dA.t()), dq, adj
+
+    def _q_args(self, q_eval):
+        """(tensor to keep alive, (pointer, stride0, stride1)) of an optional (n+1, B) objective as the C ABI takes it; None -> (None, (None, 0, 0))"""
+        if q_eval is None:
+            return None, (None, 0, 0)
+        qd = q_eval.detach().to(dtype=torch.float64, device=self.device)
+        return qd, (qd.data_ptr(), qd.stride(0), qd.stride(1))
+
+    @contextmanager
+    def _lsqr_variant(self, method: str):
+        """the iterative adjoints run LSMR's recurrences inside the block ("lsmr"), LSQR's otherwise and after it (ce_set_lsqr_variant)"""
+        _lib.check(_lib.lib().ce_set_lsqr_variant(self._h, 1 if method == "lsmr" else 0), "ce_set_lsqr_variant")
+        try:
+            yield
+        finally:
+            _lib.lib().ce_set_lsqr_variant(self._h, 0)
+
+    def lsqr_one_kernel(self, fn, name, A_ptr, A_stride, B, x, y, s, dx, dy, batch_minor_out, atol, btol, iter_lim, q_eval, conlim):
+        """The one-kernel LSQR adjoints, ce_vjp_lsqr (per-instance A) and ce_vjp_shared_a (one A): the same signature around the (A pointer, row stride) pair.
+        Returns dA, dq, adj -- or None when the library says the template does not fit this kernel (rc -2 / -3: the caller falls through)."""
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        dA_bm = torch.empty((B, self.nnz_aug), **f64); dq = torch.empty((self.n + 1, B), **f64)
+        adj = torch.empty((B,), dtype=torch.int32, device=dev); its = torch.empty((B,), dtype=torch.int32, device=dev)
+        xc, yc, sc_, dxc, dyc = (t.to(torch.float64).contiguous() for t in (x, y, s, dx, dy))
+        qd, q_args = self._q_args(q_eval)
+        rc = fn(self._h, B, A_ptr, A_stride, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dxc.data_ptr(), dyc.data_ptr(),
+                dA_bm.data_ptr(), dq.data_ptr(), B, 1, adj.data_ptr(), its.data_ptr(), float(atol), float(btol), float(conlim), int(iter_lim), self._stream())
+        if rc in (-2, -3):
+            return None
+        _lib.check(rc, name)
+        self.last_lsqr_iters = its
+        return (dA_bm.t().contiguous() if batch_minor_out else dA_bm.t()), dq, adj
+
+    def _vjp_lsqr(self, A_bm, x, y, s, dx, dy, batch_minor_out, atol, btol, iter_lim, q_eval, conlim=1e8):
+        """ce_vjp_lsqr: one workgroup per instance runs Paige & Saunders' LSQR on diffcp's adjoint system M^T r = dz with THIS instance's A (include/cone_engine.h)"""
+        B = A_bm.shape[0]
+        A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) >= self.nnz_aug)) else A_bm.contiguous()
+        out = self.lsqr_one_kernel(_lib.lib().ce_vjp_lsqr, "ce_vjp_lsqr", A_c.data_ptr(), A_c.stride(0), B, x, y, s, dx, dy, batch_minor_out, atol, btol, iter_lim, q_eval, conlim)
+        if out is None:          # CE_E_TOO_LARGE: mode="lsqr" cannot be honoured for this template
+            _warn_once("lsqr_too_large", "MI355 solver: solver_args mode='lsqr' needs the LSQR vectors of one instance in LDS, which this template exceeds; "
+                                         "falling back to the direct elimination (rank-deficient instances are flagged in info['adjoint'])")
+        return out
+
+    # introspection (bench / tests)
+    def set_profiling(self, on):
+        """False / True, or a sum of 2 (forward), 4 (adjoint), 8 (layout passes): which launches are bracketed by HIP events (include/cone_engine.h)"""
+        _lib.lib().ce_set_profiling(self._h, int(on))
+
+    def reset_profile(self):
+        _lib.lib().ce_reset_profile(self._h)
+
+    def profile(self, which: int):
+        ms, nl = C.c_double(), C.c_int()
+        _lib.check(_lib.lib().ce_get_profile(self._h, which, C.byref(ms), C.byref(nl)), "ce_get_profile")
+        return ms.value, nl.value
+
+    def launch_info(self):
+        """LDS footprints and modes of the launch plan, read once at construction (a copy: callers may keep or change it)"""
+        return dict(self._launch_info)
+
+    PLAN_FIELDS = ("fwd_mode", "f2_variant", "rt_variant", "wl", "aa_ok", "gen_blocked_f", "qp_native",
+                   "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_r", "sp_RP", "last_fast")
+
+    def plan(self):
+        """The whole launch plan (include/cone_engine.h ce_get_plan) as a dict keyed by PLAN_FIELDS.  Read from the library on every call, unlike
+        launch_info(): its last entry, last_fast, is the first tile of the most recent two-tile adjoint call and changes from call to call
+        (tests/test_gpu_plan_edges.py reads it between calls).  Nothing on the solve / vjp path calls this."""
+        L = _lib.lib()
+        cnt = L.ce_get_plan(self._h, None, 0)
+        _lib.check(min(cnt, 0), "ce_get_plan")
+        buf = (C.c_int * cnt)()
+        L.ce_get_plan(self._h, buf, cnt)
+        return dict(zip(self.PLAN_FIELDS, list(buf)))

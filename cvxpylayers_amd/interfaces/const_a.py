@@ -17,6 +17,8 @@ frozen at their own iteration.  Cones: zero / nonnegative / second-order.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import time
 
 import numpy as np
 import torch
@@ -75,70 +77,153 @@ def is_constant_A(A_bm: torch.Tensor, nnzA: int) -> bool:
     return bool((A_bm[:, :nnzA] == A_bm[0:1, :nnzA]).all().item())
 
 
+class _Ticker:
+    """CE_CA_TIMING=1: prints the wall time between stages (synchronises; off by default)"""
+
+    def __init__(self):
+        self.on, self.t = os.environ.get("CE_CA_TIMING") == "1", None
+
+    def __call__(self, tag):
+        if self.on:
+            torch.cuda.synchronize(); now = time.perf_counter()
+            if self.t is not None: print(f"[const_a] {tag}: {(now - self.t) * 1e3:.1f} ms")
+            self.t = now
+
+
+def _cone_sizes(eng, dev):
+    """z, nl, qs, PSD blocks, number of exponential / power cone triples (after the PSD blocks)"""
+    cone = eng.cone_dict
+    return (int(cone.get("z", 0)), int(cone.get("l", 0)), [int(v) for v in cone.get("q", [])], _psd_blocks(cone, dev),
+            int(cone.get("ep", 0)) + len(cone.get("p", [])))
+
+
+def _shared_matrix(eng, A_bm, settings):
+    """Dense A (solver form: A = -A_cvx) of the one shared matrix, equilibrated, with its row and column scalings D, E.
+    Everything derived from the shared matrix alone (its equilibration: 26 passes of small torch kernels, ~4 ms of launches) is kept on the
+    engine (eng._ca_cache) and reused while the caller keeps handing over the same values -- the usual case: A is a constant of the layer."""
+    dev, n, m = A_bm.device, eng.n, eng.m
+    indices, nnzA = eng._indices, eng.nnzA
+    f64 = dict(dtype=torch.float64, device=dev)
+    A_vals0 = A_bm[0, :nnzA]
+    cache = eng._ca_cache
+    if cache is not None and cache["normalize"] == bool(settings.normalize) and cache["A0"].shape == A_vals0.shape and torch.equal(cache["A0"], A_vals0):
+        return cache["A"], cache["D"], cache["E"]
+    z, nl, qs, psd, ntri = _cone_sizes(eng, dev)
+    cols = np.repeat(np.arange(n + 1), np.diff(eng._indptr))
+    A = torch.zeros((m, n), **f64)
+    A[torch.from_numpy(indices[:nnzA].astype(np.int64)).to(dev), torch.from_numpy(cols[:nnzA].astype(np.int64)).to(dev)] = -A_vals0
+    # ---- equilibration of the one shared matrix (25 Ruiz passes + 1 l2 pass, row scalings averaged inside SOC blocks)
+    D = torch.ones(m, **f64); E = torch.ones(n, **f64)
+    if settings.normalize:
+        blk = torch.full((m,), -1, dtype=torch.int64, device=dev)
+        off = z + nl
+        blocks = qs + [pb.d for pb in psd] + [3] * ntri      # row scalings are averaged inside SOC / PSD blocks and exp / power triples alike
+        for k, d in enumerate(blocks):
+            blk[off:off + d] = k
+            off += d
+        soc_rows = (blk >= 0).nonzero().flatten()
+        cnt = torch.tensor(blocks, **f64) if blocks else None
+        for p in range(NUM_RUIZ_PASSES + NUM_L2_PASSES):
+            if p >= NUM_RUIZ_PASSES:
+                Dt, Et = A.norm(dim=1), A.norm(dim=0)
+            else:
+                Dt, Et = A.abs().amax(dim=1), A.abs().amax(dim=0)
+            if blocks:
+                avg = torch.zeros(len(blocks), **f64).index_add_(0, blk[soc_rows], Dt[soc_rows]) / cnt
+                Dt = Dt.clone(); Dt[soc_rows] = avg[blk[soc_rows]]
+            Dt = 1.0 / torch.sqrt(_clamp_scale(Dt)); Et = 1.0 / torch.sqrt(_clamp_scale(Et))
+            A = Dt[:, None] * A * Et[None, :]
+            D = D * Dt; E = E * Et
+    eng._ca_cache = dict(A0=A_vals0.clone(), normalize=bool(settings.normalize), A=A, D=D, E=E)
+    return A, D, E
+
+
+def _row_split(eng, A):
+    """The singleton / dense-row split of the shared matrix (ce_shared_a_fwd.h): A = (rows with one entry) + (r_d <= 64 rows with several), kept in
+    eng._ca_cache["split"] next to the equilibrated matrix it was taken from.  Without "stable" (or with r_d > 64) only r_d, RP and stable are there."""
+    split = eng._ca_cache.get("split")
+    if split is not None:
+        return split
+    dev, n, m = A.device, eng.n, eng.m
+    indices, nnzA = eng._indices, eng.nnzA
+    f64 = dict(dtype=torch.float64, device=dev)
+    z = int(eng.cone_dict.get("z", 0))
+    cols = np.repeat(np.arange(n + 1), np.diff(eng._indptr))
+    row_nnz = np.bincount(indices[:nnzA], minlength=m)
+    drows_np = np.nonzero(row_nnz >= 2)[0].astype(np.int32)
+    r_d = int(len(drows_np))
+    RP = 16 if r_d <= 16 else (32 if r_d <= 32 else 64)
+    split = dict(r_d=r_d, RP=RP, stable=False)
+    if r_d <= 64:
+        srow = (row_nnz == 1)
+        ent_rows = indices[:nnzA].astype(np.int64); ent_cols = cols[:nnzA].astype(np.int64)
+        sing = srow[ent_rows]                                          # structural entries that sit in single-entry rows
+        srow_col_np = np.full(m, -1, dtype=np.int32); srow_col_np[drows_np] = -2 - np.arange(r_d, dtype=np.int32); srow_col_np[ent_rows[sing]] = ent_cols[sing]      # >= 0 column of a singleton row, -2 - a: dense row in slot a, -1 empty row
+        order = np.argsort(ent_cols[sing], kind="stable")
+        scol_row_np = ent_rows[sing][order].astype(np.int32)
+        scol_ptr_np = np.concatenate([[0], np.cumsum(np.bincount(ent_cols[sing], minlength=n))]).astype(np.int32)
+        ti32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        drow_t, srow_col_t, scol_ptr_t, scol_row_t = ti32(drows_np if r_d else np.zeros(1)), ti32(srow_col_np), ti32(scol_ptr_np), ti32(scol_row_np if len(scol_row_np) else np.zeros(1))
+        srow_val = torch.zeros(m, **f64)
+        if sing.any():
+            rs_t = torch.from_numpy(ent_rows[sing]).to(dev); cs_t = torch.from_numpy(ent_cols[sing]).to(dev)
+            srow_val[rs_t] = A[rs_t, cs_t]
+        AdT = torch.zeros((n, RP), **f64)
+        if r_d:
+            AdT[:, :r_d] = A[torch.from_numpy(drows_np.astype(np.int64)).to(dev), :].t()
+        d0s = torch.ones(m, **f64); d0s[:z] = ZERO_CONE_FACTOR
+        gs = torch.zeros(n, **f64)
+        if sing.any():
+            gs.index_add_(0, cs_t, d0s[rs_t] * srow_val[rs_t] ** 2)
+        # Woodbury is only stable when the diagonal part carries weight in EVERY column (each variable sits in some single-entry row:
+        # bounds, identity blocks); a column without one has Dg_j = rho_x = 1e-6 and the formula cancels catastrophically
+        split.update(stable=bool((gs.min() >= 1e-2).item()) if n else False, drow_t=drow_t, srow_col_t=srow_col_t, scol_ptr_t=scol_ptr_t,
+                     scol_row_t=scol_row_t, srow_val=srow_val, AdT=AdT, gs=gs)
+    eng._ca_cache["split"] = split
+    return split
+
+
+def _solve_one_kernel(eng, split, B, D, E, bh, ch, sigma, nrm_b0, nrm_c0, settings, warm):
+    """ce_solve_shared_a (k_sa_fwd): every iterate of an instance stays in LDS, no host round trips.  Returns x, y, s, iters, status, resid, or None
+    when the library says the iterates do not fit (rc -2 / -3: the batch-GEMM loop serves the call)."""
+    dev, n, m = bh.device, eng.n, eng.m
+    f64 = dict(dtype=torch.float64, device=dev)
+    r_d, RP = split["r_d"], split["RP"]
+    drow_t, srow_col_t, scol_ptr_t, scol_row_t, srow_val, AdT, gs = (split[k] for k in ("drow_t", "srow_col_t", "scol_ptr_t", "scol_row_t", "srow_val", "AdT", "gs"))
+    xo = torch.empty((B, n), **f64); yo = torch.empty((B, m), **f64); so = torch.empty((B, m), **f64)
+    it_o = torch.empty(B, dtype=torch.int32, device=dev); st_o = torch.empty(B, dtype=torch.int32, device=dev); rs_o = torch.empty((B, 3), **f64)
+    wx = wy = ws = None
+    settings.warm_start = 0
+    if warm is not None:
+        wx, wy, ws = (t.detach().to(device=dev, dtype=torch.float64).contiguous() for t in warm)
+        settings.warm_start = 1
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    rc = _lib.lib().ce_solve_shared_a(eng._h, B, r_d, RP, AdT.data_ptr(), drow_t.data_ptr(), srow_col_t.data_ptr(), srow_val.data_ptr(), scol_ptr_t.data_ptr(),
+                                      scol_row_t.data_ptr(), gs.data_ptr(), D.data_ptr(), E.data_ptr(), bh.data_ptr(), ch.data_ptr(), sigma.data_ptr(),
+                                      nrm_b0.data_ptr(), nrm_c0.data_ptr(), C.byref(settings), ptr(wx), ptr(wy), ptr(ws), xo.data_ptr(), yo.data_ptr(),
+                                      so.data_ptr(), it_o.data_ptr(), st_o.data_ptr(), rs_o.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc in (-2, -3):
+        return None
+    _lib.check(rc, "ce_solve_shared_a")
+    eng._note_acceleration(settings, honoured=True, path="shared-A forward kernel")     # k_sa_fwd implements it (one-pair history, like k_fwd2)
+    eng.last_const_a_kernel = "k_sa_fwd"
+    return xo, yo, so, it_o, st_o, rs_o
+
+
 def solve_const_a(eng, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None):
     """eng: ConeEngine; A_bm (B, nnz_aug) batch-major values of [A_cvx | b_cvx]; q_eval (n+1, B).  Returns x, y, s, iters, status, resid."""
-    import os, time
-    _timing = os.environ.get("CE_CA_TIMING") == "1"
-    def _tick(tag, _t=[None]):
-        if _timing:
-            torch.cuda.synchronize(); now = time.perf_counter()
-            if _t[0] is not None: print(f"[const_a] {tag}: {(now - _t[0]) * 1e3:.1f} ms")
-            _t[0] = now
-    _tick("start")
-    L = _lib.lib()
-    dev = A_bm.device
-    n, m = eng.n, eng.m
-    B = A_bm.shape[0]
-    l = n + m + 1
-    lp = l + (l & 1)                         # even row pitch
-    indices, indptr = eng._indices, eng._indptr
-    nnzA = int(indptr[n])
-    cols = np.repeat(np.arange(n + 1), np.diff(indptr))
+    tick = _Ticker()
+    tick("start")
+    dev, n, m, B = A_bm.device, eng.n, eng.m, A_bm.shape[0]
+    nnzA = eng.nnzA
     f64 = dict(dtype=torch.float64, device=dev)
-    # ---- dense A (solver form: A = -A_cvx), b (B, m), c (B, n)
+    # ---- b (B, m), c (B, n) of every instance
     b = torch.zeros((B, m), **f64)
     if eng.nnz_aug > nnzA:
-        b[:, torch.from_numpy(indices[nnzA:].astype(np.int64)).to(dev)] = A_bm[:, nnzA:]
+        b[:, torch.from_numpy(eng._indices[nnzA:].astype(np.int64)).to(dev)] = A_bm[:, nnzA:]
     c = q_eval[:n].t().to(torch.float64).contiguous()
-    cone = eng.cone_dict
-    z, nl, qs = int(cone.get("z", 0)), int(cone.get("l", 0)), [int(v) for v in cone.get("q", [])]
-    psd = _psd_blocks(cone, dev)
-    ntri = int(cone.get("ep", 0)) + len(cone.get("p", []))       # exponential / power cone triples (after the PSD blocks)
-    # Everything derived from the shared matrix alone (its equilibration: 26 passes of small torch kernels, ~4 ms of launches) is kept on the
-    # engine and reused while the caller keeps handing over the same values -- the usual case: A is a constant of the layer.
-    A_vals0 = A_bm[0, :nnzA]
-    cache = getattr(eng, "_ca_cache", None)
-    if cache is not None and cache["normalize"] == bool(settings.normalize) and cache["A0"].shape == A_vals0.shape and torch.equal(cache["A0"], A_vals0):
-        A, D, E = cache["A"], cache["D"], cache["E"]
-    else:
-        cache = None
-        A = torch.zeros((m, n), **f64)
-        A[torch.from_numpy(indices[:nnzA].astype(np.int64)).to(dev), torch.from_numpy(cols[:nnzA].astype(np.int64)).to(dev)] = -A_vals0
-        # ---- equilibration of the one shared matrix (25 Ruiz passes + 1 l2 pass, row scalings averaged inside SOC blocks)
-        D = torch.ones(m, **f64); E = torch.ones(n, **f64)
-        if settings.normalize:
-            blk = torch.full((m,), -1, dtype=torch.int64, device=dev)
-            off = z + nl
-            blocks = qs + [pb.d for pb in psd] + [3] * ntri      # row scalings are averaged inside SOC / PSD blocks and exp / power triples alike
-            for k, d in enumerate(blocks):
-                blk[off:off + d] = k
-                off += d
-            soc_rows = (blk >= 0).nonzero().flatten()
-            cnt = torch.tensor(blocks, **f64) if blocks else None
-            for p in range(NUM_RUIZ_PASSES + NUM_L2_PASSES):
-                if p >= NUM_RUIZ_PASSES:
-                    Dt, Et = A.norm(dim=1), A.norm(dim=0)
-                else:
-                    Dt, Et = A.abs().amax(dim=1), A.abs().amax(dim=0)
-                if blocks:
-                    avg = torch.zeros(len(blocks), **f64).index_add_(0, blk[soc_rows], Dt[soc_rows]) / cnt
-                    Dt = Dt.clone(); Dt[soc_rows] = avg[blk[soc_rows]]
-                Dt = 1.0 / torch.sqrt(_clamp_scale(Dt)); Et = 1.0 / torch.sqrt(_clamp_scale(Et))
-                A = Dt[:, None] * A * Et[None, :]
-                D = D * Dt; E = E * Et
-        eng._ca_cache = dict(A0=A_vals0.clone(), normalize=bool(settings.normalize), A=A, D=D, E=E)
-    _tick("extract + equilibrate")
-    At = A.t().contiguous()
+    A, D, E = _shared_matrix(eng, A_bm, settings)
+    tick("extract + equilibrate")
     nrm_b0 = b.abs().amax(dim=1) if m else torch.zeros(B, **f64)
     nrm_c0 = c.abs().amax(dim=1)
     bh = b * D; ch = c * E
@@ -151,64 +236,25 @@ def solve_const_a(eng, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=
     #      is diagonal + rank r and is applied by the Woodbury identity; every iterate of an instance stays in LDS, no host round trips.
     #      Taken whenever the template has that shape, the Woodbury form is stable and the iterates fit LDS (measured against the batch-GEMM
     #      path below: 28 vs 40 ms at BASELINE config 4, 420 vs 480 ms at config 5 with B = 16384); CE_SA_FWD=0 disables.
-    _saf = os.environ.get("CE_SA_FWD")
-    if _saf != "0":
-        split = eng._ca_cache.get("split")
-        if split is None:
-            row_nnz = np.bincount(indices[:nnzA], minlength=m)
-            drows_np = np.nonzero(row_nnz >= 2)[0].astype(np.int32)
-            r_d = int(len(drows_np))
-            RP = 16 if r_d <= 16 else (32 if r_d <= 32 else 64)
-            split = dict(r_d=r_d, RP=RP, stable=False)
-            if r_d <= 64:
-                srow = (row_nnz == 1)
-                ent_rows = indices[:nnzA].astype(np.int64); ent_cols = cols[:nnzA].astype(np.int64)
-                sing = srow[ent_rows]                                          # structural entries that sit in single-entry rows
-                srow_col_np = np.full(m, -1, dtype=np.int32); srow_col_np[drows_np] = -2 - np.arange(r_d, dtype=np.int32); srow_col_np[ent_rows[sing]] = ent_cols[sing]      # >= 0 column of a singleton row, -2 - a: dense row in slot a, -1 empty row
-                order = np.argsort(ent_cols[sing], kind="stable")
-                scol_row_np = ent_rows[sing][order].astype(np.int32)
-                scol_ptr_np = np.concatenate([[0], np.cumsum(np.bincount(ent_cols[sing], minlength=n))]).astype(np.int32)
-                ti32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-                drow_t, srow_col_t, scol_ptr_t, scol_row_t = ti32(drows_np if r_d else np.zeros(1)), ti32(srow_col_np), ti32(scol_ptr_np), ti32(scol_row_np if len(scol_row_np) else np.zeros(1))
-                srow_val = torch.zeros(m, **f64)
-                if sing.any():
-                    rs_t = torch.from_numpy(ent_rows[sing]).to(dev); cs_t = torch.from_numpy(ent_cols[sing]).to(dev)
-                    srow_val[rs_t] = A[rs_t, cs_t]
-                AdT = torch.zeros((n, RP), **f64)
-                if r_d:
-                    AdT[:, :r_d] = A[torch.from_numpy(drows_np.astype(np.int64)).to(dev), :].t()
-                d0s = torch.ones(m, **f64); d0s[:z] = ZERO_CONE_FACTOR
-                gs = torch.zeros(n, **f64)
-                if sing.any():
-                    gs.index_add_(0, cs_t, d0s[rs_t] * srow_val[rs_t] ** 2)
-                # Woodbury is only stable when the diagonal part carries weight in EVERY column (each variable sits in some single-entry row:
-                # bounds, identity blocks); a column without one has Dg_j = rho_x = 1e-6 and the formula cancels catastrophically
-                split.update(stable=bool((gs.min() >= 1e-2).item()) if n else False, drow_t=drow_t, srow_col_t=srow_col_t, scol_ptr_t=scol_ptr_t,
-                             scol_row_t=scol_row_t, srow_val=srow_val, AdT=AdT, gs=gs)
-            eng._ca_cache["split"] = split
-        r_d, RP, stable = split["r_d"], split["RP"], split["stable"]
-        if r_d <= 64 and stable:
-            drow_t, srow_col_t, scol_ptr_t, scol_row_t, srow_val, AdT, gs = (split[k] for k in ("drow_t", "srow_col_t", "scol_ptr_t", "scol_row_t", "srow_val", "AdT", "gs"))
-        if r_d <= 64 and stable:
-            xo = torch.empty((B, n), **f64); yo = torch.empty((B, m), **f64); so = torch.empty((B, m), **f64)
-            it_o = torch.empty(B, dtype=torch.int32, device=dev); st_o = torch.empty(B, dtype=torch.int32, device=dev); rs_o = torch.empty((B, 3), **f64)
-            wx = wy = ws = None
-            settings.warm_start = 0
-            if warm is not None:
-                wx, wy, ws = (t.detach().to(device=dev, dtype=torch.float64).contiguous() for t in warm)
-                settings.warm_start = 1
-            ptr = lambda t: t.data_ptr() if t is not None else None
-            rc = L.ce_solve_shared_a(eng._h, B, r_d, RP, AdT.data_ptr(), drow_t.data_ptr(), srow_col_t.data_ptr(), srow_val.data_ptr(), scol_ptr_t.data_ptr(),
-                                     scol_row_t.data_ptr(), gs.data_ptr(), D.data_ptr(), E.data_ptr(), bh.data_ptr(), ch.data_ptr(), sigma.data_ptr(),
-                                     nrm_b0.data_ptr(), nrm_c0.data_ptr(), C.byref(settings), ptr(wx), ptr(wy), ptr(ws), xo.data_ptr(), yo.data_ptr(),
-                                     so.data_ptr(), it_o.data_ptr(), st_o.data_ptr(), rs_o.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc == 0:
-                eng._note_acceleration(settings, honoured=True, path="shared-A forward kernel")     # k_sa_fwd implements it (one-pair history, like k_fwd2)
-                eng.last_const_a_kernel = "k_sa_fwd"
-                _tick("k_sa_fwd (enqueued)")
-                return xo, yo, so, it_o, st_o, rs_o
-            if rc not in (-2, -3):
-                _lib.check(rc, "ce_solve_shared_a")
+    if os.environ.get("CE_SA_FWD") != "0":
+        split = _row_split(eng, A)
+        if split["r_d"] <= 64 and split["stable"]:
+            out = _solve_one_kernel(eng, split, B, D, E, bh, ch, sigma, nrm_b0, nrm_c0, settings, warm)
+            if out is not None:
+                tick("k_sa_fwd (enqueued)")
+                return out
+    return _solve_batch_gemm(eng, A, D, E, bh, ch, sigma, nrm_b0, nrm_c0, settings, warm, tick)
+
+
+def _solve_batch_gemm(eng, A, D, E, bh, ch, sigma, nrm_b0, nrm_c0, settings, warm, _tick):
+    """The batch-GEMM loop: the three matrix products of the iteration as fp64 GEMMs over the whole batch, the per-instance remainder in the ce_ca_* kernels."""
+    L = _lib.lib()
+    dev, n, m, B = bh.device, eng.n, eng.m, bh.shape[0]
+    l = n + m + 1
+    lp = l + (l & 1)                         # even row pitch
+    f64 = dict(dtype=torch.float64, device=dev)
+    z, nl, qs, psd, ntri = _cone_sizes(eng, dev)
+    At = A.t().contiguous()
     eng.last_const_a_kernel = "batch GEMM"
     eng._note_acceleration(settings, honoured=False, path="constant-A batch-GEMM path")
     # ---- one eigendecomposition serves every instance and every rescale:  A^T D0 A = Q Lam Q^T
@@ -429,42 +475,27 @@ def _psd_eig(v, psd):
 def vjp_const_a(eng, A_bm, x, y, s, dx, dy, batch_minor_out=False, atol=1e-8, btol=1e-8, iter_lim=0, q_eval=None, conlim=1e8):
     """Returns dA (nnz_aug, B), dq (n+1, B), adj_status (B,) in the boundary convention (diffcp_if.py:91-92).
     atol / btol / iter_lim: LSQR's stopping rule; the defaults are diffcp's (1e-8, 1e-8, 2 N with N = n + m + 1: what diffcp_if.py:86 runs and
-    oracle/cone_oracle.c:85,712 restates); the plugin forwards solver_args["lsqr_atol" / "lsqr_btol" / "lsqr_iter_lim"] (mi355_if.lsqr_rule).
+    oracle/cone_oracle.c:85,712 restates); the plugin forwards solver_args["lsqr_atol" / "lsqr_btol" / "lsqr_iter_lim"] (solver_args.lsqr_rule).
     q_eval (n+1, B): the forward call's objective values.  With them the one-kernel LSQR solves diffcp's FULL (n + m + 1) system (tau row and column: b and c
     enter); without them r_tau is pinned to 0 -- the same gradients wherever the system is regular, a different minimum-norm element on degenerate faces."""
     if iter_lim <= 0:
         iter_lim = 2 * (eng.n + eng.m + 1)
     dev = A_bm.device
     n, m, B = eng.n, eng.m, A_bm.shape[0]
-    import os as _os
     # The one-kernel LSQR (ce_shared_a.h).  With the singleton / dense-row split of A (at most 64 rows with several entries) its products are
     # balanced and it beats the batched implementation below at every size measured (BASELINE config 5, B = 16384: 0.26 s against 0.73 s);
     # without the split its CSR / CSC products serialise on the longest row and lose at very large batch x nnz (1.05 s there), hence the
     # work threshold for that case only.  CE_SA_KERNEL=1 / 0 forces / disables.
-    _sa = _os.environ.get("CE_SA_KERNEL")
+    _sa = os.environ.get("CE_SA_KERNEL")
     _row_nnz = np.bincount(eng._indices[:eng.nnzA], minlength=m) if eng.nnzA else np.zeros(m, dtype=np.int64)
     _has_split = int((_row_nnz >= 2).sum()) <= 64
     if _sa != "0" and (_sa == "1" or _has_split or B * max(eng.nnzA, 1) <= (1 << 26)):
         # one kernel, one workgroup per instance (ce_shared_a.h); falls through to the batched torch implementation when the template
         # has exponential / power cones or the LSQR vectors of an instance do not fit LDS
-        f64_ = dict(dtype=torch.float64, device=dev)
-        dA_bm = torch.empty((B, eng.nnz_aug), **f64_); dq = torch.empty((n + 1, B), **f64_)
-        adj = torch.empty((B,), dtype=torch.int32, device=dev); its = torch.empty((B,), dtype=torch.int32, device=dev)
-        xc, yc, sc_, dxc, dyc = (t.to(torch.float64).contiguous() for t in (x, y, s, dx, dy))
-        if q_eval is not None:
-            qd = q_eval.detach().to(device=dev, dtype=torch.float64)
-            q_args = (qd.data_ptr(), qd.stride(0), qd.stride(1))
-        else:
-            q_args = (None, 0, 0)
         assert A_bm.stride(1) == 1
-        rc = _lib.lib().ce_vjp_shared_a(eng._h, B, A_bm.data_ptr(), A_bm.stride(0), *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dxc.data_ptr(), dyc.data_ptr(),
-                                        dA_bm.data_ptr(), dq.data_ptr(), B, 1, adj.data_ptr(), its.data_ptr(), atol, btol, float(conlim), int(iter_lim),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc == 0:
-            eng.last_lsqr_iters = its
-            return (dA_bm.t().contiguous() if batch_minor_out else dA_bm.t()), dq, adj
-        if rc not in (-2, -3):
-            _lib.check(rc, "ce_vjp_shared_a")
+        out = eng.lsqr_one_kernel(_lib.lib().ce_vjp_shared_a, "ce_vjp_shared_a", A_bm.data_ptr(), A_bm.stride(0), B, x, y, s, dx, dy, batch_minor_out, atol, btol, iter_lim, q_eval, conlim)
+        if out is not None:
+            return out
     indices, indptr = eng._indices, eng._indptr
     nnzA = eng.nnzA
     cols_np = np.repeat(np.arange(n + 1), np.diff(indptr))
@@ -569,7 +600,6 @@ def vjp_const_a(eng, A_bm, x, y, s, dx, dy, batch_minor_out=False, atol=1e-8, bt
 
     state = [ux, uy, ut, vx, vy, vt, wx, wy, wt, rx, ry, rt, alfa, rhobar, phibar, anorm, ddnorm, xxnorm, zz, cs2, sn2, live]
     BLK = 16
-    import os
     graph = None
     if os.environ.get("CE_CA_GRAPH", "1") != "0":
         # the loop is host-bound for small batches (~60 small launches per iteration): capture BLK iterations once and replay

@@ -1,0 +1,128 @@
+"""Solver-argument rules of the MI355 plugin: which solver_args exist, what they mean for the forward settings and the adjoint, what is said once."""
+from __future__ import annotations
+
+import ctypes as C
+import warnings
+
+from cvxpylayers_amd import _lib
+
+try:  # subclass diffcp.SolverError when diffcp is importable so `pytest.raises(diffcp.SolverError)` keeps working
+    import diffcp as _diffcp  # type: ignore
+
+    _SolverErrorBase = _diffcp.SolverError
+except Exception:  # pragma: no cover - diffcp is not installed in this image
+    _SolverErrorBase = Exception
+
+
+class SolverError(_SolverErrorBase):
+    """Raised when any instance of the batch is infeasible / unbounded / failed
+    (reference contract: tests/test_torch.py:299-316 expects diffcp.SolverError for the whole batch)."""
+
+
+STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infeasible", -6: "Unbounded/Inaccurate",
+                -7: "Infeasible/Inaccurate", -4: "Failed", 0: "Unfinished"}
+
+_KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
+               "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
+               "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system"}
+
+# Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
+# iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
+# lsqr_atol / lsqr_btol / lsqr_iter_lim (callers that need gradients to 1e-5 against a direct elimination pass tight values explicitly).
+# adjoint_system: "full" (default) = diffcp's (n + m + 1) system M^T r = dz, tau row and column included -- LSQR then returns diffcp's minimum-norm element on
+# rank-deficient systems and takes diffcp's number of iterations;  "reduced" = r_tau pinned to 0 (the system of rounds 1-4: the same gradients wherever the
+# system is regular and the point accurate, a quarter of the LSQR iterations at loose eps, where the full system is nearly singular AND inconsistent).
+LSQR_ATOL, LSQR_BTOL = 1e-8, 1e-8
+
+
+def lsqr_rule(merged_args: dict, n: int, m: int) -> tuple:
+    """(atol, btol, iter_lim, system, method) of the iterative adjoint from merged solver_args; defaults = diffcp's.  method: "lsqr", or "lsmr" for diffcp's mode="lsmr"
+    (the same operator and tolerances under Fong & Saunders' LSMR recurrences and stopping tests: ce_set_lsqr_variant)"""
+    lim = merged_args.get("lsqr_iter_lim")
+    system = str(merged_args.get("adjoint_system", "full"))
+    if system not in ("full", "reduced"):
+        raise ValueError(f"MI355 solver: adjoint_system must be 'full' or 'reduced', got {system!r}")
+    return (float(merged_args.get("lsqr_atol", LSQR_ATOL)), float(merged_args.get("lsqr_btol", LSQR_BTOL)),
+            int(lim) if lim not in (None, 0) else 2 * (n + m + 1), system, "lsmr" if str(merged_args.get("mode", "")) == "lsmr" else "lsqr")
+
+
+def unpack_rule(lsqr, n: int, m: int) -> tuple:
+    """(atol, btol, iter_lim, system, method) from a rule of three to five entries (callers of ConeEngine.vjp pass what they care about); None = diffcp's defaults"""
+    t = tuple(lsqr) if lsqr is not None else lsqr_rule({}, n, m)
+    return t + ("full", "lsqr")[len(t) - 3:] if len(t) < 5 else t[:5]
+
+
+
+def adjoint_mode(merged_args: dict) -> str:
+    """diffcp's `mode` (adj_batch / solve_and_derivative_batch; diffcp_if.py:86 runs its default "lsqr") for PER-INSTANCE-A templates:
+    absent -> "direct": the rank-revealing elimination (k_backward_rt / k_backward: the same gradients as LSQR wherever the adjoint system is regular) and,
+    behind it on the device, diffcp's LSQR for exactly the instances the elimination found RANK DEFICIENT (ce_vjp with q_vals; include/cone_engine.h) -- the
+    default answer is diffcp's minimum-norm element everywhere, regular instances pay nothing;
+    "dense" -> "dense": the elimination alone (a basic solution on rank-deficient systems);
+    "lsqr" -> diffcp's LSQR on the full (n + m + 1) system with its stopping rule for every instance (ce_vjp_lsqr).  Shared-A templates run LSQR whatever the mode says."""
+    mode = str(merged_args.get("mode", ""))
+    return "lsqr" if mode in ("lsqr", "lsmr") else ("dense" if mode == "dense" else "direct")          # ("lsmr": the iterative path with LSMR's recurrences, lsqr_rule()[4])
+
+
+_WARNED: set = set()
+
+
+def _warn_once(key: str, msg: str):
+    """one warning per process and topic (the plugin is called once per training step: repeating it would drown the log)"""
+    if key not in _WARNED:
+        _WARNED.add(key)
+        warnings.warn(msg, stacklevel=3)
+
+
+def note_ignored_args(merged_args: dict, explicit_lookback: bool):
+    """The reference's solver arguments this plugin ACCEPTS but does not act on, said once instead of swallowed silently (diffcp_if.py:356-367 forwards them to
+    diffcp / SCS):  acceleration_lookback > 1 -- the kernels keep ONE secant pair whatever the lookback (SCS keeps `lookback` pairs; same fixed point,
+    iteration counts within 2.5 % on the BASELINE configurations);  mode other than "lsqr" / "dense" (diffcp's "lsmr") and solve_method -- see adjoint_mode();
+    n_jobs_forward / n_jobs_backward -- the batch runs on the GPU."""
+    lb = merged_args.get("acceleration_lookback")
+    if explicit_lookback and lb is not None and int(lb) > 1:      # (the DEFAULT configuration stays silent -- valid calls must survive `-W error`; info["acceleration"] and the docs carry the one-pair fact)
+        _warn_once("lookback", f"MI355 solver: acceleration_lookback={int(lb)}" + ("" if explicit_lookback else " (SCS's default, which the reference forwards)") +
+                   " runs as type-I Anderson acceleration with a ONE-pair history (memory 1), not a " + str(int(lb)) + "-pair history; "
+                   "pass acceleration_lookback=1 to say so explicitly, 0 to iterate plainly")
+    for k in ("mode", "solve_method", "n_jobs_forward", "n_jobs_backward"):
+        if k == "mode" and str(merged_args.get(k)) in ("lsqr", "lsmr", "dense"):          # acted on: adjoint_mode()
+            continue
+        if k in merged_args:
+            _warn_once(k, f"MI355 solver: solver_args[{k!r}]={merged_args[k]!r} is accepted for compatibility with the DIFFCP plugin and ignored "
+                          "(the adjoint method is fixed per template, the batch is solved on the GPU)")
+
+
+def dims_to_solver_dict(dims) -> dict:
+    """ConeDims (attrs zero/nonneg/soc/exp/psd/p3d) or an SCS-style dict -> {"z","l","q","ep","s","p"}
+    (what cvxpy.reductions.solvers.conic_solvers.scs_conif.dims_to_solver_dict returns; diffcp_if.py:8,150)."""
+    if isinstance(dims, dict):
+        return {"z": int(dims.get("z", dims.get("f", 0))), "l": int(dims.get("l", 0)), "q": [int(v) for v in dims.get("q", [])],
+                "ep": int(dims.get("ep", 0)), "s": [int(v) for v in dims.get("s", [])], "p": list(dims.get("p", []))}
+    return {"z": int(dims.zero), "l": int(dims.nonneg), "q": [int(v) for v in dims.soc], "ep": int(getattr(dims, "exp", 0)),
+            "s": [int(v) for v in getattr(dims, "psd", [])], "p": list(getattr(dims, "p3d", []))}
+
+
+def make_settings(merged_args: dict) -> _lib.CeSettings:
+    """solver_args (SCS / diffcp keyword names) -> ce_settings.  diffcp maps `eps` to eps_abs and eps_rel."""
+    unknown = set(merged_args) - _KNOWN_ARGS
+    if unknown:
+        raise ValueError(f"MI355 solver: unknown solver_args {sorted(unknown)}")
+    s = _lib.CeSettings()
+    _lib.lib().ce_default_settings(C.byref(s))
+    a = dict(merged_args)
+    if "eps" in a:
+        s.eps_abs = s.eps_rel = float(a["eps"])
+    for k in ("eps_abs", "eps_rel", "eps_infeas", "alpha", "rho_x", "scale"):
+        if k in a:
+            setattr(s, k, float(a[k]))
+    for k in ("max_iters", "normalize", "adaptive_scale"):
+        if k in a:
+            setattr(s, k, int(a[k]))
+    # Anderson acceleration: ce_default_settings carries SCS's defaults (lookback 10, interval 10; diffcp forwards them,
+    # diffcp_if.py:356-367); acceleration_lookback=0 switches it off.  The kernels keep a one-pair history whatever the lookback.
+    if a.get("acceleration_lookback") is not None:
+        s.acceleration_lookback = max(int(a["acceleration_lookback"]), 0)
+    if a.get("acceleration_interval") not in (0, None):
+        s.acceleration_interval = int(a["acceleration_interval"])
+    return s
