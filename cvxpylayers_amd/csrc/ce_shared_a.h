@@ -31,6 +31,13 @@ struct SaStruct {            // sparse structure of the template's A part (devic
     const int *bpos;         // [m]       position of the row's b entry in the value order (-1: structurally zero)
 };
 
+// FORWARD derivative (k_sa_lsqr<..., FWD = true>; diffcp's D, oracle/cone_oracle.c apply_M): tangents in, solution tangents out.  Null tangent = zero.
+struct SaJvp {
+    const double *tA; long stAb;             // [B][nnz_aug] tangent of the boundary's value rows (A part read only when the template's A is per instance)
+    const double *tq; long stqk, stqb;       // tangent of q_eval, entry j of instance i at j * stqk + i * stqb (the last entry is ignored)
+    double *dx, *dy, *ds;                    // [B][n], [B][m], [B][m] (ds may be null)
+};
+
 constexpr int SA_G = 8;      // lanes per row / column of a sparse product (DPP butterfly over 8 lanes)
 
 // out(i, sum_k vals[src[k]] x[idx[k]]) for every row i of a CSR-like structure; all threads call it
@@ -52,6 +59,7 @@ __device__ __forceinline__ void sa_spmv(const int *__restrict__ ptr, const int *
 
 // LDS doubles.  nvv: rows in front of the first PSD block (v = y - s is kept for those only; PSD blocks read y - s once, at the start).
 // The partial sums of the dense-row products (2 NT doubles) share the PSD scratch matrices when the template has PSD blocks.
+// The forward derivative (FWD) runs the same bidiagonalisation on the same vectors: its footprint is this function's with lsmr = 0.
 __host__ __device__ inline size_t sa_lsqr_lds_doubles(int n, int m, int nq, int ns, int maxs, int RP, int nvv, int ntri = 0, int lsmr = 0) {
     const int kp = ns > 0 ? psd_mfma_kp(maxs) : 0;
     return (size_t)(RP > 0 ? 2 * RP + (ns > 0 ? 0 : 2 * NT) : 0) + (size_t)(ns > 0 ? (2 * ns + 2) * kp * (kp + 1) + 2 * kp + 8 : 0) + NW * 8 +
@@ -63,12 +71,15 @@ __host__ __device__ inline size_t sa_lsqr_lds_doubles(int n, int m, int nq, int 
 // HPSD / HTRI: the template has PSD blocks / exponential-power triples (false: their code is compiled out -- the plain-cone instantiation carried 50 spilled VGPRs of it)
 // LSMR: the same Golub-Kahan bidiagonalisation driven by Fong & Saunders' LSMR recurrences and stopping tests (diffcp's mode="lsmr"; oracle/cone_oracle.c lsmr_core,
 // pinned on scipy.sparse.linalg.lsmr): every product, cone derivative and reduction below is shared, the solution update needs one more vector (h-bar) and |x|.
-template <int RP, bool HPSD = true, bool HTRI = true, bool LSMR = false>
+// FWD: the forward derivative  M d = -dQ pi  instead of the adjoint  M^T r = dz  (M = N^T below): the Golub-Kahan process with the two operator applications
+// swapped, its own right-hand side and outputs (SaJvp); cone data, dproj, both_products, the A staging and the LSQR recurrences are the adjoint's.  LSQR only.
+template <int RP, bool HPSD = true, bool HTRI = true, bool LSMR = false, bool FWD = false>
 __global__ void __launch_bounds__(NT, 3)
 k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long sAb, int per_inst, const double *__restrict__ qg, long sqk, long sqb, const double *__restrict__ xg, const double *__restrict__ yg,
           const double *__restrict__ sg, const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo,
           double *__restrict__ dqo, long sdqk, long sdqb, int *__restrict__ adj_status, int *__restrict__ iters_o, double atol, double btol, double conlim, int itn_lim,
-          const int *__restrict__ sel = nullptr, int status_or = 0, int a_lds = 0, int *__restrict__ sel_reset = nullptr) {
+          const int *__restrict__ sel = nullptr, int status_or = 0, int a_lds = 0, int *__restrict__ sel_reset = nullptr, SaJvp W = SaJvp{}) {
+    static_assert(!(FWD && LSMR), "the forward derivative runs LSQR's recurrences only");
     // sel != nullptr (ce_vjp's re-solve of the instances its direct elimination flagged rank-deficient): sel[0] instances are listed in sel[1 ...] (appended by
     // the elimination kernel on the same stream); the grid is a fixed number of workgroups that walk the list -- the host never learns the count.  status_or is
     // OR-ed into the adj_status of every instance served (ce_vjp: 4 | 8 = "rank-deficient, re-solved by LSQR").
@@ -323,27 +334,60 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
     //      N   (r_x, r_y, r_t) = ( -A^T r_y - c r_t ,  DPi(A r_x - b r_t - r_y) + r_y ,  c.r_x + b.r_y )
     //      N^T (p_x, p_y, p_t) = (  A^T q + c p_t   , -A p_x + b p_t - q + p_y          , -c.p_x - b.q   ),     q = DPi(p_y)
     double acc = 0, acct = 0, dsum = 0;
-    for (int j = tid; j < n; j += NT) { const double v = dxg[(size_t)inst * n + j]; ux[j] = v; rx[j] = 0.0; if constexpr (LSMR) hbx[j] = 0.0; acc = fma(v, v, acc); acct = fma(x[j], v, acct); }
-    for (int i = tid; i < m; i += NT) { const double v = dyg[(size_t)inst * m + i]; ty[i] = v; ry[i] = 0.0; if constexpr (LSMR) hby[i] = 0.0; acct = fma(y[i], v, acct); }
-    __syncthreads();
-    dproj(ty, 1.0, [&](int i, double o) { uy[i] = o; acc = fma(o, o, acc); });
-    acc = sum_two(acc, acct, dsum);
-    double ut = TAU ? -dsum : 0.0, vt = 0.0, wt = 0.0, rt = 0.0;          // dz_tau = -(x.dx + y.dy)
-    const double bnorm = sqrt(fma(ut, ut, acc));
-    double beta = bnorm, ib = 1.0 / safe(beta);
-    // u <- u / beta ;  q = DPi(uy) ;  v = N^T u
-    for (int j = tid; j < n; j += NT) ux[j] *= ib;
-    dproj(uy, ib, [&](int i, double o) { qv[i] = o; to_wyd(i, o); });
-    if (ntri > 0) __syncthreads();                       // a triple's thread reads three rows of uy that other threads rescale below
-    for (int i = tid; i < m; i += NT) uy[i] *= ib;       // (every other read of uy by dproj is behind one of its barriers, or by the row's own thread)
-    ut *= ib;
-    __syncthreads();
-    acc = 0; acct = 0;
-    both_products(qv, ux, [&](int j, double a, double cj) { const double v = fma(cj, ut, a); vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
-                  [&](int i, double a, double bi) { const double v = fma(bi, ut, -a - qv[i] + uy[i]); vy[i] = v; acc = fma(v, v, acc); acct = fma(bi, qv[i], acct); });
-    acc = sum_two(acc, acct, dsum);
-    vt = TAU ? -dsum : 0.0;
-    double alfa = sqrt(fma(vt, vt, acc));
+    double ut, vt = 0.0, wt = 0.0, rt = 0.0, bnorm, beta, ib, alfa;
+    if constexpr (FWD) {
+        // ---- LSQR on  M d = -g,  M = N^T:  u-space <- N^T v,  v-space <- N u.   g = dQ pi = ( dA^T y + dc , -dA x + db , -dc.x - db.y )  with the tangents in the
+        //      boundary convention: dA = -tA_eval (A part), db = +tA_eval (b column), dc = tq_eval[:n]
+        const double *tA = W.tA ? W.tA + (size_t)inst * W.stAb : nullptr, *tq = W.tq ? W.tq + (size_t)inst * W.stqb : nullptr;
+        for (int j = tid; j < n; j += NT) { const double v = tq ? tq[(size_t)j * W.stqk] : 0.0; ux[j] = -v; rx[j] = 0.0; acct = fma(x[j], v, acct); }
+        for (int i = tid; i < m; i += NT) { const int pb = tA ? S.bpos[i] : -1; const double v = pb >= 0 ? tA[pb] : 0.0; uy[i] = -v; ry[i] = 0.0; acct = fma(y[i], v, acct); }
+        if (tA && per_inst) {          // (a shared A has no tangent)
+            __syncthreads();
+            sa_spmv(S.csc_ptr, S.csc_row, (const int *)nullptr, tA, n, [&](int i) { return y[i]; }, [&](int j, double a) { ux[j] += a; });
+            sa_spmv(S.csr_ptr, S.csr_col, S.csr_src, tA, m, [&](int j) { return x[j]; }, [&](int i, double a) { uy[i] -= a; });
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += NT) acc = fma(ux[j], ux[j], acc);
+        for (int i = tid; i < m; i += NT) acc = fma(uy[i], uy[i], acc);
+        acc = sum_two(acc, acct, dsum);
+        ut = TAU ? dsum : 0.0;                             // -g_tau = dc.x + db.y
+        bnorm = sqrt(fma(ut, ut, acc));
+        beta = bnorm; ib = 1.0 / safe(beta);
+        // u <- u / beta ;  v = N u
+        for (int j = tid; j < n; j += NT) ux[j] *= ib;
+        for (int i = tid; i < m; i += NT) { const double v = uy[i] * ib; uy[i] = v; to_wyd(i, v); }
+        ut *= ib;
+        __syncthreads();
+        acc = 0; acct = 0;
+        both_products(uy, ux, [&](int j, double a, double cj) { const double v = -a - cj * ut; vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
+                      [&](int i, double a, double bi) { const double uyi = uy[i]; ty[i] = a - bi * ut - uyi; acct = fma(bi, uyi, acct); });
+        dproj(ty, 1.0, [&](int i, double o) { const double v = o + uy[i]; vy[i] = v; acc = fma(v, v, acc); });
+        acc = sum_two(acc, acct, dsum);
+        vt = TAU ? dsum : 0.0;
+        alfa = sqrt(fma(vt, vt, acc));
+    } else {
+        for (int j = tid; j < n; j += NT) { const double v = dxg[(size_t)inst * n + j]; ux[j] = v; rx[j] = 0.0; if constexpr (LSMR) hbx[j] = 0.0; acc = fma(v, v, acc); acct = fma(x[j], v, acct); }
+        for (int i = tid; i < m; i += NT) { const double v = dyg[(size_t)inst * m + i]; ty[i] = v; ry[i] = 0.0; if constexpr (LSMR) hby[i] = 0.0; acct = fma(y[i], v, acct); }
+        __syncthreads();
+        dproj(ty, 1.0, [&](int i, double o) { uy[i] = o; acc = fma(o, o, acc); });
+        acc = sum_two(acc, acct, dsum);
+        ut = TAU ? -dsum : 0.0;             // dz_tau = -(x.dx + y.dy)
+        bnorm = sqrt(fma(ut, ut, acc));
+        beta = bnorm; ib = 1.0 / safe(beta);
+        // u <- u / beta ;  q = DPi(uy) ;  v = N^T u
+        for (int j = tid; j < n; j += NT) ux[j] *= ib;
+        dproj(uy, ib, [&](int i, double o) { qv[i] = o; to_wyd(i, o); });
+        if (ntri > 0) __syncthreads();                       // a triple's thread reads three rows of uy that other threads rescale below
+        for (int i = tid; i < m; i += NT) uy[i] *= ib;       // (every other read of uy by dproj is behind one of its barriers, or by the row's own thread)
+        ut *= ib;
+        __syncthreads();
+        acc = 0; acct = 0;
+        both_products(qv, ux, [&](int j, double a, double cj) { const double v = fma(cj, ut, a); vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
+                      [&](int i, double a, double bi) { const double v = fma(bi, ut, -a - qv[i] + uy[i]); vy[i] = v; acc = fma(v, v, acc); acct = fma(bi, qv[i], acct); });
+        acc = sum_two(acc, acct, dsum);
+        vt = TAU ? -dsum : 0.0;
+        alfa = sqrt(fma(vt, vt, acc));
+    }
     // |w|^2 of the current search direction, as per-thread partial sums: LSQR's estimate of cond(N) (the `conlim` stopping test) needs sum_k |w_k|^2 / rho_k^2;
     // the partial sums ride on the first reduction of the NEXT iteration (no barrier of their own)
     double wsq = 0, ddnorm = 0;
@@ -373,37 +417,64 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
     while (live && itn < itn_lim) {
         itn++;
         LS_T(7);
-        // t = N v :  tx = -A^T vy - c vt ;  ty = DPi(A vx - b vt - vy) + vy ;  tt = c.vx + b.vy ;   u-hat = t - alfa u
-        acc = 0; acct = 0;
-        both_products(vy, vx, [&](int j, double a, double cj) { const double v = -a - cj * vt - alfa * ux[j]; ux[j] = v; acc = fma(v, v, acc); acct = fma(cj, vx[j], acct); },
-                      [&](int i, double a, double bi) { const double vyi = vy[i]; ty[i] = a - bi * vt - vyi; acct = fma(bi, vyi, acct); });
-        LS_T(0);
-        dproj(ty, 1.0, [&](int i, double o) { const double v = o + vy[i] - alfa * uy[i]; uy[i] = v; acc = fma(v, v, acc); });
-        LS_T(1);
         double wsum = 0;
-        acc = sum_three(acc, acct, wsq, dsum, wsum);
-        wsum = fma(wt, wt, wsum);                          // |w_{k-1}|^2, tau component included
-        ut = TAU ? dsum - alfa * ut : 0.0;
-        beta = sqrt(fma(ut, ut, acc));
-        LS_T(2);
-        ib = 1.0 / safe(beta);
-        anorm = sqrt(anorm * anorm + alfa * alfa + beta * beta);
-        // u = u-hat / beta ;  q = DPi(uy) ;  (tx, ty) = N^T u ;  v-hat = t - beta v
-        for (int j = tid; j < n; j += NT) ux[j] *= ib;
-        dproj(uy, ib, [&](int i, double o) { qv[i] = o; to_wyd(i, o); });
-        if (ntri > 0) __syncthreads();
-        for (int i = tid; i < m; i += NT) uy[i] *= ib;
-        ut *= ib;
-        __syncthreads();
-        LS_T(3);
-        acc = 0; acct = 0;
-        both_products(qv, ux, [&](int j, double a, double cj) { const double v = fma(cj, ut, a) - beta * vx[j]; vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
-                      [&](int i, double a, double bi) { const double qi = qv[i]; const double v = fma(bi, ut, -a - qi + uy[i]) - beta * vy[i]; vy[i] = v; acc = fma(v, v, acc); acct = fma(bi, qi, acct); });
-        LS_T(4);
-        acc = sum_two(acc, acct, dsum);
-        vt = TAU ? -dsum - beta * vt : 0.0;
-        alfa = sqrt(fma(vt, vt, acc));
-        LS_T(5);
+        if constexpr (FWD) {
+            // q = DPi(vy) ;  u-hat = N^T v - alfa u
+            dproj(vy, 1.0, [&](int i, double o) { qv[i] = o; to_wyd(i, o); });
+            __syncthreads();
+            acc = 0; acct = 0;
+            both_products(qv, vx, [&](int j, double a, double cj) { const double v = fma(cj, vt, a) - alfa * ux[j]; ux[j] = v; acc = fma(v, v, acc); acct = fma(cj, vx[j], acct); },
+                          [&](int i, double a, double bi) { const double qi = qv[i]; const double v = fma(bi, vt, -a - qi + vy[i]) - alfa * uy[i]; uy[i] = v; acc = fma(v, v, acc); acct = fma(bi, qi, acct); });
+            acc = sum_three(acc, acct, wsq, dsum, wsum);
+            wsum = fma(wt, wt, wsum);
+            ut = TAU ? -dsum - alfa * ut : 0.0;
+            beta = sqrt(fma(ut, ut, acc));
+            ib = 1.0 / safe(beta);
+            anorm = sqrt(anorm * anorm + alfa * alfa + beta * beta);
+            // u = u-hat / beta ;  v-hat = N u - beta v
+            for (int j = tid; j < n; j += NT) ux[j] *= ib;
+            for (int i = tid; i < m; i += NT) { const double v = uy[i] * ib; uy[i] = v; to_wyd(i, v); }
+            ut *= ib;
+            __syncthreads();
+            acc = 0; acct = 0;
+            both_products(uy, ux, [&](int j, double a, double cj) { const double v = -a - cj * ut - beta * vx[j]; vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
+                          [&](int i, double a, double bi) { const double uyi = uy[i]; ty[i] = a - bi * ut - uyi; acct = fma(bi, uyi, acct); });
+            dproj(ty, 1.0, [&](int i, double o) { const double v = o + uy[i] - beta * vy[i]; vy[i] = v; acc = fma(v, v, acc); });
+            acc = sum_two(acc, acct, dsum);
+            vt = TAU ? dsum - beta * vt : 0.0;
+            alfa = sqrt(fma(vt, vt, acc));
+        } else {
+            // t = N v :  tx = -A^T vy - c vt ;  ty = DPi(A vx - b vt - vy) + vy ;  tt = c.vx + b.vy ;   u-hat = t - alfa u
+            acc = 0; acct = 0;
+            both_products(vy, vx, [&](int j, double a, double cj) { const double v = -a - cj * vt - alfa * ux[j]; ux[j] = v; acc = fma(v, v, acc); acct = fma(cj, vx[j], acct); },
+                          [&](int i, double a, double bi) { const double vyi = vy[i]; ty[i] = a - bi * vt - vyi; acct = fma(bi, vyi, acct); });
+            LS_T(0);
+            dproj(ty, 1.0, [&](int i, double o) { const double v = o + vy[i] - alfa * uy[i]; uy[i] = v; acc = fma(v, v, acc); });
+            LS_T(1);
+            acc = sum_three(acc, acct, wsq, dsum, wsum);
+            wsum = fma(wt, wt, wsum);                          // |w_{k-1}|^2, tau component included
+            ut = TAU ? dsum - alfa * ut : 0.0;
+            beta = sqrt(fma(ut, ut, acc));
+            LS_T(2);
+            ib = 1.0 / safe(beta);
+            anorm = sqrt(anorm * anorm + alfa * alfa + beta * beta);
+            // u = u-hat / beta ;  q = DPi(uy) ;  (tx, ty) = N^T u ;  v-hat = t - beta v
+            for (int j = tid; j < n; j += NT) ux[j] *= ib;
+            dproj(uy, ib, [&](int i, double o) { qv[i] = o; to_wyd(i, o); });
+            if (ntri > 0) __syncthreads();
+            for (int i = tid; i < m; i += NT) uy[i] *= ib;
+            ut *= ib;
+            __syncthreads();
+            LS_T(3);
+            acc = 0; acct = 0;
+            both_products(qv, ux, [&](int j, double a, double cj) { const double v = fma(cj, ut, a) - beta * vx[j]; vx[j] = v; acc = fma(v, v, acc); acct = fma(cj, ux[j], acct); },
+                          [&](int i, double a, double bi) { const double qi = qv[i]; const double v = fma(bi, ut, -a - qi + uy[i]) - beta * vy[i]; vy[i] = v; acc = fma(v, v, acc); acct = fma(bi, qi, acct); });
+            LS_T(4);
+            acc = sum_two(acc, acct, dsum);
+            vt = TAU ? -dsum - beta * vt : 0.0;
+            alfa = sqrt(fma(vt, vt, acc));
+            LS_T(5);
+        }
         if constexpr (LSMR) {
             double chat, shat, alphahat; sym_ortho(alphabar, 0.0, chat, shat, alphahat);
             const double rhoold = mrho; double c_, s_; sym_ortho(alphahat, beta, c_, s_, mrho);
@@ -466,17 +537,29 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
         cs2 = uniform_d(cs2); sn2 = uniform_d(sn2); ddnorm = uniform_d(ddnorm);
     }
     __syncthreads();
-    // ---- outputs in the boundary convention: dA_eval = [-dA.data, db[b_idx]], dq_eval = [dc, 0]  (diffcp_if.py:91-92);
-    //      dA_ij = x_j r_y,i - y_i r_x,j ,  db = y r_tau - r_y ,  dc = x r_tau - r_x        (oracle/cone_oracle.c adjoint_one: dQ = r Pi(z)^T antisymmetrised)
-    double *dA = dAo + (size_t)inst * T.nnz_aug;
-    for (int k = tid; k < T.nnz_aug; k += NT) {
-        const int r = T.rowidx[k], c = T.colidx[k];
-        dA[k] = (c < n) ? -(x[c] * ry[r] - y[r] * rx[c]) : fma(y[r], rt, -ry[r]);
+    if constexpr (FWD) {
+        // ---- outputs: the tangents of the solution,  dx = d_x - x d_tau ,  dy = DPi(d_y) - y d_tau ,  ds = DPi(d_y) - d_y - s d_tau      (oracle/cone_oracle.c: diffcp's D)
+        dproj(ry, 1.0, [&](int i, double o) { qv[i] = o; });
+        __syncthreads();
+        for (int j = tid; j < n; j += NT) W.dx[(size_t)inst * n + j] = fma(-x[j], rt, rx[j]);
+        for (int i = tid; i < m; i += NT) {
+            const double qi = qv[i];
+            W.dy[(size_t)inst * m + i] = fma(-y[i], rt, qi);
+            if (W.ds) W.ds[(size_t)inst * m + i] = fma(-s[i], rt, qi - ry[i]);
+        }
+    } else {
+        // ---- outputs in the boundary convention: dA_eval = [-dA.data, db[b_idx]], dq_eval = [dc, 0]  (diffcp_if.py:91-92);
+        //      dA_ij = x_j r_y,i - y_i r_x,j ,  db = y r_tau - r_y ,  dc = x r_tau - r_x        (oracle/cone_oracle.c adjoint_one: dQ = r Pi(z)^T antisymmetrised)
+        double *dA = dAo + (size_t)inst * T.nnz_aug;
+        for (int k = tid; k < T.nnz_aug; k += NT) {
+            const int r = T.rowidx[k], c = T.colidx[k];
+            dA[k] = (c < n) ? -(x[c] * ry[r] - y[r] * rx[c]) : fma(y[r], rt, -ry[r]);
+        }
+        for (int j = tid; j <= n; j += NT) dqo[j * sdqk + inst * sdqb] = (j < n) ? fma(x[j], rt, -rx[j]) : 0.0;
     }
-    for (int j = tid; j <= n; j += NT) dqo[j * sdqk + inst * sdqb] = (j < n) ? fma(x[j], rt, -rx[j]) : 0.0;
 #ifdef CE_TIMING
     __syncthreads();
-    if (tid == 0) for (int k = 0; k < 8; k++) dA[k] = (double)ls_tacc[k];
+    if constexpr (!FWD) if (tid == 0) for (int k = 0; k < 8; k++) dAo[(size_t)inst * T.nnz_aug + k] = (double)ls_tacc[k];
 #endif
     if (tid == 0) { if (adj_status) adj_status[inst] = (live ? 1 : 0) | status_or; if (iters_o) iters_o[inst] = itn; }
     __syncthreads();          // (the next listed instance reuses every LDS vector)

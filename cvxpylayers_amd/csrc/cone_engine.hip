@@ -637,7 +637,7 @@ int ce_vjp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const
 static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
-                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr);
+                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr, const SaJvp *fwd = nullptr);
 int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *P_vals,
               const double *x, const double *y, const double *s, const double *dx, const double *dy,
               double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, double *dP_vals, int *adj_status, void *stream) {
@@ -980,17 +980,19 @@ int ce_solve_shared_a(ce_handle h, int B, int r, int RP, const double *AdT, cons
 static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
-                           const int *sel, int status_or, int *sel_reset) {
-    if (!h || B <= 0 || !A_vals0 || !x || !y || !s || !dx || !dy || !dA_bm || !dq_vals) { g_err = "null argument"; return CE_E_BADARG; }
+                           const int *sel, int status_or, int *sel_reset, const SaJvp *fwd) {
+    // fwd != nullptr: the forward derivative (ce_jvp_lsqr / ce_jvp_shared_a) -- k_sa_lsqr<..., FWD> on the same plan; dx ... dq_vals are unused
+    if (!h || B <= 0 || !A_vals0 || !x || !y || !s) { g_err = "null argument"; return CE_E_BADARG; }
+    if (fwd ? (!fwd->dx || !fwd->dy) : (!dx || !dy || !dA_bm || !dq_vals)) { g_err = "null argument"; return CE_E_BADARG; }
     const DevT &T = h->T;
     // products through the singleton / dense-row split when the template has one (CE_SA_SPLIT=0: CSR / CSC products)
     int RP = h->sp_RP;
     if (const char *e = getenv("CE_SA_SPLIT")) { if (atoi(e) == 0) RP = 0; }
     if (per_inst) RP = 0;      // the split's dense rows are ONE matrix (instance 0's values); per-instance values go through the CSR / CSC products
-    const int lsmr = (h->lsqr_variant == 1 && !sel) ? 1 : 0;      // (the re-solve list of ce_vjp stays diffcp's default, LSQR)
+    const int lsmr = (h->lsqr_variant == 1 && !sel && !fwd) ? 1 : 0;      // (the re-solve list of ce_vjp stays diffcp's default, LSQR)
     if (RP > 0 && sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8 > LDS_LIMIT) RP = 0;
     size_t lds = sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8;
-    if (lds > LDS_LIMIT) { g_err = "shared-A adjoint kernel: the LSQR vectors of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
+    if (lds > LDS_LIMIT) { g_err = fwd ? "forward-derivative kernel: the LSQR vectors of one instance do not fit LDS" : "shared-A adjoint kernel: the LSQR vectors of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
     // per-instance A: staged dense in LDS when it fits behind the vectors with three workgroups per CU to spare (CE_LSQR_A_LDS=0 disables)
     int a_lds = 0;
     if (per_inst && RP == 0) {
@@ -1004,6 +1006,8 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
         SA_ATTR(0); SA_ATTR(16); SA_ATTR(32); SA_ATTR(64); SA_ATTR(0, false, false); SA_ATTR(16, false, false); SA_ATTR(32, false, false); SA_ATTR(64, false, false);
         SA_ATTR(16, true, false); SA_ATTR(32, true, false); SA_ATTR(64, true, false);
         SA_ATTR(0, true, true, true); SA_ATTR(16, true, true, true); SA_ATTR(32, true, true, true); SA_ATTR(64, true, true, true);
+        SA_ATTR(0, false, false, false, true); SA_ATTR(16, false, false, false, true); SA_ATTR(32, false, false, false, true); SA_ATTR(64, false, false, false, true);
+        SA_ATTR(0, true, true, false, true); SA_ATTR(16, true, true, false, true); SA_ATTR(32, true, true, false, true); SA_ATTR(64, true, true, false, true);
 #undef SA_ATTR
         h->sa_lsqr_attr = true;
     }
@@ -1029,7 +1033,7 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
     // Several instances per workgroup share the stream over A_d^T (ce_shared_a_mi.h) where the template allows it: plain cones, the split's products, the solution
     // in the owners' registers, no re-solve list, and enough instances to fill the device either way.  CE_SA_LSQR_NI=1 keeps one instance per workgroup (A/B), 2 / 3 force.
     int ni = 0;
-    if (RP > 0 && !per_inst && !sel && !lsmr && T.ns == 0 && T.nep + T.np == 0 && T.n <= SAMI_EL * 256 && T.m <= SAMI_EL * 256) {
+    if (RP > 0 && !per_inst && !sel && !lsmr && !fwd && T.ns == 0 && T.nep + T.np == 0 && T.n <= SAMI_EL * 256 && T.m <= SAMI_EL * 256) {
         ni = 0;      // (measured slower than one instance per workgroup at config 5: profiles/r06/n_*; opt-in)
         if (const char *e = getenv("CE_SA_LSQR_NI")) { const int v = atoi(e); ni = (v == 2 || v == 3) ? v : 0; }
         while (ni >= 2 && sa_lsqr_mi_lds_doubles(T.n, T.m, T.nq, RP, ni) * 8 > LDS_LIMIT) ni--;
@@ -1054,11 +1058,15 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
     if (const char *e = getenv("CE_SA_LSQR_PADLDS")) { const size_t want = (size_t)atoi(e) * 1024; if (want > lds && want <= LDS_LIMIT) lds = want; }      // (residency experiment: workgroups per CU)
     {
         ProfScope ps(h, 1, (hipStream_t)stream);
-#define LAUNCH_SAL(...) hipLaunchKernelGGL((k_sa_lsqr<__VA_ARGS__>), dim3(B), dim3(NT), lds, (hipStream_t)stream, T, S, F, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters, atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, a_lds, sel_reset)
+#define LAUNCH_SAL(...) hipLaunchKernelGGL((k_sa_lsqr<__VA_ARGS__>), dim3(B), dim3(NT), lds, (hipStream_t)stream, T, S, F, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters, atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, a_lds, sel_reset, fwd ? *fwd : SaJvp{})
         // plain cones / PSD without triples: instantiations without the other cones' code (CE_SA_LSQR_SPEC=0: the general kernel)
         const bool tri = T.nep + T.np > 0, psd = T.ns > 0;
         int spec = 1; if (const char *e = getenv("CE_SA_LSQR_SPEC")) spec = atoi(e);
-        if (lsmr) { if (RP == 0) LAUNCH_SAL(0, true, true, true); else if (RP == 16) LAUNCH_SAL(16, true, true, true); else if (RP == 32) LAUNCH_SAL(32, true, true, true); else LAUNCH_SAL(64, true, true, true); }
+        if (fwd) {      // plain cones, or the general kernel (PSD blocks and triples)
+            if (!tri && !psd) { if (RP == 0) LAUNCH_SAL(0, false, false, false, true); else if (RP == 16) LAUNCH_SAL(16, false, false, false, true); else if (RP == 32) LAUNCH_SAL(32, false, false, false, true); else LAUNCH_SAL(64, false, false, false, true); }
+            else if (RP == 0) LAUNCH_SAL(0, true, true, false, true); else if (RP == 16) LAUNCH_SAL(16, true, true, false, true); else if (RP == 32) LAUNCH_SAL(32, true, true, false, true); else LAUNCH_SAL(64, true, true, false, true);
+        }
+        else if (lsmr) { if (RP == 0) LAUNCH_SAL(0, true, true, true); else if (RP == 16) LAUNCH_SAL(16, true, true, true); else if (RP == 32) LAUNCH_SAL(32, true, true, true); else LAUNCH_SAL(64, true, true, true); }
         else if (spec && !tri && !psd) { if (RP == 0) LAUNCH_SAL(0, false, false); else if (RP == 16) LAUNCH_SAL(16, false, false); else if (RP == 32) LAUNCH_SAL(32, false, false); else LAUNCH_SAL(64, false, false); }
         else if (spec && !tri && RP > 0) { if (RP == 16) LAUNCH_SAL(16, true, false); else if (RP == 32) LAUNCH_SAL(32, true, false); else LAUNCH_SAL(64, true, false); }
         else if (RP == 0) LAUNCH_SAL(0); else if (RP == 16) LAUNCH_SAL(16); else if (RP == 32) LAUNCH_SAL(32); else LAUNCH_SAL(64);
@@ -1077,6 +1085,26 @@ int ce_vjp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const do
                 double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
     if (sA_b == 0 && B > 1) { g_err = "ce_vjp_lsqr: per-instance values need a batch stride"; return CE_E_BADARG; }
     return vjp_lsqr_launch(h, B, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+static int jvp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
+                           const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h) { g_err = "null argument"; return CE_E_BADARG; }
+    if (h->plan.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
+    const SaJvp W{tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds};
+    return vjp_lsqr_launch(h, B, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, nullptr, nullptr, nullptr, nullptr, 0, 0, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream,
+                           nullptr, 0, nullptr, &W);
+}
+int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    return jvp_lsqr_launch(h, B, A_vals0, sA_b, 0, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+int ce_jvp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (sA_b == 0 && B > 1) { g_err = "ce_jvp_lsqr: per-instance values need a batch stride"; return CE_E_BADARG; }
+    return jvp_lsqr_launch(h, B, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
 }
 int ce_ca_triples(ce_handle h, int B, int lp, double *U, double *roots, const int *active, void *stream) {
     if (!h || B <= 0 || !U || !roots || !active) { g_err = "null argument"; return CE_E_BADARG; }

@@ -40,7 +40,8 @@ class ConeEngine:
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
-        self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint
+        self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
+        self.last_jvp_kernel = None           # "ce_jvp_lsqr" / "ce_jvp_shared_a"
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -329,6 +330,42 @@ class ConeEngine:
             _warn_once("lsqr_too_large", "MI355 solver: solver_args mode='lsqr' needs the LSQR vectors of one instance in LDS, which this template exceeds; "
                                          "falling back to the direct elimination (rank-deficient instances are flagged in info['adjoint'])")
         return out
+
+    def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8):
+        """Forward-mode derivative of the solution map (diffcp's `derivative`): tangents tA_bm (B, nnz_aug) of the value rows and tq (n+1, B) of q_eval, either may be
+        None (zero).  Returns dx (B, n), dy (B, m), ds (B, m), status (B,) -- 1: LSQR hit its iteration limit -- and sets last_lsqr_iters.
+        One kernel per call, ce_jvp_lsqr, or ce_jvp_shared_a when `path` is "const_a" (only the b entries of tA_bm are read there: a shared A has no tangent).
+        path, lsqr (rule, adjoint_system) and q_eval as vjp(); the LSQR recurrences only.  NotImplementedError when the LSQR vectors of one instance exceed LDS."""
+        B = A_bm.shape[0]
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        if B == 0:
+            return torch.empty((0, self.n), **f64), torch.empty((0, self.m), **f64), torch.empty((0, self.m), **f64), torch.empty((0,), dtype=torch.int32, device=dev)
+        if path is None:
+            path = self.last_path
+        atol, btol, lim, system, _ = unpack_rule(lsqr, self.n, self.m)
+        if q_eval is None and system != "reduced":
+            q_eval = self._recent_q(A_bm)
+        if system == "reduced":
+            q_eval = None
+        shared = path == "const_a"
+        fn, name = (_lib.lib().ce_jvp_shared_a, "ce_jvp_shared_a") if shared else (_lib.lib().ce_jvp_lsqr, "ce_jvp_lsqr")
+        A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) >= self.nnz_aug)) else A_bm.contiguous()
+        xc, yc, sc_ = (t.detach().to(**f64).contiguous() for t in (x, y, s))
+        tA_c = tA_bm.detach().to(**f64).contiguous() if tA_bm is not None else None
+        tqd, tq_args = self._q_args(tq)
+        qd, q_args = self._q_args(q_eval)
+        dx = torch.empty((B, self.n), **f64); dy = torch.empty((B, self.m), **f64); ds = torch.empty((B, self.m), **f64)
+        st = torch.empty((B,), dtype=torch.int32, device=dev); its = torch.empty((B,), dtype=torch.int32, device=dev)
+        rc = fn(self._h, B, A_c.data_ptr(), A_c.stride(0), *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args, dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(),
+                float(atol), float(btol), float(conlim), int(lim), self._stream())
+        if rc in (-2, -3):
+            raise NotImplementedError(_lib.lib().ce_last_error().decode())
+        _lib.check(rc, name)
+        self.last_jvp_kernel = name
+        self.last_lsqr_iters = its
+        return dx, dy, ds, st
 
     # introspection (bench / tests)
     def set_profiling(self, on):

@@ -87,6 +87,11 @@ def adjoint_report(info: dict) -> dict:
                 no_gradient=int(((a & 2) != 0).sum()), backward_ran=True)
 
 
+def has_tangent(*tensors) -> bool:
+    """any of the tensors is a dual tensor of the current torch.autograd.forward_ad level"""
+    return any(t is not None and torch.autograd.forward_ad.unpack_dual(t).tangent is not None for t in tensors)
+
+
 def _detect_batch_size(con_values) -> tuple[int, bool]:
     """diffcp_if.py:34-43"""
     if con_values.dim() == 1:
@@ -243,6 +248,38 @@ class _ConeLayer(torch.autograd.Function):
         ctx.set_materialize_grads(False)      # an unused output (the duals, most of the time) arrives as None instead of a freshly filled zero tensor: one launch less per step
 
     @staticmethod
+    def jvp(ctx, tP, tq, tA, *_):
+        """Forward-mode derivative (torch.autograd.forward_ad; diffcp's `derivative`, which the reference plugin never calls): the tangents of q_eval / A_eval in,
+        the tangents of (primal, dual) out, by one launch of the LSQR kernel on M d = -dQ pi (ConeEngine.jvp) under this call's lsqr_rule.  Fills info["jvp"]."""
+        saved, batch_size, originally_unbatched, in_device = ctx.backward_data
+        if saved is None:
+            raise RuntimeError("forward-mode derivative requested from a layer evaluated with needs_grad=False")
+        if saved.P_bm is not None:
+            raise NotImplementedError("MI355 solver: the forward-mode derivative is not available with a quadratic objective inside the kernels; "
+                                      "set CE_QP_EPIGRAPH=1 to bring the problem to cone form, where it applies")
+        if tq is None and tA is None:
+            return None, None, None, None
+        eng, x, y, s, failed = saved.eng, saved.x, saved.y, saved.s, saved.failed
+        with torch.cuda.device(eng.device):
+            tA_bm = tq_dev = None
+            if tA is not None:
+                tA_bm = eng.to_batch_major((tA.unsqueeze(1) if originally_unbatched else tA).detach().to(device=eng.device, dtype=torch.float64))
+            if tq is not None:
+                tq_dev = (tq.unsqueeze(1) if originally_unbatched else tq).detach().to(device=eng.device, dtype=torch.float64)
+            if failed is not None:          # masked instances: differentiate at a zero point, return NaN tangents like their NaN primal values
+                keep = ~failed[:, None]
+                x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
+            # a shared-A call whose A values merely coincide may still carry a tangent in A: the shared kernel reads the b entries only
+            path = saved.path if (saved.path != "const_a" or tA_bm is None or eng.A_is_constant) else "per_instance"
+            dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval)
+            if failed is not None:
+                nanv = float("nan")
+                dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
+        if isinstance(ctx.info, dict):
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters}
+        return dx.to(in_device), dy.to(in_device), None, None
+
+    @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dprimal, ddual, _info, _data):
         saved, batch_size, originally_unbatched, in_device = ctx.backward_data
@@ -287,6 +324,8 @@ class _CvxpyLayer:
 
     @staticmethod
     def apply(P_eval, q_eval, A_eval, cl_ctx, solver_args=None, needs_grad=True, warm_start=None):
+        if not needs_grad and has_tangent(P_eval, q_eval, A_eval):      # forward-mode AD needs what backward() needs
+            needs_grad = True
         if P_eval is None:
             return _ConeLayer.apply(None, q_eval, A_eval, cl_ctx, solver_args, needs_grad, warm_start)
         ctx = cl_ctx.solver_ctx if hasattr(cl_ctx, "solver_ctx") else cl_ctx

@@ -142,8 +142,12 @@ class _ParamMap1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, csr: _DeviceCSR, p_bm: torch.Tensor):
         fwd, bwd = csr.on(p_bm.device)
-        ctx.bwd = bwd
+        ctx.fwd, ctx.bwd = fwd, bwd
         return _spmm_bm(fwd, p_bm.contiguous())
+
+    @staticmethod
+    def jvp(ctx, _, t_p):
+        return _spmm_bm(ctx.fwd, t_p.contiguous())      # linear in p (the constant column's tangent is zero)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -160,8 +164,13 @@ class _ParamMapApply(torch.autograd.Function):
         p_bm = p_bm.contiguous()
         fA, bA = A_csr.on(p_bm.device)
         fq, bq = q_csr.on(p_bm.device)
-        ctx.bwd = (bA, bq)
+        ctx.fwd, ctx.bwd = (fA, fq), (bA, bq)
         return _spmm_bm(fA, p_bm), _spmm_bm(fq, p_bm)
+
+    @staticmethod
+    def jvp(ctx, _A, _q, t_p):
+        t_p = t_p.contiguous()                           # both maps are linear in p (the constant column's tangent is zero)
+        return _spmm_bm(ctx.fwd[0], t_p), _spmm_bm(ctx.fwd[1], t_p)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -244,13 +253,21 @@ class _RecoverMap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, csr: _DeviceCSR, layout, shapes, src: torch.Tensor):
         fwd, bwd = csr.on(src.device)
-        ctx.bwd, ctx.layout, ctx.total, ctx.src_shape = bwd, layout, fwd[3], src.shape
+        ctx.fwd, ctx.bwd, ctx.layout, ctx.shapes, ctx.total, ctx.src_shape = fwd, bwd, layout, shapes, fwd[3], src.shape
+        return _RecoverMap._recover(fwd, layout, shapes, src)
+
+    @staticmethod
+    def _recover(fwd, layout, shapes, src):
         src2 = src.reshape(-1, src.shape[-1]).contiguous()
         with torch.cuda.device(src.device):
             rec = _spmm_bm(fwd, src2)
         lead = tuple(src.shape[:-1])
         return tuple(rec[:, off:off + size].reshape(lead + tuple(shape)) if len(layout) > 1 else rec.reshape(lead + tuple(shape))
                      for (_, off, size), shape in zip(layout, shapes))
+
+    @staticmethod
+    def jvp(ctx, _csr, _layout, _shapes, t_src):
+        return _RecoverMap._recover(ctx.fwd, ctx.layout, ctx.shapes, t_src)      # the recovery is linear
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -412,6 +429,8 @@ class CvxpyLayer(torch.nn.Module):
             A_eval, q_eval = A_eval.squeeze(1), q_eval.squeeze(1)
             P_eval = P_eval.squeeze(1) if P_eval is not None else None
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        if not needs_grad:          # forward-mode AD (torch.autograd.forward_ad): a parameter that carries a tangent needs the same saved state
+            needs_grad = any(torch.autograd.forward_ad.unpack_dual(p).tangent is not None for p in params)
         layer_cls = get_torch_cvxpylayer(self.solver)
         # warm_start=True: the plugin starts from this layer's previous solution when the batch size matches (the reference keeps
         # the same cache for its MOREAU plugin, torch/cvxpylayer.py:464-487)

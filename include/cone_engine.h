@@ -91,8 +91,8 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 12
+ * layout, an entry point's signature or the meaning of an argument changes (13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+#define CE_ABI_VERSION 13
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -284,6 +284,28 @@ int ce_vjp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const 
 int ce_vjp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                 const double *x, const double *y, const double *s, const double *dx, const double *dy,
                 double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+
+/*
+ * FORWARD derivative of the solution map (diffcp's `derivative` / D of solve_and_derivative).  The reference plugin never calls it: diffcp_if.py differentiates in
+ * reverse mode only (adj_batch, diffcp_if.py:86), so there is no reference call site; the system and its conventions are diffcp's own (cone_program.py `derivative`:
+ * M d = -dQ pi by LSQR, then dx = d_x - x d_tau, dy = DPi d_y - y d_tau, ds = DPi d_y - d_y - s d_tau) and the adjoint entries above are its transpose.
+ * One workgroup per instance runs ce_vjp_lsqr's kernel with the two operator applications of the Golub-Kahan process swapped (LSQR recurrences only: ce_set_lsqr_variant
+ * does not apply).  A_vals_bm / sA_b, q_vals, x, y, s, atol / btol / conlim / iter_lim as ce_vjp_lsqr; q_vals == NULL pins d_tau = 0 and drops the tau row.
+ * Tangents in the boundary convention: tA_vals_bm (B, nnz_aug) batch-major rows stA_b apart (tangent of A_eval = [-A.data, b]), tq_vals at [k * stq_k + i * stq_b]
+ * (tangent of q_eval = [c, 0]; the last entry is ignored); a NULL tangent is zero.  Outputs dx (B, n), dy (B, m), ds (B, m; may be NULL) batch-major;
+ * jvp_status[i] = 1 when LSQR hit iter_lim; lsqr_iters (B) or NULL.  Enqueues on `stream` only, never synchronises the host.
+ * CE_E_TOO_LARGE when the LSQR vectors of one instance exceed LDS; CE_E_UNSUPPORTED for a template whose quadratic objective runs inside the kernels
+ * (ce_qp_native: differentiate the epigraph cone form instead).
+ * ce_jvp_shared_a: the template's A part is shared (A_vals0 / sA_b as ce_vjp_shared_a, the split products): only the b entries of the tangent rows are read.
+ */
+int ce_jvp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s,
+                const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s,
+                    const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
