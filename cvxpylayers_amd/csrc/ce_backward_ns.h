@@ -19,6 +19,18 @@
 // the device-side list whose instances the LSQR kernel behind this launch re-solves with diffcp's own method (cone_engine.hip ce_vjp_qp) -- this kernel is only
 // launched when that re-solve is armed, so its answer on such instances is never the final one.
 //
+//
+// FWD = true: the FORWARD derivative (diffcp's `derivative`, cone_engine.hip ce_jvp) by the same elimination.  With d_tau pinned to 0 (M z = 0 at a solution and the
+// outputs do not change under d <- d + alpha z) diffcp's M d = -g, g = dQ pi, leaves  A^T D d_y = -g_x,  -A d_x + (I - D) d_y = -g_y  (A in the solver form stored
+// here): the transpose of the adjoint's block.  In the eigenbasis of D per cone (eta = W^T d_y, gamma = W^T g_y, rotated rows a~): lambda = 1 rows are the
+// equalities  a~ d_x = gamma  with eta their multiplier, lambda = 0 rows give  eta = a~ d_x - gamma,  the others  eta = (a~ d_x - gamma) / (1 - lambda), so
+//        H d_x + B^T eta_B = -g_x + sum theta a~^T gamma,      B d_x = gamma_B
+// with the H and B above:  f = -g_x + sum theta a~^T gamma,  d_B = gamma_B,  eta_B = -mu.  Load, classification, numbering, a_z, the e_y rows, the weighted-row list
+// and steps 1-4 are stated once; FWD has its own PROLOGUE (g from the instance's tangent row through the template's CSC / CSR structure and bpos, tangents in the
+// boundary convention of k_sa_lsqr<FWD>; gamma_y, gamma_s and the weights of f per boundary cone in the classification pass) and its own EPILOGUE behind mu
+// (eta for every row, rotated back:  dx = d_x,  dy = W lambda eta,  ds = -W (1 - lambda) eta).  It uses the adjoint's LDS buffers (y and x wait in tvec and rx for the
+// tangent products; g_y lives in dv, g_x in fvec): the footprint is bwd_ns_lds_bytes_of, the plan's ns_lds serves both.  Flags and the re-solve list as the adjoint.
+//
 // Plain cones (zero / nonnegative / second-order), linear objective.  PSD / exponential / power cones and quadratic objectives keep k_backward_rt.
 #pragma once
 
@@ -49,11 +61,14 @@ __host__ __device__ inline size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int 
 #define NS_SUB(i) do { } while (0)
 #endif
 
-template <int NTILE, int NTHR>
+template <bool FWD> struct NsFwdArg { typedef NsNoJvp type; };
+template <> struct NsFwdArg<true> { typedef NsJvp type; };
+
+template <int NTILE, int NTHR, bool FWD = false>
 __global__ void __launch_bounds__(NTHR, (NTHR == 256 ? 3 : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD>::type W) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -114,6 +129,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
 #pragma unroll
         for (int u = 0; u < LU; u++) { const int k = tid + u * NTHR, kc = k < nnz ? k : 0; v0[u] = vals[kc]; r0[u] = T.rowidx[kc]; c0[u] = k < nnz ? T.colidx[kc] : -1; }
         for (int i = tid; i < m * lda; i += NTHR) A[i] = 0.0;
+        if constexpr (FWD) {          // (y and x wait in tvec and rx for the tangent products of the prologue below)
+            for (int i = tid; i < m; i += NTHR) { const double yi = yg[(size_t)inst * m + i]; vv[i] = yi - sg[(size_t)inst * m + i]; tvec[i] = yi; }
+            for (int j = tid; j < n; j += NTHR) rx[j] = xg[(size_t)inst * n + j];
+        } else
         for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; dv[i] = dyg[(size_t)inst * m + i]; }
         if (tid < 8) misc[tid] = 0;
         __syncthreads();
@@ -127,10 +146,49 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         __syncthreads();
     }
+    if constexpr (FWD) {
+        // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
+        //      (k_sa_lsqr<FWD>'s prologue: dA = -tA_eval, db = +tA_eval[bpos], dc = tq_eval[:n]).  The instance's tangent row is read through the template's CSC
+        //      (the value order itself) and CSR structure, 8 lanes per column / row, four entries in flight per lane; fixed summation order.
+        const double *tA = W.tA ? W.tA + (size_t)inst * T.nnz_aug : nullptr;
+        for (int j0 = 0; j0 < n; j0 += NTHR / 8) {
+            const int j = j0 + (tid >> 3), c8 = tid & 7;
+            double a0 = 0.0, a1 = 0.0;
+            if (tA && j < n) {
+                const int k1 = W.csc_ptr[j + 1];
+                for (int k = W.csc_ptr[j] + c8; k < k1; k += 32) {
+                    double tv[4]; int ri[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[kk]; ri[u] = T.rowidx[kk]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, tvec[ri[u]], a1); else a0 = fma(t, tvec[ri[u]], a0); }
+                }
+            }
+            const double a = group_reduce<8, false>(a0 + a1);
+            if (j < n && c8 == 0) fvec[j] = (W.tq ? W.tq[j * W.stqk + inst * W.stqb] : 0.0) - a;
+        }
+        for (int i0 = 0; i0 < m; i0 += NTHR / 8) {
+            const int i = i0 + (tid >> 3), c8 = tid & 7;
+            double a0 = 0.0, a1 = 0.0;
+            if (tA && i < m) {
+                const int k1 = W.csr_ptr[i + 1];
+                for (int k = W.csr_ptr[i] + c8; k < k1; k += 32) {
+                    double tv[4]; int ci[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[W.csr_src[kk]]; ci[u] = W.csr_col[kk]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, rx[ci[u]], a1); else a0 = fma(t, rx[ci[u]], a0); }
+                }
+            }
+            const double a = group_reduce<8, false>(a0 + a1);
+            if (i < m && c8 == 0) { const int pb = tA ? W.bpos[i] : -1; dv[i] = (pb >= 0 ? tA[pb] : 0.0) + a; }
+        }
+        __syncthreads();
+    }
     NS_STAMP(1);
     // ---- classify + d = DPi(v) dy in ONE pass: 16 lanes per cone (a row per lane, sums by DPP butterflies inside the 16-lane row), nonnegative rows beside them.
     //      (One thread per cone walked its rows in dependent loops: 8 of 256 threads busy, ~25 k cycles for the two phases.)  dv holds dy: transformed in place.
-    for (int i = tid; i < z + T.l; i += NTHR) { const bool eq = (i < z || vv[i] > 0); rkind[i] = eq ? RK_EQ : RK_FREE; if (!eq) dv[i] = 0.0; }
+    for (int i = tid; i < z + T.l; i += NTHR) { const bool eq = (i < z || vv[i] > 0); rkind[i] = eq ? RK_EQ : RK_FREE; if constexpr (!FWD) if (!eq) dv[i] = 0.0; }
     for (int c0 = 0; c0 < nq; c0 += NTHR / 16) {
         const int c = c0 + (tid >> 4), l16 = tid & 15;
         const bool cv = c < nq;
@@ -146,6 +204,18 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         double zd = 0.0;
         const double i2n = kind == 2 ? 1.0 / (2 * nz) : 0.0, cz = kind == 2 ? t0 * zh / (nz * nz) : 0.0;
         const int rk = kind == 0 ? RK_EQ : (kind == 1 ? RK_FREE : RK_SOCB);
+        if constexpr (FWD) {
+            // the rows keep g_y (the epilogue wants it unrotated); per boundary cone gamma_y = e_y . g, gamma_s = e_s . g (cinfo[2], cinfo[3]) and the weights
+            // u_i = theta (g_i - z-hat_i (z-hat . g_z)) of the cone's z-rows in  f + g_x = sum theta a~^T gamma = A^T u  (tvec; 0 on the t-row)
+            for (int i = r0 + 1 + l16; i < r1; i += 16) rkind[i] = rk;
+            if (kind == 2) {
+                const double zeta = zh / nz, th = lam / (1 - lam), inz = 1.0 / nz;
+                for (int i = r0 + 1 + l16; i < r1; i += 16) tvec[i] = th * (dv[i] - vv[i] * inz * zeta);
+                if (l16 == 0) { tvec[r0] = 0.0; cinfo[5 * c + 2] = (h0 + zeta) * M_SQRT1_2; cinfo[5 * c + 3] = (h0 - zeta) * M_SQRT1_2; }
+            }
+            if (cv && l16 == 0) { rkind[r0] = rk; ckind[c] = kind; cinfo[5 * c] = lam; cinfo[5 * c + 1] = nz; cinfo[5 * c + 4] = lam / (1 - lam); }
+            continue;
+        }
         for (int i = r0 + 1 + l16; i < r1; i += 16) {
             rkind[i] = rk;
             if (kind == 1) dv[i] = 0.0;
@@ -211,9 +281,15 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         __syncthreads();
     }
     const int neq = misc[0], KW = misc[3], KW4 = (KW + 4) & ~3;          // (at least one pad entry: entry KW stands for f in the null-space transform)
-    if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient; the LSQR launch behind this kernel serves it)
-        for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[(size_t)inst * T.nnz_aug + k] = 0.0;
-        for (int j = tid; j <= n; j += NTHR) dqo[j * sdqk + inst * sdqb] = 0.0;
+    if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient / zero tangents; the LSQR launch behind this kernel serves it)
+        if constexpr (FWD) {
+            for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = 0.0;
+            for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = 0.0; if (W.ds) W.ds[(size_t)inst * m + i] = 0.0; }
+            if (tid == 0 && W.iters) W.iters[inst] = 0;
+        } else {
+            for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[(size_t)inst * T.nnz_aug + k] = 0.0;
+            for (int j = tid; j <= n; j += NTHR) dqo[j * sdqk + inst * sdqb] = 0.0;
+        }
         if (tid == 0) { if (adj_status) adj_status[inst] = 2; if (fix) fix[1 + atomicAdd(fix, 1)] = inst; }
         return;
     }
@@ -242,6 +318,8 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
         }
         acc = group_reduce<4, false>(acc);
+        if constexpr (FWD) { if (j < n && part == 0) fvec[j] = acc - fvec[j]; }          // f = -g_x + sum theta a~^T gamma
+        else
         if (j < n && part == 0) fvec[j] = acc + dxg[(size_t)inst * n + j];
     }
     __syncthreads();
@@ -774,6 +852,51 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     }
     __syncthreads();
     NS_STAMP(8);
+    if constexpr (FWD) {
+        // ---- FWD epilogue: d_x = r_x, eta_B = -mu; per row eta = W^T d_y, then dy = W lambda eta -> vv, ds = -W (1 - lambda) eta -> dv (dv held g_y):
+        //      equality rows dy = eta, ds = 0; eliminated rows (lambda = 0) dy = 0, ds = gamma - a . d_x (their rows of A are untouched: 4 lanes per row);
+        //      boundary cones from gamma_y, gamma_s, q_i = a_i . d_x (qv2) and a_z . d_x (qaz), with p = (I - z-hat z-hat^T)(A_z d_x - g_z) = (1 - lambda) eta_perp.
+        for (int i0 = 0; i0 < m; i0 += NTHR / 4) {
+            const int i = i0 + (tid >> 2), part = tid & 3;
+            const bool live = i < m && rkind[i < m ? i : 0] == RK_FREE;
+            double a0 = 0.0, a1 = 0.0;
+            if (live) {
+                const double *row = A + i * lda;
+                for (int j = part; j < n; j += 8) {
+                    const int j2 = min(j + 4, n - 1);
+                    const double r0v = row[j], r1v = row[j2], x0 = rx[j], x1 = rx[j2];
+                    a0 = fma(r0v, x0, a0); a1 = fma(r1v, (j + 4 < n) ? x1 : 0.0, a1);
+                }
+            }
+            const double a = group_reduce<4, false>(a0 + a1);
+            if (live && part == 0) { dv[i] -= a; vv[i] = 0.0; }
+        }
+        for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) { vv[i] = -dB[eqrow[i]]; dv[i] = 0.0; }
+        for (int c = tid; c < nq; c += NTHR) {
+            if (ckind[c] != 2) continue;
+            const int r0 = T.qoff[c], r1 = T.qoff[c + 1];
+            const double inz = 1.0 / cinfo[5 * c + 1], gy = cinfo[5 * c + 2], gs = cinfo[5 * c + 3], th = cinfo[5 * c + 4];
+            const double etay = -dB[ceq[c]], zq = qaz[c], zeta = (gy - gs) * M_SQRT1_2;
+            const double ayd = pcol[ceq[c]] >= 0 ? gy : 0.0;                      // a_y . d_x = gamma_y (the equality; a dropped row is flagged anyway)
+            const double q0 = M_SQRT2 * ayd - zq;                                 // a_0 . d_x
+            const double etas = (q0 - zq) * M_SQRT1_2 - gs;                       // a_s . d_x - gamma_s
+            for (int i = r0 + 1; i < r1; i++) {
+                const double zh = vv[i] * inz, pp = (qv2[i] - zh * zq) - (dv[i] - zh * zeta);
+                vv[i] = fma(th, pp, zh * etay * M_SQRT1_2); dv[i] = zh * etas * M_SQRT1_2 - pp;
+            }
+            vv[r0] = etay * M_SQRT1_2; dv[r0] = -etas * M_SQRT1_2;
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = rx[j];
+        for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = vv[i]; if (W.ds) W.ds[(size_t)inst * m + i] = dv[i]; }
+        if (tid == 0) {
+            const int fl = misc[2];
+            if (adj_status) adj_status[inst] = fl;
+            if (W.iters) W.iters[inst] = 0;
+            if (fix && (fl & 4)) fix[1 + atomicAdd(fix, 1)] = inst;      // rank-deficient system: the LSQR launch behind this kernel re-solves it (ce_jvp)
+        }
+        return;
+    }
     // ---- r_y (as k_backward_rt; the t-row of a boundary cone holds a_y: a_0 . r_x = sqrt 2 (a_y . r_x) - a_z . r_x)
     for (int i = tid; i < z + T.l; i += NTHR) vv[i] = (eqrow[i] >= 0) ? dB[eqrow[i]] : dv[i];
     for (int c = tid; c < nq; c += NTHR) {

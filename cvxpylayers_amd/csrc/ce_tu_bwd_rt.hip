@@ -49,14 +49,22 @@ hipError_t ce_setattr_bwd_rt_plain(int bytes) { return setattr_brt<CE_BRT_PSD !=
 // search-free null-space adjoint (ce_backward_ns.h)
 int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a) {
     switch (variant) {
-#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.fix); return 0;
+#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.fix, NsNoJvp{}); return 0;
+        CE_NS_VARIANTS(X)
+#undef X
+    default: return -1;
+    }
+}
+int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w) {
+    switch (variant) {
+#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR, true>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, nullptr, nullptr, nullptr, nullptr, 0L, 0L, a.adj, a.fix, w); return 0;
         CE_NS_VARIANTS(X)
 #undef X
     default: return -1;
     }
 }
 hipError_t ce_setattr_bwd_ns(int bytes) {
-#define X(V, NTILE, NTHR) SETATTR((k_backward_ns<NTILE, NTHR>));
+#define X(V, NTILE, NTHR) SETATTR((k_backward_ns<NTILE, NTHR>)); SETATTR((k_backward_ns<NTILE, NTHR, true>));
     CE_NS_VARIANTS(X)
 #undef X
     return hipSuccess;

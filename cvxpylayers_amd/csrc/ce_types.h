@@ -48,6 +48,20 @@ struct CeBwdArgs {
     int nonfinal;               // k_backward_rt: 1 = first launch of a two-tile plan (an instance this tile does not hold is not listed: the retry launch serves it)
 };
 
+// k_backward_ns<..., FWD = true> (ce_backward_ns.h): what the forward derivative's elimination reads and writes beside CeBwdArgs' A, x, y, s, adj and fix
+struct NsJvp {
+    const int *csc_ptr;      // [n + 1]  column starts of the A part in the value order (its rows: DevT::rowidx)
+    const int *csr_ptr;      // [m + 1]
+    const int *csr_col;      // [nnzA]
+    const int *csr_src;      // [nnzA]   position of the entry in the value order
+    const int *bpos;         // [m]      position of the row's b entry in the value order (-1: structurally zero)
+    const double *tA;        // [B][nnz_aug] tangent of the value rows (NULL: zero)
+    const double *tq; long stqk, stqb;       // tangent of q_eval, entry j of instance i at j * stqk + i * stqb (NULL: zero)
+    double *dx, *dy, *ds;    // [B][n], [B][m], [B][m] (ds may be NULL)
+    int *iters;              // [B] <- 0: a directly solved instance took no LSQR iteration (NULL: not wanted)
+};
+struct NsNoJvp {};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -57,6 +71,7 @@ int ce_launch_fwd_rt(int variant, int B, size_t lds, hipStream_t st, const CeFwd
 int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones)
+int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);      // the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // raise the dynamic-LDS limit of every kernel of the family

@@ -1088,12 +1088,14 @@ int ce_vjp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const do
 }
 static int jvp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
-                           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+                           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
+                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr) {
+    // sel: the re-solve list of ce_jvp (B is then the fixed grid that walks it; the kernel addresses every per-instance array by the LISTED instance)
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     if (h->plan.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
     const SaJvp W{tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds};
     return vjp_lsqr_launch(h, B, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, nullptr, nullptr, nullptr, nullptr, 0, 0, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream,
-                           nullptr, 0, nullptr, &W);
+                           sel, status_or, sel_reset, &W);
 }
 int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const double *q_vals, long sq_k, long sq_b,
                     const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
@@ -1105,6 +1107,39 @@ int ce_jvp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const do
                 double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
     if (sA_b == 0 && B > 1) { g_err = "ce_jvp_lsqr: per-instance values need a batch stride"; return CE_E_BADARG; }
     return jvp_lsqr_launch(h, B, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+           const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    // the forward derivative as ce_vjp_qp runs the adjoint: the search-free elimination (k_backward_ns<..., FWD>), then the fixed grid of LSQR workgroups that
+    // re-solves the instances it listed as rank deficient -- the same two alternating lists, no memset, no host round trip
+    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
+    if (P.ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    if (sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, h->psd_first, T.nep + T.np) * 8 > LDS_LIMIT) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = "ce_jvp: A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (h->fix_cap < B) {
+        HIPCHK(h->d_fix.reserve(2 * ((size_t)B + 1))); h->fix_cap = B; h->fix_par = 0;
+        HIPCHK(hipMemsetAsync(h->d_fix.get(), 0, sizeof(int) * 2 * ((size_t)B + 1), st));
+    }
+    int *const fix_cur = h->d_fix.get() + (size_t)h->fix_par * (h->fix_cap + 1), *const fix_oth = h->d_fix.get() + (size_t)(1 - h->fix_par) * (h->fix_cap + 1);
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix_cur;
+    const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
+    if (ce_launch_fwd_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
+    const int prof_keep = h->prof; h->prof = 0;          // (inside this scope's bracket already)
+    const int rc = jvp_lsqr_launch(h, B < 768 ? B : 768, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
+                                   atol, btol, conlim, iter_lim, stream, fix_cur, 4 | 8, fix_oth);
+    h->fix_par ^= 1;
+    h->prof = prof_keep;
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return CE_OK;
 }
 int ce_ca_triples(ce_handle h, int B, int lp, double *U, double *roots, const int *active, void *stream) {
     if (!h || B <= 0 || !U || !roots || !active) { g_err = "null argument"; return CE_E_BADARG; }

@@ -41,7 +41,7 @@ class ConeEngine:
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
-        self.last_jvp_kernel = None           # "ce_jvp_lsqr" / "ce_jvp_shared_a"
+        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -331,11 +331,16 @@ class ConeEngine:
                                          "falling back to the direct elimination (rank-deficient instances are flagged in info['adjoint'])")
         return out
 
-    def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8):
+    def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "lsqr"):
         """Forward-mode derivative of the solution map (diffcp's `derivative`): tangents tA_bm (B, nnz_aug) of the value rows and tq (n+1, B) of q_eval, either may be
         None (zero).  Returns dx (B, n), dy (B, m), ds (B, m), status (B,) -- 1: LSQR hit its iteration limit -- and sets last_lsqr_iters.
         One kernel per call, ce_jvp_lsqr, or ce_jvp_shared_a when `path` is "const_a" (only the b entries of tA_bm are read there: a shared A has no tangent).
-        path, lsqr (rule, adjoint_system) and q_eval as vjp(); the LSQR recurrences only.  NotImplementedError when the LSQR vectors of one instance exceed LDS."""
+        path, lsqr (rule, adjoint_system) and q_eval as vjp(); the LSQR recurrences only.  NotImplementedError when the LSQR vectors of one instance exceed LDS.
+        method="direct": ce_jvp on the per-instance path -- the search-free elimination, then LSQR under the same rule for the instances it flags rank deficient
+        (status 4 | 8 and iterations > 0 there, status 0 and 0 iterations elsewhere).  Where the library has no elimination for the template, and on the const_a
+        path, the LSQR call runs instead; last_jvp_kernel names the entry point that ran."""
+        if method not in ("lsqr", "direct"):
+            raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -357,9 +362,17 @@ class ConeEngine:
         qd, q_args = self._q_args(q_eval)
         dx = torch.empty((B, self.n), **f64); dy = torch.empty((B, self.m), **f64); ds = torch.empty((B, self.m), **f64)
         st = torch.empty((B,), dtype=torch.int32, device=dev); its = torch.empty((B,), dtype=torch.int32, device=dev)
-        rc = fn(self._h, B, A_c.data_ptr(), A_c.stride(0), *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
-                tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args, dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(),
-                float(atol), float(btol), float(conlim), int(lim), self._stream())
+        def call(fn, A_t):
+            return fn(self._h, B, A_t.data_ptr(), A_t.stride(0), *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                      tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args, dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(),
+                      float(atol), float(btol), float(conlim), int(lim), self._stream())
+        rc = -2
+        if method == "direct" and not shared:
+            rc = call(_lib.lib().ce_jvp, A_c if A_c.stride(0) == self.nnz_aug else A_c.contiguous())
+            if rc != -2:          # (CE_E_UNSUPPORTED: no elimination for this template -- the LSQR call below serves it)
+                name = "ce_jvp"
+        if rc == -2:
+            rc = call(fn, A_c)
         if rc in (-2, -3):
             raise NotImplementedError(_lib.lib().ce_last_error().decode())
         _lib.check(rc, name)

@@ -25,7 +25,7 @@ from cvxpylayers_amd.interfaces.cone_engine import ConeEngine
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, lsqr_rule, make_settings, note_ignored_args, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lsqr_rule, make_settings, note_ignored_args, unpack_rule)
 
 
 class MI355_ctx:
@@ -145,6 +145,7 @@ class _Saved(NamedTuple):
     failed: Optional[torch.Tensor]          # raise_on_error=False: mask of the instances returned as NaN
     lsqr: tuple                             # lsqr_rule() of this call
     q_eval: Optional[torch.Tensor]          # (n+1, B) objective values (linear objective only)
+    jvp_mode: str = "lsqr"                  # jvp_mode() of this call
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -205,7 +206,8 @@ class _ConeLayer(torch.autograd.Function):
             # are diffcp's LSQR element from the device-side re-solve); adjoint_report(info) counts them
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
             lsqr = lsqr_rule(merged_args, eng.n, eng.m)
-            saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if P_bm is None else None) if needs_grad else None
+            fwd_mode = jvp_mode(merged_args)
+            saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if P_bm is None else None, fwd_mode) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -250,7 +252,9 @@ class _ConeLayer(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, tP, tq, tA, *_):
         """Forward-mode derivative (torch.autograd.forward_ad; diffcp's `derivative`, which the reference plugin never calls): the tangents of q_eval / A_eval in,
-        the tangents of (primal, dual) out, by one launch of the LSQR kernel on M d = -dQ pi (ConeEngine.jvp) under this call's lsqr_rule.  Fills info["jvp"]."""
+        the tangents of (primal, dual) out, by one launch of the LSQR kernel on M d = -dQ pi (ConeEngine.jvp) under this call's lsqr_rule -- or, with solver_args
+        jvp_mode="direct", by the direct elimination with LSQR for the rank-deficient instances only.  Fills info["jvp"]: status, iters and the path that ran
+        ("direct" / "lsqr": a template without the elimination runs LSQR and says so)."""
         saved, batch_size, originally_unbatched, in_device = ctx.backward_data
         if saved is None:
             raise RuntimeError("forward-mode derivative requested from a layer evaluated with needs_grad=False")
@@ -271,12 +275,12 @@ class _ConeLayer(torch.autograd.Function):
                 x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
             # a shared-A call whose A values merely coincide may still carry a tangent in A: the shared kernel reads the b entries only
             path = saved.path if (saved.path != "const_a" or tA_bm is None or eng.A_is_constant) else "per_instance"
-            dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval)
+            dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode)
             if failed is not None:
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel == "ce_jvp" else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod

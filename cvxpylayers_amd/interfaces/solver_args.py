@@ -25,7 +25,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -63,6 +63,18 @@ def adjoint_mode(merged_args: dict) -> str:
     "lsqr" -> diffcp's LSQR on the full (n + m + 1) system with its stopping rule for every instance (ce_vjp_lsqr).  Shared-A templates run LSQR whatever the mode says."""
     mode = str(merged_args.get("mode", ""))
     return "lsqr" if mode in ("lsqr", "lsmr") else ("dense" if mode == "dense" else "direct")          # ("lsmr": the iterative path with LSMR's recurrences, lsqr_rule()[4])
+
+
+def jvp_mode(merged_args: dict) -> str:
+    """How the forward-mode derivative (torch.autograd.forward_ad) solves diffcp's M d = -dQ pi on PER-INSTANCE-A templates:
+    absent / "lsqr" -> diffcp's LSQR for every instance (ce_jvp_lsqr);
+    "direct" -> the search-free elimination the default adjoint runs, and behind it on the device LSQR for exactly the instances it finds rank deficient
+    (ce_jvp).  Templates without that elimination (PSD / exponential / power cones, n > 108) and shared-A templates run LSQR whatever this says;
+    info["jvp"]["path"] tells which one ran."""
+    mode = str(merged_args.get("jvp_mode", "lsqr"))
+    if mode not in ("lsqr", "direct"):
+        raise ValueError(f"MI355 solver: jvp_mode must be 'lsqr' or 'direct', got {mode!r}")
+    return mode
 
 
 _WARNED: set = set()

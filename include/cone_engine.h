@@ -91,8 +91,8 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 13
+ * layout, an entry point's signature or the meaning of an argument changes (14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+#define CE_ABI_VERSION 14
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -306,6 +306,19 @@ int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const 
                     const double *x, const double *y, const double *s,
                     const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                     double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+/*
+ * The forward derivative by DIRECT ELIMINATION, what ce_vjp is to ce_vjp_lsqr: with d_tau pinned to 0 the system M d = -dQ pi reduces, cone block by cone block, to the
+ * saddle system of ce_vjp's search-free null-space elimination (the transposed block: same reduced Hessian and equality rows, another right-hand side and
+ * epilogue), solved by the same kernel; behind it a fixed grid of ce_jvp_lsqr's workgroups re-solves, on the device, the instances the elimination found rank
+ * deficient with diffcp's LSQR under atol / btol / conlim / iter_lim (no host round trip).  Arguments, conventions and outputs as ce_jvp_lsqr (per-instance A).
+ * jvp_status[i] is ce_vjp's bit field: 0 solved directly (lsqr_iters[i] = 0); 4 | 8 = rank deficient, re-solved by LSQR (bit 0: it hit iter_lim; lsqr_iters[i] > 0).
+ * CE_E_UNSUPPORTED when the template has no search-free elimination (ce_adjoint_ns_variant(h) < 0: PSD / exponential / power cones, n > 108, a quadratic
+ * objective inside the kernels) or the LSQR vectors of one instance exceed LDS: callers use ce_jvp_lsqr.
+ */
+int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+           const double *x, const double *y, const double *s,
+           const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
