@@ -31,6 +31,12 @@
 // (eta for every row, rotated back:  dx = d_x,  dy = W lambda eta,  ds = -W (1 - lambda) eta).  It uses the adjoint's LDS buffers (y and x wait in tvec and rx for the
 // tangent products; g_y lives in dv, g_x in fvec): the footprint is bwd_ns_lds_bytes_of, the plan's ns_lds serves both.  Flags and the re-solve list as the adjoint.
 //
+// REF = true (with FWD): one safeguarded NEWTON STEP on the KKT residual (cone_engine.hip ce_refine).  With v = y - s, y^ = Pi(v), s^ = y^ - v the residual map
+//        F_x = A^T y^ + c,   F_y = A x + s^ - b        has the Jacobian system   A^T D dv = -F_x,  -A dx + (I - D) dv = F_y,
+// the forward derivative's block with g_x = F_x, g_y = -F_y: the FWD path runs unchanged between another PROLOGUE (projection, the two dense products with the A
+// in LDS, b through bpos, c from q_eval, rho before) and another EPILOGUE behind eta (x+ = x + dx, v+ = v + dy - ds, projection, the value row scattered into LDS
+// again, rho after, keep or reject, x, y, s written in place).  No buffer beyond the adjoint's (the block maxima go through `red`).  A flagged instance keeps its point.
+//
 // Plain cones (zero / nonnegative / second-order), linear objective.  PSD / exponential / power cones and quadratic objectives keep k_backward_rt.
 #pragma once
 
@@ -61,14 +67,26 @@ __host__ __device__ inline size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int 
 #define NS_SUB(i) do { } while (0)
 #endif
 
-template <bool FWD> struct NsFwdArg { typedef NsNoJvp type; };
-template <> struct NsFwdArg<true> { typedef NsJvp type; };
+// where v = (t0, z) of a second-order cone of dimension d, |z| = nz, lies: 0 inside the cone (DPi = I), 1 inside its polar (DPi = 0), 2 outside both (lam: the
+// eigenvalue (t0 + nz) / (2 nz) of DPi on z-hat's complement).  ONE statement for the classification pass and for the projection of the refinement mode: the Newton
+// step is right only when D and y-hat = Pi(v) come from the same decision.
+__device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &lam) {
+    int kind; lam = 0.0;
+    if (d == 1) kind = t0 >= 0 ? 0 : 1;
+    else if (nz <= t0) kind = 0; else if (nz <= -t0) kind = 1; else { kind = 2; lam = (t0 + nz) / (2 * nz); }
+    return kind;
+}
 
-template <int NTILE, int NTHR, bool FWD = false>
+template <bool FWD, bool REF = false> struct NsFwdArg { typedef NsNoJvp type; };
+template <> struct NsFwdArg<true, false> { typedef NsJvp type; };
+template <> struct NsFwdArg<true, true> { typedef NsRefine type; };
+
+template <int NTILE, int NTHR, bool FWD = false, bool REF = false>
 __global__ void __launch_bounds__(NTHR, (NTHR == 256 ? 3 : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD>::type W) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF>::type W) {
+    static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -90,7 +108,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     double *cinfo = p; p += 5 * nqs; // per cone: lambda, |z|, e_y.d, e_s.d, theta
     double *tvec = p; p += KWMAX;    // per weighted row: t_k = a_k . x_p ; later q_k = a_k . r_x
     double *wgt = p; p += KWMAX;     // per weighted row: its weight in H (theta_c for the z-rows of cone c, -theta_c for a_z)
-    double *red = p; p += NWB * 8;
+    double *red = p; p += NWB * 8;   // REF: the partial maxima of the residual norms, two per wave
     double *qaz = p; p += nqs;       // a_z . r_x per cone
     p += (p - sm) & 1;
     double *U = p; p += bwd_ns_union_doubles(n, m, nqs, NTILE);
@@ -119,6 +137,94 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     __shared__ long long tstamp[16], tsub[16];
     if (threadIdx.x < 16) tsub[threadIdx.x] = 0;
 #endif
+    // ---- REF: the instance's record of this call.  An instance the forward solve failed on (16), one whose earlier step the safeguard rejected (2) or the
+    //      elimination flagged (4) keeps its point bit for bit and takes no further step.  rho_cur: rho of the point as stored when it was written.
+    int rst0 = 0; double rho_cur = 0.0, rho0 = 0.0;
+    if constexpr (REF) {
+        rst0 = W.first ? ((W.status && W.status[inst] < 0) ? 16 : 0) : W.rstatus[inst];
+        if (!W.first) rho_cur = W.resid[2 * (size_t)inst + 1];
+        if (W.first && tid == 0) {
+            W.rstatus[inst] = rst0; W.steps[inst] = 0;
+            if (rst0) { W.resid[2 * (size_t)inst] = __builtin_nan(""); W.resid[2 * (size_t)inst + 1] = __builtin_nan(""); }
+        }
+        if (rst0 & (2 | 4 | 16)) return;
+    }
+    // REF: y-hat = the projection of v onto the dual cone (zero -> free, nonnegative, second-order) by ns_soc_kind, the decision of the classification pass below
+    // (16 lanes per cone); s-hat = y-hat - v
+    auto project_dual = [&](const double *vs, double *yh) {
+        if constexpr (!REF) return;
+        else {
+        for (int i = tid; i < z + T.l; i += NTHR) { const double w = vs[i]; yh[i] = (i < z || w > 0) ? w : 0.0; }
+        for (int c0 = 0; c0 < nq; c0 += NTHR / 16) {
+            const int c = c0 + (tid >> 4), l16 = tid & 15;
+            const bool cv = c < nq;
+            const int r0 = cv ? T.qoff[c] : 0, r1 = cv ? T.qoff[c + 1] : 0, d = r1 - r0;
+            const double t0 = cv ? vs[r0] : 0.0;
+            double nz2 = 0.0;
+            for (int i = r0 + 1 + l16; i < r1; i += 16) { const double w = vs[i]; nz2 = fma(w, w, nz2); }
+            nz2 = group_reduce<16, false>(nz2);
+            const double nz = sqrt(nz2);
+            double lam;
+            const int kind = ns_soc_kind(d, t0, nz, lam);
+            if (kind == 0) lam = 1.0;          // Pi(v) = v inside the cone, 0 inside the polar, lam (nz, z) else
+            for (int i = r0 + 1 + l16; i < r1; i += 16) yh[i] = lam * vs[i];
+            if (cv && l16 == 0) yh[r0] = kind == 2 ? lam * nz : lam * t0;
+        }
+        }
+    };
+    // REF: the KKT residual at (x, y-hat, s-hat) of the instance in A:  F_x = A^T y-hat + c,  F_y = A x + s-hat - b  (b through bpos, c from q_eval); returns
+    // rho = max(|F_x|, |F_y|) / (1 + max(|b|, |c|)), a non-finite entry counting as infinite.  keep: F_x -> fvec, -F_y -> dv (g_x, g_y of the elimination).
+    // Four lanes per column / row, fixed summation order; ends behind a barrier.
+    auto kkt_residual = [&](const double *xs, const double *yh, const double *vs, bool keep) -> double {
+        if constexpr (!REF) return 0.0;
+        else {
+        const double *vals = Avals + (size_t)inst * T.nnz_aug;
+        const double inf = __builtin_inf();
+        double mx = 0.0, sc = 0.0;
+        for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
+            const int j = j0 + (tid >> 2), part = tid & 3;
+            double a0 = 0.0, a1 = 0.0;
+            if (j < n) for (int i = part; i < m; i += 8) {
+                const int i2 = min(i + 4, m - 1);
+                const double r0v = A[i * lda + j], r1v = A[i2 * lda + j], y0 = yh[i], y1 = yh[i2];
+                a0 = fma(r0v, y0, a0); a1 = fma(r1v, (i + 4 < m) ? y1 : 0.0, a1);
+            }
+            const double a = group_reduce<4, false>(a0 + a1);
+            if (j < n && part == 0) {
+                const double cj = W.q[j * W.sqk + inst * W.sqb], f = a + cj, fa = fabs(f);
+                if (keep) fvec[j] = f;
+                mx = fmax(mx, fa < inf ? fa : inf); sc = fmax(sc, fabs(cj));
+            }
+        }
+        for (int i0 = 0; i0 < m; i0 += NTHR / 4) {
+            const int i = i0 + (tid >> 2), part = tid & 3;
+            double a0 = 0.0, a1 = 0.0;
+            if (i < m) {
+                const double *row = A + i * lda;
+                for (int j = part; j < n; j += 8) {
+                    const int j2 = min(j + 4, n - 1);
+                    const double r0v = row[j], r1v = row[j2], x0 = xs[j], x1 = xs[j2];
+                    a0 = fma(r0v, x0, a0); a1 = fma(r1v, (j + 4 < n) ? x1 : 0.0, a1);
+                }
+            }
+            const double a = group_reduce<4, false>(a0 + a1);
+            if (i < m && part == 0) {
+                const int pb = W.bpos[i];
+                const double bi = pb >= 0 ? vals[pb] : 0.0, f = a + (yh[i] - vs[i]) - bi, fa = fabs(f);
+                if (keep) dv[i] = -f;
+                mx = fmax(mx, fa < inf ? fa : inf); sc = fmax(sc, fabs(bi));
+            }
+        }
+        mx = wave_reduce_dpp<true>(mx); sc = wave_reduce_dpp<true>(sc);
+        if (lane == 0) { red[2 * wave] = mx; red[2 * wave + 1] = sc; }
+        __syncthreads();
+        double mxa = 0.0, sca = 0.0;
+#pragma unroll
+        for (int w = 0; w < NWB; w++) { mxa = fmax(mxa, red[2 * w]); sca = fmax(sca, red[2 * w + 1]); }
+        __syncthreads();
+        return mxa / (1.0 + sca);
+        }
+    };
     NS_STAMP(0);
     // ---- load: the instance's values scattered into dense solver form A = -A_cvx (b is not needed: r_tau is pinned)
     {
@@ -129,7 +235,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
 #pragma unroll
         for (int u = 0; u < LU; u++) { const int k = tid + u * NTHR, kc = k < nnz ? k : 0; v0[u] = vals[kc]; r0[u] = T.rowidx[kc]; c0[u] = k < nnz ? T.colidx[kc] : -1; }
         for (int i = tid; i < m * lda; i += NTHR) A[i] = 0.0;
-        if constexpr (FWD) {          // (y and x wait in tvec and rx for the tangent products of the prologue below)
+        if constexpr (REF) {          // (in / out arrays: read through the pointers they are written through)
+            for (int i = tid; i < m; i += NTHR) vv[i] = W.y[(size_t)inst * m + i] - W.s[(size_t)inst * m + i];
+            for (int j = tid; j < n; j += NTHR) rx[j] = W.x[(size_t)inst * n + j];
+        } else if constexpr (FWD) {          // (y and x wait in tvec and rx for the tangent products of the prologue below)
             for (int i = tid; i < m; i += NTHR) { const double yi = yg[(size_t)inst * m + i]; vv[i] = yi - sg[(size_t)inst * m + i]; tvec[i] = yi; }
             for (int j = tid; j < n; j += NTHR) rx[j] = xg[(size_t)inst * n + j];
         } else
@@ -146,7 +255,14 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         __syncthreads();
     }
-    if constexpr (FWD) {
+    if constexpr (REF) {
+        // ---- REF prologue: the residual map itself in the place of dQ pi:  g_x = F_x -> fvec,  g_y = -F_y -> dv,  evaluated at the complementary pair
+        //      y-hat = Pi(v) (-> tvec), s-hat = y-hat - v, never at the caller's y, s;  rho before the step
+        project_dual(vv, tvec);
+        __syncthreads();
+        rho0 = kkt_residual(rx, tvec, vv, true);
+        if (W.first) rho_cur = rho0;
+    } else if constexpr (FWD) {
         // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
         //      (k_sa_lsqr<FWD>'s prologue: dA = -tA_eval, db = +tA_eval[bpos], dc = tq_eval[:n]).  The instance's tangent row is read through the template's CSC
         //      (the value order itself) and CSR structure, 8 lanes per column / row, four entries in flight per lane; fixed summation order.
@@ -198,9 +314,8 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         for (int i = r0 + 1 + l16; i < r1; i += 16) { const double w = vv[i]; nz2 = fma(w, w, nz2); zh = fma(w, dv[i], zh); }
         nz2 = group_reduce<16, false>(nz2); zh = group_reduce<16, false>(zh);
         const double nz = sqrt(nz2);
-        int kind; double lam = 0.0;
-        if (d == 1) kind = t0 >= 0 ? 0 : 1;
-        else if (nz <= t0) kind = 0; else if (nz <= -t0) kind = 1; else { kind = 2; lam = (t0 + nz) / (2 * nz); }
+        double lam;
+        const int kind = ns_soc_kind(d, t0, nz, lam);
         double zd = 0.0;
         const double i2n = kind == 2 ? 1.0 / (2 * nz) : 0.0, cz = kind == 2 ? t0 * zh / (nz * nz) : 0.0;
         const int rk = kind == 0 ? RK_EQ : (kind == 1 ? RK_FREE : RK_SOCB);
@@ -282,7 +397,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     }
     const int neq = misc[0], KW = misc[3], KW4 = (KW + 4) & ~3;          // (at least one pad entry: entry KW stands for f in the null-space transform)
     if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient / zero tangents; the LSQR launch behind this kernel serves it)
-        if constexpr (FWD) {
+        if constexpr (REF) {
+            if (tid == 0) { W.rstatus[inst] = rst0 | 4; if (W.first) W.resid[2 * (size_t)inst] = rho0; W.resid[2 * (size_t)inst + 1] = rho_cur; }
+        } else if constexpr (FWD) {
             for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = 0.0;
             for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = 0.0; if (W.ds) W.ds[(size_t)inst * m + i] = 0.0; }
             if (tid == 0 && W.iters) W.iters[inst] = 0;
@@ -887,6 +1004,43 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             vv[r0] = etay * M_SQRT1_2; dv[r0] = -etas * M_SQRT1_2;
         }
         __syncthreads();
+        if constexpr (REF) {
+            // ---- REF epilogue: x+ = x + dx -> rx,  v+ = v + (dy - ds) -> vv,  y+ = Pi(v+) -> tvec,  s+ = y+ - v+.  The elimination overwrote A: the instance's
+            //      value row is scattered again for rho at the new point.  The step is kept only when the elimination raised no flag and rho fell below the
+            //      rho of the point that came in (as evaluated now AND as recorded when that point was written: the record never increases); else nothing is written.
+            const bool flagged = (misc[2] & 4) != 0;
+            bool ok = false;
+            double rho1 = rho_cur;
+            if (!flagged) {          // (uniform)
+                const double *vals = Avals + (size_t)inst * T.nnz_aug;
+                for (int j = tid; j < n; j += NTHR) rx[j] += W.x[(size_t)inst * n + j];
+                for (int i = tid; i < m; i += NTHR) vv[i] = (W.y[(size_t)inst * m + i] - W.s[(size_t)inst * m + i]) + (vv[i] - dv[i]);
+                for (int i = tid; i < m * lda; i += NTHR) A[i] = 0.0;
+                __syncthreads();
+                for (int k0 = tid; k0 < T.nnzA; k0 += 4 * NTHR) {
+                    double v0[4]; int r0[4], c0[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int k = k0 + u * NTHR, kc = k < T.nnzA ? k : 0; v0[u] = vals[kc]; r0[u] = T.rowidx[kc]; c0[u] = k < T.nnzA ? T.colidx[kc] : -1; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (c0[u] >= 0) A[r0[u] * lda + c0[u]] = -v0[u];
+                }
+                project_dual(vv, tvec);
+                __syncthreads();
+                rho1 = kkt_residual(rx, tvec, vv, false);
+                ok = rho1 < fmin(rho0, rho_cur);
+                if (ok) {
+                    for (int j = tid; j < n; j += NTHR) W.x[(size_t)inst * n + j] = rx[j];
+                    for (int i = tid; i < m; i += NTHR) { const double yi = tvec[i]; W.y[(size_t)inst * m + i] = yi; W.s[(size_t)inst * m + i] = yi - vv[i]; }
+                }
+            }
+            if (tid == 0) {
+                W.rstatus[inst] = rst0 | (ok ? 1 : (flagged ? 4 : 2));
+                if (ok) W.steps[inst] += 1;
+                if (W.first) W.resid[2 * (size_t)inst] = rho0;
+                W.resid[2 * (size_t)inst + 1] = ok ? rho1 : rho_cur;
+            }
+            return;
+        } else {
         for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = rx[j];
         for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = vv[i]; if (W.ds) W.ds[(size_t)inst * m + i] = dv[i]; }
         if (tid == 0) {
@@ -896,6 +1050,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             if (fix && (fl & 4)) fix[1 + atomicAdd(fix, 1)] = inst;      // rank-deficient system: the LSQR launch behind this kernel re-solves it (ce_jvp)
         }
         return;
+        }
     }
     // ---- r_y (as k_backward_rt; the t-row of a boundary cone holds a_y: a_0 . r_x = sqrt 2 (a_y . r_x) - a_z . r_x)
     for (int i = tid; i < z + T.l; i += NTHR) vv[i] = (eqrow[i] >= 0) ? dB[eqrow[i]] : dv[i];

@@ -63,8 +63,16 @@ int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwd
     default: return -1;
     }
 }
+int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w) {
+    switch (variant) {
+#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR, true, true>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0L, 0L, nullptr, nullptr, w); return 0;
+        CE_NS_VARIANTS(X)
+#undef X
+    default: return -1;
+    }
+}
 hipError_t ce_setattr_bwd_ns(int bytes) {
-#define X(V, NTILE, NTHR) SETATTR((k_backward_ns<NTILE, NTHR>)); SETATTR((k_backward_ns<NTILE, NTHR, true>));
+#define X(V, NTILE, NTHR) SETATTR((k_backward_ns<NTILE, NTHR>)); SETATTR((k_backward_ns<NTILE, NTHR, true>)); SETATTR((k_backward_ns<NTILE, NTHR, true, true>));
     CE_NS_VARIANTS(X)
 #undef X
     return hipSuccess;

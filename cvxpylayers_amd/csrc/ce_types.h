@@ -61,6 +61,18 @@ struct NsJvp {
     int *iters;              // [B] <- 0: a directly solved instance took no LSQR iteration (NULL: not wanted)
 };
 struct NsNoJvp {};
+// k_backward_ns<..., FWD = true, REF = true>: one safeguarded Newton step on the KKT residual (cone_engine.hip ce_refine).  The kernel reads the instance's b through
+// bpos and c from q, updates x, y, s IN PLACE when the step is kept, and keeps the per-instance record of the call (one launch = one step)
+struct NsRefine {
+    const int *bpos;         // [m]      position of the row's b entry in the value order (-1: structurally zero)
+    const double *q; long sqk, sqb;          // q_eval, entry j of instance i at j * sqk + i * sqb
+    double *x, *y, *s;       // [B][n], [B][m], [B][m] in / out
+    const int *status;       // [B] forward status (< 0: the instance is skipped); NULL: every instance is refined
+    int *rstatus;            // [B] bit field: 1 a step was kept, 2 a step was rejected by the safeguard, 4 flagged by the elimination, 16 skipped
+    int *steps;              // [B] steps kept
+    double *resid;           // [B][2] rho before the first step, rho of the returned point
+    int first;               // 1: first launch of the call (the record is initialised)
+};
 
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
@@ -72,6 +84,7 @@ int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeF
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones)
 int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);      // the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused)
+int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);      // ... and for one Newton refinement step (a.T and a.Abm alone are read)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // raise the dynamic-LDS limit of every kernel of the family

@@ -1141,6 +1141,28 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
     HIPCHK(hipGetLastError());
     return CE_OK;
 }
+int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+              const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    // `steps` launches of k_backward_ns<..., FWD, REF>, one complete safeguarded Newton step each; the per-instance record (refine_status, steps_taken, resid)
+    // carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine: null argument or negative step count"; return CE_E_BADARG; }
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
+    if (P.ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_refine: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
+    for (int k = 0; k < steps; k++) {
+        const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
+        if (ce_launch_refine_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
 int ce_ca_triples(ce_handle h, int B, int lp, double *U, double *roots, const int *active, void *stream) {
     if (!h || B <= 0 || !U || !roots || !active) { g_err = "null argument"; return CE_E_BADARG; }
     const int ntri = h->T.nep + h->T.np;

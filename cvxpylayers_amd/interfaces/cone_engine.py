@@ -380,6 +380,31 @@ class ConeEngine:
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
+    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None):
+        """`steps` safeguarded Newton steps on the KKT residual of (x, y, s) (include/cone_engine.h ce_refine): A_bm (B, nnz_aug), q_eval (n+1, B), x (B, n), y, s
+        (B, m); status (B,) int32 or None: instances with a negative forward status are skipped.  Returns x, y, s, info -- contiguous fp64 tensors on this
+        engine's device are refined IN PLACE and handed back, others are copied first.  info: "status" (bits 1 a step kept, 2 a step rejected, 4 flagged by the
+        elimination, 16 skipped), "steps" (kept per instance), "resid_before" / "resid_after" (rho of the point that came in and of the one returned), "path"
+        "ns" -- or "none", with the other entries None and the point untouched, where the library has no elimination for the template.  No host synchronisation."""
+        B = A_bm.shape[0]
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        none = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
+        if B == 0 or int(steps) <= 0:
+            return x, y, s, none
+        x, y, s = (t.detach().to(**f64).contiguous() for t in (x, y, s))
+        A_c = A_bm if (A_bm.is_contiguous() and A_bm.dtype == torch.float64) else A_bm.to(torch.float64).contiguous()
+        qd, q_args = self._q_args(q_eval)
+        st_c = status.to(device=dev, dtype=torch.int32).contiguous() if status is not None else None
+        rst = torch.empty((B,), dtype=torch.int32, device=dev); taken = torch.empty((B,), dtype=torch.int32, device=dev)
+        resid = torch.empty((B, 2), **f64)
+        rc = _lib.lib().ce_refine(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                  st_c.data_ptr() if st_c is not None else None, int(steps), rst.data_ptr(), taken.data_ptr(), resid.data_ptr(), self._stream())
+        if rc == -2:
+            return x, y, s, none
+        _lib.check(rc, "ce_refine")
+        return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns"}
+
     # introspection (bench / tests)
     def set_profiling(self, on):
         """False / True, or a sum of 2 (forward), 4 (adjoint), 8 (layout passes): which launches are bracketed by HIP events (include/cone_engine.h)"""

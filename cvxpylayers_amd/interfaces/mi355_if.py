@@ -25,7 +25,7 @@ from cvxpylayers_amd.interfaces.cone_engine import ConeEngine
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lsqr_rule, make_settings, note_ignored_args, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lsqr_rule, make_settings, note_ignored_args, refine_steps, unpack_rule)
 
 
 class MI355_ctx:
@@ -174,6 +174,7 @@ class _ConeLayer(torch.autograd.Function):
         settings = make_settings(merged_args)
         note_ignored_args({"acceleration_lookback": settings.acceleration_lookback, **{k: merged_args[k] for k in ("mode", "solve_method", "n_jobs_forward", "n_jobs_backward") if k in merged_args}},
                           explicit_lookback="acceleration_lookback" in merged_args)
+        n_refine = refine_steps(merged_args)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
         with torch.cuda.device(dev):
@@ -188,6 +189,17 @@ class _ConeLayer(torch.autograd.Function):
                 P_bm = P_eval.detach().to(device=dev, dtype=torch.float64).t().contiguous()        # (B, nnz_p)
             x, y, s, iters, status, resid = eng.solve(A_bm, q_dev, settings, warm=warm, P_bm=P_bm)
             path = adjoint_path(eng.last_path, P_bm is not None, merged_args)          # recorded per call: the backward of THIS node must not follow a later solve's path
+            # solver_args refine_steps: Newton refinement behind the solve on the same stream, BEFORE the warm-start memory, the saved state and the failure
+            # masking are formed: warm starts, backward and jvp all see the refined point.  Failed instances (status < 0) are skipped on the device.
+            refine_info = None
+            if n_refine > 0:
+                refine_info = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
+                if P_bm is None and eng.last_path == "per_instance" and status.numel():
+                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status)
+                if refine_info["path"] == "none" and status.numel():
+                    _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD / "
+                                              "exponential / power cones, n > 108, a shared A, a quadratic objective inside the kernels); the solver's point is returned "
+                                              "unrefined (info['refine']['path'] == 'none')")
             eng._last_solution = (x.detach(), y.detach(), s)
             # The reference raises from forward() when an instance fails (diffcp_if.py:365-372), so the host has to learn the outcome here: one tiny
             # reduction kernel + 8 bytes into pinned memory behind the solve (ce_status_summary) and ONE stream synchronisation -- not the status
@@ -205,6 +217,8 @@ class _ConeLayer(torch.autograd.Function):
             # info["adjoint"] is filled by backward(): "status" = the per-instance bit field of include/cone_engine.h ce_vjp (4: rank-deficient system, 8: gradients
             # are diffcp's LSQR element from the device-side re-solve); adjoint_report(info) counts them
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
+            if refine_info is not None:
+                info["refine"] = refine_info
             lsqr = lsqr_rule(merged_args, eng.n, eng.m)
             fwd_mode = jvp_mode(merged_args)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if P_bm is None else None, fwd_mode) if needs_grad else None

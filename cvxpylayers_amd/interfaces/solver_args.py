@@ -4,6 +4,8 @@ from __future__ import annotations
 import ctypes as C
 import warnings
 
+import numpy as np
+
 from cvxpylayers_amd import _lib
 
 try:  # subclass diffcp.SolverError when diffcp is importable so `pytest.raises(diffcp.SolverError)` keeps working
@@ -25,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -75,6 +77,16 @@ def jvp_mode(merged_args: dict) -> str:
     if mode not in ("lsqr", "direct"):
         raise ValueError(f"MI355 solver: jvp_mode must be 'lsqr' or 'direct', got {mode!r}")
     return mode
+
+
+def refine_steps(merged_args: dict) -> int:
+    """Newton refinement steps behind the forward solve (ce_refine: the search-free elimination on the KKT residual, every step safeguarded so that the residual
+    never grows): an integer >= 0, default 0 = none.  Templates without that elimination (PSD / exponential / power cones, n > 108, shared-A paths, a quadratic
+    objective inside the kernels) keep the solver's point and say so once; info["refine"]["path"] tells which."""
+    v = merged_args.get("refine_steps", 0)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+        raise ValueError(f"MI355 solver: refine_steps must be an integer >= 0, got {v!r}")
+    return int(v)
 
 
 _WARNED: set = set()

@@ -91,8 +91,8 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 14
+ * layout, an entry point's signature or the meaning of an argument changes (15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+#define CE_ABI_VERSION 15
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -319,6 +319,29 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
            const double *x, const double *y, const double *s,
            const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
            double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+
+/*
+ * NEWTON REFINEMENT of solutions by ce_jvp's elimination.  For a point (x, y, s) let v = y - s, y^ = Pi(v) (the projection onto the dual cone), s^ = y^ - v: a
+ * complementary pair in the cones by construction.  The KKT residual there is  F_x = A^T y^ + c,  F_y = A x + s^ - b  (A = -A_vals, b = A_vals[b entries],
+ * c = q_vals[:n]),  rho = max(|F_x|_inf, |F_y|_inf) / (1 + max(|b|_inf, |c|_inf)).  One step solves the Jacobian system of (x, v) -> F,
+ *        A^T D dv = -F_x,    -A dx + (I - D) dv = F_y        (D = DPi(v)),
+ * which is ce_jvp's system with the residual in the place of dQ pi, by the same search-free elimination (one launch of the same kernel with another prologue and
+ * epilogue), and moves to  x+ = x + dx,  v+ = v + dv,  y+ = Pi(v+),  s+ = y+ - v+.
+ * SAFEGUARD: the step is kept only if rho(x+, y+, s+) < rho(x, y^, s^); otherwise the instance keeps its point bit for bit and takes no further step.  The same
+ * holds for an instance the elimination flags (a redundant equality row, a vanishing pivot of the reduced Hessian, more active rows than variables: no LSQR
+ * re-solve runs here) and for instances whose forward status is negative (status may be NULL: every instance is refined).  The returned point never has a
+ * larger rho than the one that came in.
+ * x (B, n), y, s (B, m) batch-major, updated IN PLACE; A_vals_bm (B, nnz_aug) contiguous batch-major rows (sA_b = nnz_aug); q_vals as ce_solve.
+ * refine_status[i] bits: 1 at least one step kept, 2 a step rejected by the safeguard, 4 flagged by the elimination, 16 skipped (failed forward status).
+ * steps_taken[i]: steps kept.  resid (B, 2): rho before the first step, rho of the returned point (NaN, NaN for a skipped instance).
+ * Enqueues `steps` launches on `stream` (steps = 0: none, the outputs are not written) and never synchronises the host.
+ * With ce_set_profiling on, the launches are bracketed under class 1 (the adjoint's kernel family: it is that kernel), although the plugin calls this inside forward().
+ * CE_E_UNSUPPORTED as ce_jvp: no search-free elimination (ce_adjoint_ns_variant(h) < 0: PSD / exponential / power cones, n > 108) or a quadratic objective
+ * inside the kernels.  CE_E_BADARG for rows that are not contiguous batch-major.
+ */
+int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+              double *x, double *y, double *s /* in/out */, const int *status /* may be NULL */, int steps,
+              int *refine_status, int *steps_taken, double *resid, void *stream);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
