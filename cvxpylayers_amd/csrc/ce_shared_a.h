@@ -21,22 +21,7 @@
 #endif
 #include "ce_shared_a_ops.h"
 
-struct SaStruct {            // sparse structure of the template's A part (device arrays, built once per engine)
-    const int *csc_ptr;      // [n + 1]   column starts in the value order of the boundary (CSC of [A_cvx | b_cvx], first nnzA entries)
-    const int *csc_row;      // [nnzA]
-    const int *csr_ptr;      // [m + 1]
-    const int *csr_col;      // [nnzA]
-    const int *csr_src;      // [nnzA]    position of the entry in the value order
-    int nnzA;
-    const int *bpos;         // [m]       position of the row's b entry in the value order (-1: structurally zero)
-};
-
-// FORWARD derivative (k_sa_lsqr<..., FWD = true>; diffcp's D, oracle/cone_oracle.c apply_M): tangents in, solution tangents out.  Null tangent = zero.
-struct SaJvp {
-    const double *tA; long stAb;             // [B][nnz_aug] tangent of the boundary's value rows (A part read only when the template's A is per instance)
-    const double *tq; long stqk, stqb;       // tangent of q_eval, entry j of instance i at j * stqk + i * stqb (the last entry is ignored)
-    double *dx, *dy, *ds;                    // [B][n], [B][m], [B][m] (ds may be null)
-};
+// SaStruct, SaJvp: ce_types.h (the launcher of ce_tu_sa_lsqr.hip takes them from the host)
 
 constexpr int SA_G = 8;      // lanes per row / column of a sparse product (DPP butterfly over 8 lanes)
 

@@ -22,22 +22,7 @@
 #define SA_T(k) do { } while (0)
 #endif
 
-struct SaFwd {
-    int r, RP;                   // dense rows, padded to a multiple of 16
-    const double *AdT;           // [n][RP]  equilibrated dense rows, transposed (solver sign), zero padded
-    const int *drow;             // [r]      row index of dense row a
-    const int *srow_col;         // [m]      column of a singleton row, -1 otherwise
-    const double *srow_val;      // [m]      its (equilibrated, solver-sign) value
-    const int *scol_ptr;         // [n + 1]  singleton rows of every column
-    const int *scol_row;         // [#singleton entries]
-    const double *gs;            // [n]      sum over the singleton rows of column j of d0_i a_i^2
-    const double *Dv, *Ev;       // [m], [n] equilibration
-    unsigned long long *psd_stats;   // debug (CE_PSD_STATS=1): projections / refinement steps / warm Jacobi fall-backs / cold starts, or null
-    double *aa_ws;                   // Anderson acceleration history, [B][4][lp] doubles of global memory (x_prev, f_prev, f_save, [w_prev when it does not fit LDS]; read once
-                                     // per acceleration_interval iterations), or null: plain iteration
-    int aa_w_lds;                    // the input of the last iteration (w_prev: read by the safeguard, written on two of ten iterations) lives in LDS
-    int psd_refine;                  // 1: eigen-refinement on the matrix cores (default); 0 (CE_PSD_REFINE=0): warm-started Jacobi sweeps only, restart at check iterations (round 2)
-};
+// SaFwd: ce_types.h (the launcher of ce_tu_sa_fwd.hip takes it from the host)
 
 // LDS doubles (see the carve in the kernel)
 __host__ __device__ inline size_t sa_fwd_cidx_doubles(int n, int m, int nq, int r, int nsing) {

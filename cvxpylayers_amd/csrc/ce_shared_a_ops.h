@@ -7,18 +7,7 @@
 #define SA_UR64 2
 #endif
 
-// fields the product routines read (SaFwd and SaSplit both carry them):
-//   r, AdT, drow[r], srow_col[m] (-1: not a singleton row), srow_val[m], scol_ptr[n + 1], scol_row[]
-struct SaSplit {
-    int r, RP;
-    const double *AdT;
-    const int *drow, *srow_col;
-    const double *srow_val;
-    const int *scol_ptr, *scol_row;
-    const int *rowslot;          // [m] slot a of a dense row, -1 otherwise
-    const int *sing_i;           // [n] the singleton row of column j when it has exactly one (the rule: bounds, -I embeddings), -1: none, -2: several (walk scol_ptr / scol_row)
-    const double *sing_v;        // [n] its value (filled with srow_val by k_sa_fill_split)
-};
+// SaSplit (ce_types.h) carries the fields the product routines read; SaFwd carries the same ones.
 
 // out[a] = sum_j AdT[j][a] xin[j]  (a < RP).  Thread (a-pair, g) sums rows j = g, g + ng, ... with eight 16-byte loads in flight (RP / 2 lanes
 // cover a row: a wave reads whole rows, 1 KB per instruction); partials through `part` (2 NTH doubles of LDS).  Ends synchronised.

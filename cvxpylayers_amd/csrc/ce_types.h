@@ -74,6 +74,72 @@ struct NsRefine {
     int first;               // 1: first launch of the call (the record is initialised)
 };
 
+// ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
+// fields the product routines read (SaFwd and SaSplit both carry them):
+//   r, AdT, drow[r], srow_col[m] (-1: not a singleton row), srow_val[m], scol_ptr[n + 1], scol_row[]
+struct SaSplit {
+    int r, RP;
+    const double *AdT;
+    const int *drow, *srow_col;
+    const double *srow_val;
+    const int *scol_ptr, *scol_row;
+    const int *rowslot;          // [m] slot a of a dense row, -1 otherwise
+    const int *sing_i;           // [n] the singleton row of column j when it has exactly one (the rule: bounds, -I embeddings), -1: none, -2: several (walk scol_ptr / scol_row)
+    const double *sing_v;        // [n] its value (filled with srow_val by k_sa_fill_split)
+};
+
+struct SaStruct {            // sparse structure of the template's A part (device arrays, built once per engine)
+    const int *csc_ptr;      // [n + 1]   column starts in the value order of the boundary (CSC of [A_cvx | b_cvx], first nnzA entries)
+    const int *csc_row;      // [nnzA]
+    const int *csr_ptr;      // [m + 1]
+    const int *csr_col;      // [nnzA]
+    const int *csr_src;      // [nnzA]    position of the entry in the value order
+    int nnzA;
+    const int *bpos;         // [m]       position of the row's b entry in the value order (-1: structurally zero)
+};
+
+// FORWARD derivative (k_sa_lsqr<..., FWD = true>; diffcp's D, oracle/cone_oracle.c apply_M): tangents in, solution tangents out.  Null tangent = zero.
+struct SaJvp {
+    const double *tA; long stAb;             // [B][nnz_aug] tangent of the boundary's value rows (A part read only when the template's A is per instance)
+    const double *tq; long stqk, stqb;       // tangent of q_eval, entry j of instance i at j * stqk + i * stqb (the last entry is ignored)
+    double *dx, *dy, *ds;                    // [B][n], [B][m], [B][m] (ds may be null)
+};
+
+struct SaFwd {
+    int r, RP;                   // dense rows, padded to a multiple of 16
+    const double *AdT;           // [n][RP]  equilibrated dense rows, transposed (solver sign), zero padded
+    const int *drow;             // [r]      row index of dense row a
+    const int *srow_col;         // [m]      column of a singleton row, -1 otherwise
+    const double *srow_val;      // [m]      its (equilibrated, solver-sign) value
+    const int *scol_ptr;         // [n + 1]  singleton rows of every column
+    const int *scol_row;         // [#singleton entries]
+    const double *gs;            // [n]      sum over the singleton rows of column j of d0_i a_i^2
+    const double *Dv, *Ev;       // [m], [n] equilibration
+    unsigned long long *psd_stats;   // debug (CE_PSD_STATS=1): projections / refinement steps / warm Jacobi fall-backs / cold starts, or null
+    double *aa_ws;                   // Anderson acceleration history, [B][4][lp] doubles of global memory (x_prev, f_prev, f_save, [w_prev when it does not fit LDS]; read once
+                                     // per acceleration_interval iterations), or null: plain iteration
+    int aa_w_lds;                    // the input of the last iteration (w_prev: read by the safeguard, written on two of ten iterations) lives in LDS
+    int psd_refine;                  // 1: eigen-refinement on the matrix cores (default); 0 (CE_PSD_REFINE=0): warm-started Jacobi sweeps only, restart at check iterations (round 2)
+};
+
+// arguments of one k_sa_fwd launch (T, F, S and the arrays in the kernel's order)
+struct CeSaFwdArgs {
+    DevT T; SaFwd F; ce_settings S;
+    const double *b_hat, *c_hat, *sigma, *nrm_b0, *nrm_c0, *warm_x, *warm_y, *warm_s;
+    double *x, *y, *s; int *iters, *status; double *resid;
+};
+// arguments of one k_sa_lsqr launch; the adjoint reads dx, dy and writes dA, dq, the forward derivative (FWD rows) reads and writes through W instead
+struct CeSaLsqrArgs {
+    DevT T; SaStruct S; SaSplit F;
+    const double *A_vals0; long sA_b; int per_inst;
+    const double *q; long sqk, sqb;
+    const double *x, *y, *s, *dx, *dy;
+    double *dA, *dq; long sdqk, sdqb; int *adj, *iters;
+    double atol, btol, conlim; int iter_lim;
+    const int *sel; int status_or, a_lds; int *sel_reset;      // the re-solve list of ce_vjp / ce_jvp (ce_shared_a.h)
+    SaJvp W;
+};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -87,6 +153,11 @@ int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwd
 int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);      // ... and for one Newton refinement step (a.T and a.Abm alone are read)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
+int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
+int ce_launch_sa_lsqr(int variant, int grid, size_t lds, hipStream_t st, const CeSaLsqrArgs &a);      // row of CE_SA_LSQR_VARIANTS; grid: B, or the fixed grid that walks a.sel
+// k_sa_fill_split (ce_shared_a_ops.h; its arguments in the kernel's order): refills the split's A_d^T (zeroed by the caller) and singleton values from this call's A
+void ce_launch_sa_fill_split(hipStream_t st, int nnzA, int RP, const int *rowidx, const int *colidx, const int *rowslot, const double *vals, double *AdT, double *srow_val,
+                             const int *sing_i, double *sing_v);
 // raise the dynamic-LDS limit of every kernel of the family
 hipError_t ce_setattr_fwd2_plain(int bytes);
 hipError_t ce_setattr_fwd2_psd(int bytes);
@@ -97,3 +168,5 @@ hipError_t ce_setattr_bwd_rt_plain(int bytes);
 hipError_t ce_setattr_bwd_rt_psd(int bytes);
 hipError_t ce_setattr_bwd_ns(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
+hipError_t ce_setattr_sa_fwd(int bytes);
+hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -1,7 +1,7 @@
-// ce_variants.h -- the instantiated variants of every tiled kernel family, stated ONCE.  The launcher translation units expand a
-// list into their `switch` and their set-attribute loop; the host (cone_engine.hip) expands the same list into its planning
-// table.  A row's first entry is the variant index the planner, ce_get_plan and the tests' ledger name it by; the planner takes
-// the FIRST row that fits, so the order of the rows is part of the plan.  The trailing 0 / 1 columns say for which kinds the
+// ce_variants.h -- the instantiated variants of every kernel family with more than one, stated ONCE.  The launcher translation units
+// expand a list into their `switch` and their set-attribute loop; the host (cone_engine.hip) expands the same list into its planning
+// table.  A row's first entry is the variant index the planner, ce_get_plan and the tests' ledger name it by; for the tiled families the
+// planner takes the FIRST row that fits, so the order of the rows is part of the plan (the shared-A families are selected by value).  The trailing 0 / 1 columns say for which kinds the
 // row is instantiated: a 0 discards the launch at compile time and the planner skips the row for templates of that kind.
 // Adding a variant: one row here, one ledger entry in tests/test_gpu_plan_edges.py::EXPECTED.
 #pragma once
@@ -38,3 +38,49 @@
     X(0, 2, 256) \
     X(1, 4, 256) \
     X(2, 7, 512)
+
+// k_sa_fwd (ce_shared_a_fwd.h), shared-A forward:  X(index, RP, threads per workgroup, CIDX, HTRI)
+//   RP: dense rows padded;  CIDX: the template's index arrays in LDS (512 threads only);  HTRI: exponential / power triples compiled in
+//   (rows without CIDX serve every cone kind).  The host selects a row by these values (cone_engine.hip sa_fwd_select): the order is free.
+#define CE_SA_FWD_VARIANTS(X) \
+    X(0, 16, 256, 0, 1) \
+    X(1, 32, 256, 0, 1) \
+    X(2, 64, 256, 0, 1) \
+    X(3, 16, 512, 0, 1) \
+    X(4, 32, 512, 0, 1) \
+    X(5, 64, 512, 0, 1) \
+    X(6, 16, 512, 1, 0) \
+    X(7, 32, 512, 1, 0) \
+    X(8, 64, 512, 1, 0) \
+    X(9, 16, 512, 1, 1) \
+    X(10, 32, 512, 1, 1) \
+    X(11, 64, 512, 1, 1)
+
+// k_sa_lsqr (ce_shared_a.h), LSQR adjoint and forward derivative:  X(index, RP, HPSD, HTRI, LSMR, FWD)
+//   RP 0: products through the CSR / CSC structure (per-instance values, or no split);  HPSD / HTRI: PSD blocks / triples compiled in;
+//   LSMR: Fong & Saunders' recurrences;  FWD: the forward derivative.  Selected by these values (cone_engine.hip sa_lsqr_select).
+//   (PSD without triples has no RP = 0 row: those calls run the general kernel.)
+#define CE_SA_LSQR_VARIANTS(X) \
+    X(0, 0, 1, 1, 0, 0) \
+    X(1, 16, 1, 1, 0, 0) \
+    X(2, 32, 1, 1, 0, 0) \
+    X(3, 64, 1, 1, 0, 0) \
+    X(4, 0, 0, 0, 0, 0) \
+    X(5, 16, 0, 0, 0, 0) \
+    X(6, 32, 0, 0, 0, 0) \
+    X(7, 64, 0, 0, 0, 0) \
+    X(8, 16, 1, 0, 0, 0) \
+    X(9, 32, 1, 0, 0, 0) \
+    X(10, 64, 1, 0, 0, 0) \
+    X(11, 0, 1, 1, 1, 0) \
+    X(12, 16, 1, 1, 1, 0) \
+    X(13, 32, 1, 1, 1, 0) \
+    X(14, 64, 1, 1, 1, 0) \
+    X(15, 0, 0, 0, 0, 1) \
+    X(16, 16, 0, 0, 0, 1) \
+    X(17, 32, 0, 0, 0, 1) \
+    X(18, 64, 0, 0, 0, 1) \
+    X(19, 0, 1, 1, 0, 1) \
+    X(20, 16, 1, 1, 0, 1) \
+    X(21, 32, 1, 1, 0, 1) \
+    X(22, 64, 1, 1, 0, 1)

@@ -48,9 +48,8 @@ namespace {
 #include "ce_backward_ns.h"    // bwd_ns_lds_bytes_of (launch planning); kernels in ce_tu_bwd_rt.hip
 #include "ce_psd_mfma.h"
 #include "ce_const_a.h"
-#include "ce_shared_a.h"
-#include "ce_shared_a_mi.h"
-#include "ce_shared_a_fwd.h"
+#include "ce_shared_a.h"      // sa_lsqr_lds_doubles (launch planning); k_sa_lsqr is instantiated in ce_tu_sa_lsqr.hip
+#include "ce_shared_a_fwd.h"  // sa_fwd_lds_doubles, sa_fwd_cidx_doubles; k_sa_fwd is instantiated in ce_tu_sa_fwd.hip
 }  // namespace
 
 // ================================================================================================
@@ -128,7 +127,8 @@ struct ce_engine {
     DevBuf<int> d_sp_drow, d_sp_srow_col, d_sp_scol_ptr, d_sp_scol_row, d_sp_rowslot, d_sp_sing_i;
     DevBuf<double> d_sp_sing_v, d_sp_AdT, d_sp_sval;
     DevBuf<int> d_bpos;          // [m] position of the row's b entry in the boundary's value order (-1: structurally zero): the tau column of the shared-A adjoint
-    bool sa_fwd_attr = false, sa_lsqr_attr = false, sa_lsqr_mi_attr = false;      // MaxDynamicSharedMemorySize is per device: set once per engine (an engine is bound to one device, one caller thread)
+    bool sa_fwd_attr = false, sa_lsqr_attr = false;      // MaxDynamicSharedMemorySize is per device: set once per engine (an engine is bound to one device, one caller thread)
+    int last_sa_fwd = -1, last_sa_lsqr = -1;       // rows of CE_SA_FWD_VARIANTS / CE_SA_LSQR_VARIANTS the last such launch ran (-1: none yet; ce_get_plan)
     int lsqr_variant = 0;                          // 0: LSQR, 1: LSMR (ce_set_lsqr_variant; the calls that solve EVERY instance iteratively: ce_vjp_shared_a, ce_vjp_lsqr)
     DevBuf<int> d_summary; unsigned summary_next = 0;   // ce_status_summary staging (8 slots of 3 ints)
     DevBuf<double> d_qT;         // batch-major copy of the objective values for the LSQR adjoint kernels (vjp_lsqr_launch)
@@ -178,6 +178,8 @@ struct F2Row { F2Geom g; bool wl, qp; };
 struct RtRow { int CH1, T1, TG, CH2, T2, VP; };
 struct BrtRow { int TI, TJ, TH, BGR; bool psd; };
 struct NsRow { int NTILE, NTHR; };
+struct SaFwdRow { int RP, NTH; bool cidx, tri; };
+struct SaLsqrRow { int RP; bool psd, tri, lsmr, fwd; };
 #define X(V, CHT, T1, CHA, T2, CHG, TG, NTH, WL, QP) {f2_geom<CHT, T1, CHA, T2, CHG, TG, NTH>(), WL != 0, QP != 0},
 static const F2Row F2_ROWS[] = {CE_F2_VARIANTS(X)};
 #undef X
@@ -190,9 +192,16 @@ static const BrtRow BRT_ROWS[] = {CE_BRT_VARIANTS(X)};
 #define X(V, NTILE, NTHR) {NTILE, NTHR},
 static const NsRow NS_ROWS[] = {CE_NS_VARIANTS(X)};
 #undef X
+#define X(V, RP, NTH, CIDX, HTRI) {RP, NTH, CIDX != 0, HTRI != 0},
+static const SaFwdRow SA_FWD_ROWS[] = {CE_SA_FWD_VARIANTS(X)};
+#undef X
+#define X(V, RP, HPSD, HTRI, LSMR, FWD) {RP, HPSD != 0, HTRI != 0, LSMR != 0, FWD != 0},
+static const SaLsqrRow SA_LSQR_ROWS[] = {CE_SA_LSQR_VARIANTS(X)};
+#undef X
 template <int N> constexpr bool rows_in_order(const int (&v)[N]) { for (int i = 0; i < N; i++) if (v[i] != i) return false; return true; }
 #define X(V, ...) V,
-static_assert(rows_in_order({CE_F2_VARIANTS(X)}) && rows_in_order({CE_RT_VARIANTS(X)}) && rows_in_order({CE_BRT_VARIANTS(X)}) && rows_in_order({CE_NS_VARIANTS(X)}),
+static_assert(rows_in_order({CE_F2_VARIANTS(X)}) && rows_in_order({CE_RT_VARIANTS(X)}) && rows_in_order({CE_BRT_VARIANTS(X)}) && rows_in_order({CE_NS_VARIANTS(X)}) &&
+              rows_in_order({CE_SA_FWD_VARIANTS(X)}) && rows_in_order({CE_SA_LSQR_VARIANTS(X)}),
               "ce_variants.h: a row's index is its position in its list");
 #undef X
 
@@ -638,6 +647,37 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
                            const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr, const SaJvp *fwd = nullptr);
+// The re-solve list of ce_vjp_qp and ce_jvp.  The elimination kernel of a call appends the instances whose system it found rank deficient (or too large for its
+// tile) to a device-side list; a fixed grid of LSQR workgroups behind it walks the list and overwrites those instances' results with diffcp's minimum-norm answer
+// (k_sa_lsqr with the instance's own A).  No host round trip; an empty list costs one launch of workgroups that return at once.
+// TWO lists (count | entries) in d_fix, used alternately: the LSQR launch of a call empties the list of the call before -- no memset per call.
+struct FixLists { int *cur, *oth; };
+static bool resolve_fits(const ce_engine *h) {      // the LSQR vectors of one instance (CSR / CSC products: per-instance values) fit LDS
+    const DevT &T = h->T;
+    return sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, h->psd_first, T.nep + T.np) * 8 <= LDS_LIMIT;
+}
+// part one, in front of the elimination launch: the list this call appends to and the other one; d_fix grows and is zeroed on first use for a batch size
+static int resolve_lists(ce_handle h, int B, hipStream_t st, FixLists *L) {
+    if (h->fix_cap < B) {
+        HIPCHK(h->d_fix.reserve(2 * ((size_t)B + 1))); h->fix_cap = B; h->fix_par = 0;
+        HIPCHK(hipMemsetAsync(h->d_fix.get(), 0, sizeof(int) * 2 * ((size_t)B + 1), st));
+    }
+    L->cur = h->d_fix.get() + (size_t)h->fix_par * (h->fix_cap + 1); L->oth = h->d_fix.get() + (size_t)(1 - h->fix_par) * (h->fix_cap + 1);
+    return CE_OK;
+}
+// part two, behind it: lsqr(grid, sel, status_or, sel_reset) launches the LSQR kernel over the current list; the served instances get 4 | 8 ("rank deficient,
+// re-solved by LSQR") OR-ed into their status.  The caller's ProfScope brackets the launch already: the engine's profiling is off for its duration.
+extern "C++" {
+template <class F>
+static int resolve_run(ce_handle h, int B, const FixLists &L, F &&lsqr) {
+    const int grid = B < 768 ? B : 768;          // three workgroups per CU: what the LSQR kernel's LDS allows
+    const int prof_keep = h->prof; h->prof = 0;
+    const int rc = lsqr(grid, L.cur, 4 | 8, L.oth);
+    h->fix_par ^= 1;
+    h->prof = prof_keep;
+    return rc;
+}
+}  // extern "C++"
 int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *P_vals,
               const double *x, const double *y, const double *s, const double *dx, const double *dy,
               double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, double *dP_vals, int *adj_status, void *stream) {
@@ -664,21 +704,14 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         gK = h->gws.get(); gA = h->gws.get() + (size_t)B * perK;
     }
     // Rank-deficient adjoint systems (redundant equality rows, degenerate active sets): the elimination kernels set the free variables to zero -- a BASIC
-    // solution -- where the reference's LSQR (diffcp_if.py:86 -> adj_batch) returns the minimum-norm one.  The kernels append such instances (and the ones whose
-    // system exceeds the register tile) to a device-side list; a fixed grid of LSQR workgroups behind them walks the list and overwrites those instances'
-    // gradients with diffcp's answer (k_sa_lsqr with the instance's own A, full (n + m + 1) system, diffcp's stopping rule).  No host round trip; an empty list
-    // costs one launch of workgroups that return at once.
-    bool do_fix = h->resolve && h->call_q && !P_vals &&
-                  sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, h->psd_first, T.nep + T.np) * 8 <= LDS_LIMIT;
-    if (do_fix && h->fix_cap < B) {
-        HIPCHK(h->d_fix.reserve(2 * ((size_t)B + 1))); h->fix_cap = B; h->fix_par = 0;
-        HIPCHK(hipMemsetAsync(h->d_fix.get(), 0, sizeof(int) * 2 * ((size_t)B + 1), st));      // TWO lists (count | entries), used alternately: the LSQR launch of a call empties the list of the call before
-    }
+    // solution -- where the reference's LSQR (diffcp_if.py:86 -> adj_batch) returns the minimum-norm one: those instances go through the re-solve list above.
+    const bool do_fix = h->resolve && h->call_q && !P_vals && resolve_fits(h);
+    FixLists fix{nullptr, nullptr};
+    if (do_fix) { rc = resolve_lists(h, B, st, &fix); if (rc) return rc; }
     {
         ProfScope ps(h, 1, st);
         CeBwdArgs ba{};
-        int *const fix_cur = do_fix ? h->d_fix.get() + (size_t)h->fix_par * (h->fix_cap + 1) : nullptr, *const fix_oth = do_fix ? h->d_fix.get() + (size_t)(1 - h->fix_par) * (h->fix_cap + 1) : nullptr;
-        ba.fix = fix_cur;
+        ba.fix = fix.cur;
         ba.T = T; ba.nkcap = P.nkcap; ba.ldk = P.ldk; ba.Abm = Abm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dAbm; ba.dq = dq_vals;
         ba.sdqk = sdq_k; ba.sdqb = sdq_b; ba.adj = adj_status; ba.P = P_vals; ba.nnz_p = h->nnz_p; ba.pmap = h->d_pmap.get(); ba.prow = h->d_prow.get(); ba.pcol = h->d_pcol.get();
         ba.p_tri = h->p_tri; ba.dP = dP_vals; ba.gA = gA; ba.gK = gK;
@@ -718,12 +751,10 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         } else lrc = ce_launch_bwd_generic(P.bwd_mode, B, P.bwd_lds, st, ba);
         if (lrc) { g_err = "internal: no backward kernel for the planned variant"; return CE_E_BADARG; }
         if (do_fix) {
-            const int grid = B < 768 ? B : 768;          // three workgroups per CU: what the LSQR kernel's LDS allows; an empty list costs one pass of workgroups that return at once
-            const int prof_keep = h->prof; h->prof = 0;          // (inside this scope's bracket already)
-            rc = vjp_lsqr_launch(h, grid, Abm, K, 1, h->call_q, h->call_sqk, h->call_sqb, x, y, s, dx, dy, dAbm, dq_vals, sdq_k, sdq_b, adj_status, nullptr,
-                                 h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, fix_cur, 4 | 8, fix_oth);
-            h->fix_par ^= 1;
-            h->prof = prof_keep;
+            rc = resolve_run(h, B, fix, [&](int grid, const int *sel, int status_or, int *sel_reset) {
+                return vjp_lsqr_launch(h, grid, Abm, K, 1, h->call_q, h->call_sqk, h->call_sqb, x, y, s, dx, dy, dAbm, dq_vals, sdq_k, sdq_b, adj_status, nullptr,
+                                       h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, sel, status_or, sel_reset);
+            });
             if (rc) return rc;
         }
         if (ba.nk_max) {      // the largest system of this call, for the tile choice of the next one (read once the copy has landed: no synchronisation here)
@@ -920,6 +951,68 @@ int ce_ca_psd_mfma(ce_handle h, int B, int lp, double *U, double *Vstate, int wa
     HIPCHK(hipGetLastError());
     return CE_OK;
 }
+// Shared-A kernels: the row of the family's list (ce_variants.h) that serves a call and the LDS of its launch, from the template's sizes and the switches, which
+// are read HERE, at every call.  No HIP call.  lds == 0: the vectors of one instance do not fit LDS.
+struct SaFwdSel { int row = -1; size_t lds = 0; int aa_w_lds = 0; };
+struct SaLsqrSel { int row = -1; size_t lds = 0; int RP = 0, a_lds = 0; };
+static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static SaFwdSel sa_fwd_select(const DevT &T, int r, int RP, bool aa) {
+    SaFwdSel out;
+    const bool tri = T.nep + T.np > 0;
+    // 512 threads per instance when the iterates of one instance leave room for a single workgroup per CU anyway (CE_SA_NT=256 / 512 forces);
+    // that instantiation also keeps the template's index arrays in LDS when they fit (CE_SA_CIDX=0 disables)
+    int nth = 256;
+    if (T.ns == 0 && sa_fwd_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, 256, T.nep + T.np) * 8 > LDS_LIMIT / 2) nth = 512;
+    { const int v = env_int("CE_SA_NT", 0); if (v == 256 || (v == 512 && T.ns == 0)) nth = v; }
+    size_t lds = sa_fwd_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, nth, T.nep + T.np) * 8;
+    if (lds > LDS_LIMIT) return out;
+    bool cidx = false;
+    if (nth == 512) {
+        const size_t with = lds + sa_fwd_cidx_doubles(T.n, T.m, T.nq, r, T.m) * 8;      // (at most m single-entry rows)
+        if (with <= LDS_LIMIT && env_int("CE_SA_CIDX", 1) != 0) { cidx = true; lds = with; }
+    }
+    if (aa) {
+        // the input of the last iteration in LDS when that does not cost a workgroup per CU (config 4: 68.7 + 3.5 KB, still two per CU)
+        const size_t l = (size_t)T.n + T.m + 1, lp = l + (l & 1), per_cu = nth == 256 ? LDS_LIMIT / 2 : LDS_LIMIT;
+        if (lds + lp * 8 <= per_cu || (lds > LDS_LIMIT / 2 && lds + lp * 8 <= LDS_LIMIT)) { out.aa_w_lds = 1; lds += lp * 8; }
+    }
+    // (the rows without CIDX carry the triples' code whatever the template)
+    for (int v = 0; v < (int)(sizeof(SA_FWD_ROWS) / sizeof(SA_FWD_ROWS[0])); v++) {
+        const SaFwdRow &R = SA_FWD_ROWS[v];
+        if (R.RP == RP && R.NTH == nth && R.cidx == cidx && R.tri == (tri || !cidx)) { out.row = v; break; }
+    }
+    out.lds = lds;
+    return out;
+}
+// per_inst: every instance has its own A values;  listed: the launch walks a re-solve list;  fwd: the forward derivative
+static SaLsqrSel sa_lsqr_select(const ce_engine *h, bool per_inst, bool listed, bool fwd) {
+    SaLsqrSel out;
+    const DevT &T = h->T;
+    const bool tri = T.nep + T.np > 0, psd = T.ns > 0;
+    // products through the singleton / dense-row split when the template has one (CE_SA_SPLIT=0: CSR / CSC products)
+    int RP = env_int("CE_SA_SPLIT", 1) == 0 ? 0 : h->sp_RP;
+    if (per_inst) RP = 0;      // the split's dense rows are ONE matrix (instance 0's values); per-instance values go through the CSR / CSC products
+    const bool lsmr = h->lsqr_variant == 1 && !listed && !fwd;      // (the re-solve list of ce_vjp stays diffcp's default, LSQR)
+    if (RP > 0 && sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8 > LDS_LIMIT) RP = 0;
+    size_t lds = sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8;
+    if (lds > LDS_LIMIT) return out;
+    // per-instance A: staged dense in LDS when it fits behind the vectors with three workgroups per CU to spare (CE_LSQR_A_LDS=0 disables)
+    if (per_inst && RP == 0) {
+        const size_t with = lds + 8 + sizeof(double) * (size_t)T.m * T.n;
+        if (env_int("CE_LSQR_A_LDS", 1) != 0 && with <= LDS_LIMIT / 3) { out.a_lds = 1; lds = with; }
+    }
+    { const size_t want = (size_t)env_int("CE_SA_LSQR_PADLDS", 0) * 1024; if (want > lds && want <= LDS_LIMIT) lds = want; }      // (residency experiment: workgroups per CU)
+    // the leanest row that has the code the template's cones need: plain cones / PSD without triples run instantiations without the other cones' code
+    // (CE_SA_LSQR_SPEC=0: the adjoint runs the general kernel)
+    const bool spec = fwd || env_int("CE_SA_LSQR_SPEC", 1) != 0;
+    for (int v = 0; v < (int)(sizeof(SA_LSQR_ROWS) / sizeof(SA_LSQR_ROWS[0])); v++) {
+        const SaLsqrRow &R = SA_LSQR_ROWS[v];
+        if (R.RP != RP || R.lsmr != lsmr || R.fwd != fwd || (psd && !R.psd) || (tri && !R.tri) || (!spec && !(R.psd && R.tri))) continue;
+        if (out.row < 0 || R.psd + R.tri < SA_LSQR_ROWS[out.row].psd + SA_LSQR_ROWS[out.row].tri) out.row = v;
+    }
+    out.lds = lds; out.RP = RP;
+    return out;
+}
 int ce_solve_shared_a(ce_handle h, int B, int r, int RP, const double *AdT, const int *drow, const int *srow_col, const double *srow_val,
                       const int *scol_ptr, const int *scol_row, const double *gs, const double *Dv, const double *Ev, const double *b_hat,
                       const double *c_hat, const double *sigma, const double *nrm_b0, const double *nrm_c0, const ce_settings *settings,
@@ -929,50 +1022,27 @@ int ce_solve_shared_a(ce_handle h, int B, int r, int RP, const double *AdT, cons
         !settings || !x || !y || !s || !iters || !status) { g_err = "null argument"; return CE_E_BADARG; }
     const DevT &T = h->T;
     if (r < 0 || r > RP || (RP != 16 && RP != 32 && RP != 64)) { g_err = "shared-A forward kernel: at most 64 dense rows (RP in 16, 32, 64)"; return CE_E_UNSUPPORTED; }
-    // 512 threads per instance when the iterates of one instance leave room for a single workgroup per CU anyway (CE_SA_NT=256 / 512 forces);
-    // that instantiation also keeps the template's index arrays in LDS when they fit (CE_SA_CIDX=0 disables)
-    int nth = 256;
-    if (T.ns == 0 && sa_fwd_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, 256, T.nep + T.np) * 8 > LDS_LIMIT / 2) nth = 512;
-    if (const char *e = getenv("CE_SA_NT")) { const int v = atoi(e); if (v == 256 || (v == 512 && T.ns == 0)) nth = v; }
-    size_t lds = sa_fwd_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, nth, T.nep + T.np) * 8;
-    if (lds > LDS_LIMIT) { g_err = "shared-A forward kernel: the iterates of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
-    bool cidx = false;
-    if (nth == 512) {
-        const size_t with = lds + sa_fwd_cidx_doubles(T.n, T.m, T.nq, r, T.m) * 8;      // (at most m single-entry rows)
-        const char *e = getenv("CE_SA_CIDX");
-        if (with <= LDS_LIMIT && !(e && atoi(e) == 0)) { cidx = true; lds = with; }
-    }
+    const SaFwdSel sel = sa_fwd_select(T, r, RP, settings->acceleration_lookback > 0);
+    if (sel.lds == 0) { g_err = "shared-A forward kernel: the iterates of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
     HIPCHK(hipSetDevice(h->device));
-    if (!h->sa_fwd_attr) {
-#define SA_ATTR(...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sa_fwd<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT))
-        SA_ATTR(16, 256); SA_ATTR(32, 256); SA_ATTR(64, 256); SA_ATTR(16, 512); SA_ATTR(32, 512); SA_ATTR(64, 512); SA_ATTR(16, 512, true); SA_ATTR(32, 512, true); SA_ATTR(64, 512, true);
-        SA_ATTR(16, 512, true, false); SA_ATTR(32, 512, true, false); SA_ATTR(64, 512, true, false);
-#undef SA_ATTR
-        h->sa_fwd_attr = true;
-    }
+    if (!h->sa_fwd_attr) { HIPCHK(ce_setattr_sa_fwd((int)LDS_LIMIT)); h->sa_fwd_attr = true; }
     if (!h->d_psd_stats.get() && T.ns > 0) {
         const char *e = getenv("CE_PSD_STATS");
         if (e && atoi(e) != 0) { HIPCHK(h->d_psd_stats.reserve(16)); HIPCHK(hipMemset(h->d_psd_stats.get(), 0, 16 * sizeof(unsigned long long))); }
     }
     int psd_refine = 1; if (const char *e = getenv("CE_PSD_REFINE")) psd_refine = atoi(e) != 0;
-    double *aa_ws = nullptr; int aa_w_lds = 0;
+    double *aa_ws = nullptr;
     if (settings->acceleration_lookback > 0) {
         const size_t l = (size_t)T.n + T.m + 1, lp = l + (l & 1);
         HIPCHK(h->d_aa_ws.reserve((size_t)B * 4 * lp));
         aa_ws = h->d_aa_ws.get();
-        // the input of the last iteration in LDS when that does not cost a workgroup per CU (config 4: 68.7 + 3.5 KB, still two per CU)
-        const size_t per_cu = nth == 256 ? LDS_LIMIT / 2 : LDS_LIMIT;
-        if (lds + lp * 8 <= per_cu || (lds > LDS_LIMIT / 2 && lds + lp * 8 <= LDS_LIMIT)) { aa_w_lds = 1; lds += lp * 8; }
     }
-    SaFwd F{r, RP, AdT, drow, srow_col, srow_val, scol_ptr, scol_row, gs, Dv, Ev, h->d_psd_stats.get(), aa_ws, aa_w_lds, psd_refine};
+    const CeSaFwdArgs fa{T, SaFwd{r, RP, AdT, drow, srow_col, srow_val, scol_ptr, scol_row, gs, Dv, Ev, h->d_psd_stats.get(), aa_ws, sel.aa_w_lds, psd_refine}, *settings,
+                         b_hat, c_hat, sigma, nrm_b0, nrm_c0, warm_x, warm_y, warm_s, x, y, s, iters, status, resid};
     {
         ProfScope ps(h, 0, (hipStream_t)stream);
-#define LAUNCH_SA(NTV, ...) hipLaunchKernelGGL((k_sa_fwd<__VA_ARGS__>), dim3(B), dim3(NTV), lds, (hipStream_t)stream, T, F, *settings, b_hat, c_hat, sigma, nrm_b0, nrm_c0, warm_x, warm_y, warm_s, x, y, s, iters, status, resid)
-        if (nth == 256) { if (RP == 16) LAUNCH_SA(256, 16, 256); else if (RP == 32) LAUNCH_SA(256, 32, 256); else LAUNCH_SA(256, 64, 256); }
-        else if (!cidx) { if (RP == 16) LAUNCH_SA(512, 16, 512); else if (RP == 32) LAUNCH_SA(512, 32, 512); else LAUNCH_SA(512, 64, 512); }
-        else if (T.nep + T.np == 0) { if (RP == 16) LAUNCH_SA(512, 16, 512, true, false); else if (RP == 32) LAUNCH_SA(512, 32, 512, true, false); else LAUNCH_SA(512, 64, 512, true, false); }
-        else { if (RP == 16) LAUNCH_SA(512, 16, 512, true); else if (RP == 32) LAUNCH_SA(512, 32, 512, true); else LAUNCH_SA(512, 64, 512, true); }
-#undef LAUNCH_SA
+        if (ce_launch_sa_fwd(sel.row, B, sel.lds, (hipStream_t)stream, fa)) { g_err = "internal: no shared-A forward kernel for the selected variant"; return CE_E_BADARG; }
+        h->last_sa_fwd = sel.row;
     }
     HIPCHK(hipGetLastError());
     return CE_OK;
@@ -985,32 +1055,11 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
     if (!h || B <= 0 || !A_vals0 || !x || !y || !s) { g_err = "null argument"; return CE_E_BADARG; }
     if (fwd ? (!fwd->dx || !fwd->dy) : (!dx || !dy || !dA_bm || !dq_vals)) { g_err = "null argument"; return CE_E_BADARG; }
     const DevT &T = h->T;
-    // products through the singleton / dense-row split when the template has one (CE_SA_SPLIT=0: CSR / CSC products)
-    int RP = h->sp_RP;
-    if (const char *e = getenv("CE_SA_SPLIT")) { if (atoi(e) == 0) RP = 0; }
-    if (per_inst) RP = 0;      // the split's dense rows are ONE matrix (instance 0's values); per-instance values go through the CSR / CSC products
-    const int lsmr = (h->lsqr_variant == 1 && !sel && !fwd) ? 1 : 0;      // (the re-solve list of ce_vjp stays diffcp's default, LSQR)
-    if (RP > 0 && sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8 > LDS_LIMIT) RP = 0;
-    size_t lds = sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, RP, h->psd_first, T.nep + T.np, lsmr) * 8;
-    if (lds > LDS_LIMIT) { g_err = fwd ? "forward-derivative kernel: the LSQR vectors of one instance do not fit LDS" : "shared-A adjoint kernel: the LSQR vectors of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
-    // per-instance A: staged dense in LDS when it fits behind the vectors with three workgroups per CU to spare (CE_LSQR_A_LDS=0 disables)
-    int a_lds = 0;
-    if (per_inst && RP == 0) {
-        const char *e = getenv("CE_LSQR_A_LDS");
-        const size_t with = lds + 8 + sizeof(double) * (size_t)T.m * T.n;
-        if (!(e && atoi(e) == 0) && with <= LDS_LIMIT / 3) { a_lds = 1; lds = with; }
-    }
+    const SaLsqrSel sl = sa_lsqr_select(h, per_inst != 0, sel != nullptr, fwd != nullptr);
+    if (sl.lds == 0) { g_err = fwd ? "forward-derivative kernel: the LSQR vectors of one instance do not fit LDS" : "shared-A adjoint kernel: the LSQR vectors of one instance do not fit LDS"; return CE_E_TOO_LARGE; }
+    const int RP = sl.RP;
     HIPCHK(hipSetDevice(h->device));
-    if (!h->sa_lsqr_attr) {
-#define SA_ATTR(...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sa_lsqr<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT))
-        SA_ATTR(0); SA_ATTR(16); SA_ATTR(32); SA_ATTR(64); SA_ATTR(0, false, false); SA_ATTR(16, false, false); SA_ATTR(32, false, false); SA_ATTR(64, false, false);
-        SA_ATTR(16, true, false); SA_ATTR(32, true, false); SA_ATTR(64, true, false);
-        SA_ATTR(0, true, true, true); SA_ATTR(16, true, true, true); SA_ATTR(32, true, true, true); SA_ATTR(64, true, true, true);
-        SA_ATTR(0, false, false, false, true); SA_ATTR(16, false, false, false, true); SA_ATTR(32, false, false, false, true); SA_ATTR(64, false, false, false, true);
-        SA_ATTR(0, true, true, false, true); SA_ATTR(16, true, true, false, true); SA_ATTR(32, true, true, false, true); SA_ATTR(64, true, true, false, true);
-#undef SA_ATTR
-        h->sa_lsqr_attr = true;
-    }
+    if (!h->sa_lsqr_attr) { HIPCHK(ce_setattr_sa_lsqr((int)LDS_LIMIT)); h->sa_lsqr_attr = true; }
     // The streaming passes read c_j of their instance with every row of the matrix.  In the boundary's layout (q_eval (n + 1, B): consecutive j are B doubles apart) each of
     // those loads is a line of its own, and the lines of all resident instances (config 5: 768 x 501 x 128 B) live in the memory-side cache, not in L2: the pass waited for
     // THEM, not for the matrix.  One transpose per call gives every instance a contiguous c (4 KB, L2-resident for the whole solve).  Not for the re-solve list
@@ -1020,57 +1069,22 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
         launch_transpose((hipStream_t)stream, q_vals, h->d_qT.get(), T.n + 1, B);
         q_vals = h->d_qT.get(); sq_k = 1; sq_b = T.n + 1;
     }
-    SaStruct S{h->d_csc_ptr.get(), h->d_rowidx.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), T.nnzA, h->d_bpos.get()};
-    SaSplit F{h->sp_r, RP, h->d_sp_AdT.get(), h->d_sp_drow.get(), h->d_sp_srow_col.get(), h->d_sp_sval.get(), h->d_sp_scol_ptr.get(), h->d_sp_scol_row.get(),
-              h->d_sp_rowslot.get(), h->d_sp_sing_i.get(), h->d_sp_sing_v.get()};
+    const CeSaLsqrArgs la{T, SaStruct{h->d_csc_ptr.get(), h->d_rowidx.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), T.nnzA, h->d_bpos.get()},
+                          SaSplit{h->sp_r, RP, h->d_sp_AdT.get(), h->d_sp_drow.get(), h->d_sp_srow_col.get(), h->d_sp_sval.get(), h->d_sp_scol_ptr.get(), h->d_sp_scol_row.get(),
+                                  h->d_sp_rowslot.get(), h->d_sp_sing_i.get(), h->d_sp_sing_v.get()},
+                          A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters,
+                          atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, sl.a_lds, sel_reset, fwd ? *fwd : SaJvp{}};
     if (RP > 0) {      // the values may differ between calls: refill A_d^T / singleton values from this call's A (n RP + m doubles)
         HIPCHK(hipMemsetAsync(h->d_sp_AdT.get(), 0, sizeof(double) * (size_t)T.n * RP, (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(h->d_sp_sval.get(), 0, sizeof(double) * T.m, (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(h->d_sp_sing_v.get(), 0, sizeof(double) * T.n, (hipStream_t)stream));
-        if (T.nnzA > 0) hipLaunchKernelGGL(k_sa_fill_split, dim3((T.nnzA + 255) / 256), dim3(256), 0, (hipStream_t)stream, T.nnzA, RP, h->d_rowidx.get(), h->d_colidx.get(),
-                                           h->d_sp_rowslot.get(), A_vals0, h->d_sp_AdT.get(), h->d_sp_sval.get(), h->d_sp_sing_i.get(), h->d_sp_sing_v.get());
+        if (T.nnzA > 0) ce_launch_sa_fill_split((hipStream_t)stream, T.nnzA, RP, h->d_rowidx.get(), h->d_colidx.get(), h->d_sp_rowslot.get(), A_vals0,
+                                                h->d_sp_AdT.get(), h->d_sp_sval.get(), h->d_sp_sing_i.get(), h->d_sp_sing_v.get());
     }
-    // Several instances per workgroup share the stream over A_d^T (ce_shared_a_mi.h) where the template allows it: plain cones, the split's products, the solution
-    // in the owners' registers, no re-solve list, and enough instances to fill the device either way.  CE_SA_LSQR_NI=1 keeps one instance per workgroup (A/B), 2 / 3 force.
-    int ni = 0;
-    if (RP > 0 && !per_inst && !sel && !lsmr && !fwd && T.ns == 0 && T.nep + T.np == 0 && T.n <= SAMI_EL * 256 && T.m <= SAMI_EL * 256) {
-        ni = 0;      // (measured slower than one instance per workgroup at config 5: profiles/r06/n_*; opt-in)
-        if (const char *e = getenv("CE_SA_LSQR_NI")) { const int v = atoi(e); ni = (v == 2 || v == 3) ? v : 0; }
-        while (ni >= 2 && sa_lsqr_mi_lds_doubles(T.n, T.m, T.nq, RP, ni) * 8 > LDS_LIMIT) ni--;
-        if (ni < 2) ni = 0;
-    }
-    if (ni) {
-        if (!h->sa_lsqr_mi_attr) {
-#define SA_ATTR(RPV, NIV) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sa_lsqr_mi<RPV, NIV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT))
-            SA_ATTR(16, 2); SA_ATTR(32, 2); SA_ATTR(64, 2); SA_ATTR(16, 3); SA_ATTR(32, 3); SA_ATTR(64, 3);
-#undef SA_ATTR
-            h->sa_lsqr_mi_attr = true;
-        }
-        const size_t lds_mi = sa_lsqr_mi_lds_doubles(T.n, T.m, T.nq, RP, ni) * 8;
-        ProfScope ps(h, 1, (hipStream_t)stream);
-#define LAUNCH_MI(RPV, NIV) hipLaunchKernelGGL((k_sa_lsqr_mi<RPV, NIV>), dim3((B + NIV - 1) / NIV), dim3(NIV * 256), lds_mi, (hipStream_t)stream, T, S, F, A_vals0, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters, atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), B)
-        if (ni == 2) { if (RP == 16) LAUNCH_MI(16, 2); else if (RP == 32) LAUNCH_MI(32, 2); else LAUNCH_MI(64, 2); }
-        else { if (RP == 16) LAUNCH_MI(16, 3); else if (RP == 32) LAUNCH_MI(32, 3); else LAUNCH_MI(64, 3); }
-#undef LAUNCH_MI
-        HIPCHK(hipGetLastError());
-        return CE_OK;
-    }
-    if (const char *e = getenv("CE_SA_LSQR_PADLDS")) { const size_t want = (size_t)atoi(e) * 1024; if (want > lds && want <= LDS_LIMIT) lds = want; }      // (residency experiment: workgroups per CU)
     {
         ProfScope ps(h, 1, (hipStream_t)stream);
-#define LAUNCH_SAL(...) hipLaunchKernelGGL((k_sa_lsqr<__VA_ARGS__>), dim3(B), dim3(NT), lds, (hipStream_t)stream, T, S, F, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters, atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, a_lds, sel_reset, fwd ? *fwd : SaJvp{})
-        // plain cones / PSD without triples: instantiations without the other cones' code (CE_SA_LSQR_SPEC=0: the general kernel)
-        const bool tri = T.nep + T.np > 0, psd = T.ns > 0;
-        int spec = 1; if (const char *e = getenv("CE_SA_LSQR_SPEC")) spec = atoi(e);
-        if (fwd) {      // plain cones, or the general kernel (PSD blocks and triples)
-            if (!tri && !psd) { if (RP == 0) LAUNCH_SAL(0, false, false, false, true); else if (RP == 16) LAUNCH_SAL(16, false, false, false, true); else if (RP == 32) LAUNCH_SAL(32, false, false, false, true); else LAUNCH_SAL(64, false, false, false, true); }
-            else if (RP == 0) LAUNCH_SAL(0, true, true, false, true); else if (RP == 16) LAUNCH_SAL(16, true, true, false, true); else if (RP == 32) LAUNCH_SAL(32, true, true, false, true); else LAUNCH_SAL(64, true, true, false, true);
-        }
-        else if (lsmr) { if (RP == 0) LAUNCH_SAL(0, true, true, true); else if (RP == 16) LAUNCH_SAL(16, true, true, true); else if (RP == 32) LAUNCH_SAL(32, true, true, true); else LAUNCH_SAL(64, true, true, true); }
-        else if (spec && !tri && !psd) { if (RP == 0) LAUNCH_SAL(0, false, false); else if (RP == 16) LAUNCH_SAL(16, false, false); else if (RP == 32) LAUNCH_SAL(32, false, false); else LAUNCH_SAL(64, false, false); }
-        else if (spec && !tri && RP > 0) { if (RP == 16) LAUNCH_SAL(16, true, false); else if (RP == 32) LAUNCH_SAL(32, true, false); else LAUNCH_SAL(64, true, false); }
-        else if (RP == 0) LAUNCH_SAL(0); else if (RP == 16) LAUNCH_SAL(16); else if (RP == 32) LAUNCH_SAL(32); else LAUNCH_SAL(64);
-#undef LAUNCH_SAL
+        if (ce_launch_sa_lsqr(sl.row, B, sl.lds, (hipStream_t)stream, la)) { g_err = "internal: no LSQR kernel for the selected variant"; return CE_E_BADARG; }
+        h->last_sa_lsqr = sl.row;
     }
     HIPCHK(hipGetLastError());
     return CE_OK;
@@ -1112,31 +1126,27 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
            const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
            double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
     // the forward derivative as ce_vjp_qp runs the adjoint: the search-free elimination (k_backward_ns<..., FWD>), then the fixed grid of LSQR workgroups that
-    // re-solves the instances it listed as rank deficient -- the same two alternating lists, no memset, no host round trip
+    // re-solves the instances it listed as rank deficient -- the same re-solve list
     if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
     if (P.ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
-    if (sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, h->psd_first, T.nep + T.np) * 8 > LDS_LIMIT) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
     if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = "ce_jvp: A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    if (h->fix_cap < B) {
-        HIPCHK(h->d_fix.reserve(2 * ((size_t)B + 1))); h->fix_cap = B; h->fix_par = 0;
-        HIPCHK(hipMemsetAsync(h->d_fix.get(), 0, sizeof(int) * 2 * ((size_t)B + 1), st));
-    }
-    int *const fix_cur = h->d_fix.get() + (size_t)h->fix_par * (h->fix_cap + 1), *const fix_oth = h->d_fix.get() + (size_t)(1 - h->fix_par) * (h->fix_cap + 1);
+    FixLists fix;
+    int rc = resolve_lists(h, B, st, &fix); if (rc) return rc;
     ProfScope ps(h, 1, st);
     CeBwdArgs ba{};
-    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix_cur;
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
     if (ce_launch_fwd_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
-    const int prof_keep = h->prof; h->prof = 0;          // (inside this scope's bracket already)
-    const int rc = jvp_lsqr_launch(h, B < 768 ? B : 768, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
-                                   atol, btol, conlim, iter_lim, stream, fix_cur, 4 | 8, fix_oth);
-    h->fix_par ^= 1;
-    h->prof = prof_keep;
+    rc = resolve_run(h, B, fix, [&](int grid, const int *sel, int status_or, int *sel_reset) {
+        return jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
+                               atol, btol, conlim, iter_lim, stream, sel, status_or, sel_reset);
+    });
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return CE_OK;
@@ -1264,7 +1274,7 @@ int ce_get_plan(ce_handle h, int *out, int n_out) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     const CePlan &P = h->plan;
     const int v[] = {P.fwd_mode, P.f2_variant, P.rt_variant, P.wl ? 1 : 0, P.aa_ok ? 1 : 0, h->T.gen_blocked_f, P.qp_native ? 1 : 0,
-                     P.bwd_mode, P.brt_variant, P.two_tile ? 1 : 0, P.ns_variant, h->T.gen_blocked_b, h->sp_r, h->sp_RP, h->last_fast};
+                     P.bwd_mode, P.brt_variant, P.two_tile ? 1 : 0, P.ns_variant, h->T.gen_blocked_b, h->sp_r, h->sp_RP, h->last_fast, h->last_sa_fwd, h->last_sa_lsqr};
     const int cnt = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; out && i < cnt && i < n_out; i++) out[i] = v[i];
     return cnt;

@@ -423,12 +423,13 @@ class ConeEngine:
         return dict(self._launch_info)
 
     PLAN_FIELDS = ("fwd_mode", "f2_variant", "rt_variant", "wl", "aa_ok", "gen_blocked_f", "qp_native",
-                   "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_r", "sp_RP", "last_fast")
+                   "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_r", "sp_RP", "last_fast",
+                   "last_sa_fwd", "last_sa_lsqr")
 
     def plan(self):
         """The whole launch plan (include/cone_engine.h ce_get_plan) as a dict keyed by PLAN_FIELDS.  Read from the library on every call, unlike
-        launch_info(): its last entry, last_fast, is the first tile of the most recent two-tile adjoint call and changes from call to call
-        (tests/test_gpu_plan_edges.py reads it between calls).  Nothing on the solve / vjp path calls this."""
+        launch_info(): the last_* entries change from call to call -- last_fast is the first tile of the most recent two-tile adjoint call, last_sa_fwd /
+        last_sa_lsqr the rows of csrc/ce_variants.h the most recent shared-A forward / LSQR launch ran (tests/test_gpu_plan_edges.py reads them between calls).  Nothing on the solve / vjp path calls this."""
         L = _lib.lib()
         cnt = L.ce_get_plan(self._h, None, 0)
         _lib.check(min(cnt, 0), "ce_get_plan")

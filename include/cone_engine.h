@@ -91,8 +91,8 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 15
+ * layout, an entry point's signature or the meaning of an argument changes (16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+#define CE_ABI_VERSION 16
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -392,7 +392,10 @@ int ce_get_launch_info(ce_handle h, int *fwd_lds_bytes, int *bwd_lds_bytes, int 
  *   12 sp_r           dense rows (two or more entries) of the A part, when at most 64 (shared-A kernels; else 0)
  *   13 sp_RP          their padding 16 / 32 / 64 (0: more than 64 dense rows, the batch-GEMM path of the constant-A interface)
  *   14 last_fast      first tile of the last ce_vjp call when it ran the two-tile plan (-1: the call ran one tile / none yet)
- * The plan is fixed by ce_create (environment switches included), except last_fast. */
+ *   15 last_sa_fwd    row of CE_SA_FWD_VARIANTS (csrc/ce_variants.h) the last ce_solve_shared_a call launched (-1: none yet)
+ *   16 last_sa_lsqr   row of CE_SA_LSQR_VARIANTS the last k_sa_lsqr launch ran: ce_vjp_shared_a, ce_vjp_lsqr, ce_jvp_shared_a, ce_jvp_lsqr, or the re-solve behind
+ *                     ce_vjp / ce_jvp (-1: none yet)
+ * The plan is fixed by ce_create (environment switches included), except the last_* entries: the shared-A kernels read their switches at the call. */
 int ce_get_plan(ce_handle h, int *out, int n_out);
 
 #ifdef __cplusplus

@@ -8,8 +8,8 @@ from __future__ import annotations
 
 import numpy as np
 
-# fields that tell kernels apart; sp_r (the number of dense rows, which changes with every row of a small dense template) and last_fast (call history) are not
-# plan edges by themselves -- sp_RP is
+# fields that tell kernels apart; sp_r (the number of dense rows, which changes with every row of a small dense template) and last_fast, last_sa_fwd,
+# last_sa_lsqr (call history) are not plan edges by themselves -- sp_RP is
 EDGE_FIELDS = ("fwd_mode", "f2_variant", "rt_variant", "wl", "aa_ok", "gen_blocked_f", "qp_native",
                "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_RP")
 
@@ -110,16 +110,22 @@ LEDGER_FAMILIES = {
 # shared-A templates: v dense rows (all n columns) + one bound row per variable (single entries): sp_RP 16 / 32 / 64 / 0
 SHARED_FAMILY = ("shared_dense_rows", range(1, 72))
 SHARED_N = 8
+# the same rows followed by one more cone whose rows have a single entry each (the split's dense rows stay the first v): the cone sets that tell the
+# instantiations of the shared-A kernels apart (csrc/ce_variants.h CE_SA_FWD_VARIANTS, CE_SA_LSQR_VARIANTS).  Not swept: sp_RP depends on v alone.
+SHARED_CONE_SETS = {SHARED_FAMILY[0]: {}, SHARED_FAMILY[0] + "+psd3": {"s": [3]}, SHARED_FAMILY[0] + "+exp": {"ep": 1}}
 
 
 def shape_of(family, v):
     """(n, cones, pattern or None, P structure (indices, indptr) or None)"""
-    if family == SHARED_FAMILY[0]:
+    if family in SHARED_CONE_SETS:
         n = SHARED_N
-        cones = {"z": 0, "l": v + n, "q": []}
-        pat = np.zeros((v + n, n), dtype=bool)
+        extra = SHARED_CONE_SETS[family]
+        ne = sum(k * (k + 1) // 2 for k in extra.get("s", [])) + 3 * extra.get("ep", 0)
+        cones = {"z": 0, "l": v + n, "q": [], **extra}
+        pat = np.zeros((v + n + ne, n), dtype=bool)
         pat[:v] = True
         pat[v + np.arange(n), np.arange(n)] = True
+        pat[v + n + np.arange(ne), np.arange(ne) % n] = True
         return n, cones, pat, None
     out = {**FAMILIES, **LEDGER_FAMILIES}[family][1](v)
     n, cones = out[0], out[1]
@@ -137,6 +143,15 @@ def family_values(family):
 
 def all_families(ledger=False):
     return list(FAMILIES) + [SHARED_FAMILY[0]] + (list(LEDGER_FAMILIES) if ledger else [])
+
+
+def variant_rows(name):
+    """the rows of a variant list of csrc/ce_variants.h (e.g. "CE_SA_LSQR_VARIANTS") as tuples of ints, the row index first"""
+    import os
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cvxpylayers_amd", "csrc", "ce_variants.h")).read()
+    body = re.search(r"#define " + name + r"\(X\)((?:\s*\\\n\s*X\([^)]*\))+)", hdr).group(1)
+    return [tuple(int(t) for t in row.split(",")) for row in re.findall(r"X\(([^)]*)\)", body)]
 
 
 def plan_of(family, v, device=None):
