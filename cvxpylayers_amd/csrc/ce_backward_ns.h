@@ -37,7 +37,17 @@
 // in LDS, b through bpos, c from q_eval, rho before) and another EPILOGUE behind eta (x+ = x + dx, v+ = v + dy - ds, projection, the value row scattered into LDS
 // again, rho after, keep or reject, x, y, s written in place).  No buffer beyond the adjoint's (the block maxima go through `red`).  A flagged instance keeps its point.
 //
-// Plain cones (zero / nonnegative / second-order), linear objective.  PSD / exponential / power cones and quadratic objectives keep k_backward_rt.
+// QP = true (with FWD, REF or not): a quadratic objective 1/2 x^T P x inside the elimination (cone_engine.hip ce_jvp_qp, ce_refine_qp).  The stationarity row gains
+// P:  P d_x + A^T D d_v = -g_x  with  g_x = tP x + tA^T y + tc  (REF: F_x = P x + A^T y^ + c), so the saddle system is  (H + P) d_x + B^T eta_B = f,  B d_x = gamma_B
+// with the f above.  P (dense, symmetric, n x n, behind the index arrays in LDS: bwd_ns_qp_lds_bytes_of) enters in three places, everything else is shared:
+//   - its rows go through the null-space transform of step 2 like weighted rows (p~_j = Z^T p_j in place, t_j = p_j . x_p), and
+//     Z^T P Z = sum_j z_j p~_j^T  (z_j = row j of Z: a unit vector for a free column, -R[e,:] for the pivot column of equality e) is one more run of
+//     v_mfma_f64_16x16x4_f64 accumulations into the tiles of step 3, with  sum_j z_j t_j = Z^T P x_p  in the right-hand-side column;
+//   - g = ((H + P) r_x - f)[piv] for the multipliers: the pivot COLUMNS of P are untouched by the transform and P is symmetric.
+// With no active row at all H = 0 and the reduced Hessian is P alone: regular when P is positive definite, where the linear objective flags the instance.
+// A flagged instance keeps the dropped-variable answer with status 4 (no LSQR has a P term, so no re-solve list exists behind a QP launch).
+//
+// Plain cones (zero / nonnegative / second-order).  PSD / exponential / power cones keep k_backward_rt, and so does the ADJOINT with a quadratic objective.
 #pragma once
 
 // pitch of the sweep's row buffers: 16 mod 32 doubles (conflict-free) with at least 16 doubles of gap behind the 16 NTILE entries of a row (the gaps of the
@@ -58,6 +68,10 @@ __host__ __device__ inline size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int 
     size_t i = 2 * (size_t)m + 3 * (size_t)nqs + 4 * (size_t)n + 2 * (size_t)kw + (size_t)(NTHR / 64) + 1 + 8;
     return d * 8 + i * 4;
 }
+// QP instantiations: behind the footprint above (rounded to 8 bytes) the dense P (pitch n), t_j = p_j . x_p per row of P, and pivot column -> equality
+__host__ __device__ inline size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) {
+    return ((bwd_ns_lds_bytes_of(n, m, nq, NTILE, NTHR) + 7) & ~(size_t)7) + ((size_t)n * n + (size_t)(n + (n & 1))) * 8 + (size_t)n * 4;
+}
 
 #ifdef CE_TIMING
 #define NS_STAMP(i) do { __syncthreads(); if (threadIdx.x == 0) tstamp[i] = __builtin_readcyclecounter(); } while (0)
@@ -77,16 +91,20 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
     return kind;
 }
 
-template <bool FWD, bool REF = false> struct NsFwdArg { typedef NsNoJvp type; };
+template <bool FWD, bool REF = false, bool QP = false> struct NsFwdArg { typedef NsNoJvp type; };
 template <> struct NsFwdArg<true, false> { typedef NsJvp type; };
 template <> struct NsFwdArg<true, true> { typedef NsRefine type; };
+template <> struct NsFwdArg<true, false, true> { typedef NsJvpQp type; };
+template <> struct NsFwdArg<true, true, true> { typedef NsRefineQp type; };
 
-template <int NTILE, int NTHR, bool FWD = false, bool REF = false>
-__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? 3 : 1))
+// (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two)
+template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false>
+__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? (QP ? 2 : 3) : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF>::type W) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
+    static_assert(FWD || !QP, "the adjoint with a quadratic objective lives in k_backward_rt");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -132,6 +150,20 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     int *wsrc = ip; ip += KWMAX;     // weighted row -> row index of A (>= 0) or -1 - cone (a_z)
     int *wcnt = ip; ip += NWB + 1;
     int *misc = ip; ip += 8;         // [0] n_eq, [1] nf, [2] flags, [3] KW
+    double *Pm = nullptr, *ptv = nullptr; int *peq = nullptr;
+    if constexpr (QP) {
+        ip += (ip - (int *)sm) & 1;
+        Pm = (double *)ip;           // P, dense and symmetric (pitch n); step 2 turns its rows into p~_j = Z^T p_j in the free columns
+        ptv = Pm + n * n;            // per row of P: t_j = p_j . x_p
+        peq = (int *)(ptv + npad);   // pivot column j -> its equality e
+    }
+    // QP: the instance's P row through the template's dense entry map (-1: structural zero; a one-triangle entry stands for both matrix entries)
+    auto load_P = [&]() {
+        if constexpr (QP) {
+            const double *Pv = W.Q.P + (size_t)inst * W.Q.nnz_p;
+            for (int i = tid; i < n * n; i += NTHR) { const int k = W.Q.pmap[i]; Pm[i] = k >= 0 ? Pv[k] : 0.0; }
+        }
+    };
 
 #ifdef CE_TIMING
     __shared__ long long tstamp[16], tsub[16];
@@ -172,7 +204,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         }
     };
-    // REF: the KKT residual at (x, y-hat, s-hat) of the instance in A:  F_x = A^T y-hat + c,  F_y = A x + s-hat - b  (b through bpos, c from q_eval); returns
+    // REF: the KKT residual at (x, y-hat, s-hat) of the instance in A:  F_x = [P x +] A^T y-hat + c,  F_y = A x + s-hat - b  (b through bpos, c from q_eval); returns
     // rho = max(|F_x|, |F_y|) / (1 + max(|b|, |c|)), a non-finite entry counting as infinite.  keep: F_x -> fvec, -F_y -> dv (g_x, g_y of the elimination).
     // Four lanes per column / row, fixed summation order; ends behind a barrier.
     auto kkt_residual = [&](const double *xs, const double *yh, const double *vs, bool keep) -> double {
@@ -189,6 +221,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 const double r0v = A[i * lda + j], r1v = A[i2 * lda + j], y0 = yh[i], y1 = yh[i2];
                 a0 = fma(r0v, y0, a0); a1 = fma(r1v, (i + 4 < m) ? y1 : 0.0, a1);
             }
+            if constexpr (QP) { if (j < n) for (int i = part; i < n; i += 4) a0 = fma(Pm[j * n + i], xs[i], a0); }          // (P as loaded: untransformed at both evaluations)
             const double a = group_reduce<4, false>(a0 + a1);
             if (j < n && part == 0) {
                 const double cj = W.q[j * W.sqk + inst * W.sqb], f = a + cj, fa = fabs(f);
@@ -244,6 +277,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         } else
         for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; dv[i] = dyg[(size_t)inst * m + i]; }
         if (tid < 8) misc[tid] = 0;
+        load_P();
         __syncthreads();
 #pragma unroll
         for (int u = 0; u < LU; u++) if (c0[u] >= 0) A[r0[u] * lda + c0[u]] = -v0[u];
@@ -263,7 +297,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         rho0 = kkt_residual(rx, tvec, vv, true);
         if (W.first) rho_cur = rho0;
     } else if constexpr (FWD) {
-        // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
+        // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y [+ dP x] -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
         //      (k_sa_lsqr<FWD>'s prologue: dA = -tA_eval, db = +tA_eval[bpos], dc = tq_eval[:n]).  The instance's tangent row is read through the template's CSC
         //      (the value order itself) and CSR structure, 8 lanes per column / row, four entries in flight per lane; fixed summation order.
         const double *tA = W.tA ? W.tA + (size_t)inst * T.nnz_aug : nullptr;
@@ -280,7 +314,16 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                     for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, tvec[ri[u]], a1); else a0 = fma(t, tvec[ri[u]], a0); }
                 }
             }
-            const double a = group_reduce<8, false>(a0 + a1);
+            double as = a0 + a1;
+            if constexpr (QP) {          // - (tP x)_j: row j of the tangent of P through the dense entry map
+                if (W.Q.tP && j < n) {
+                    const double *tP = W.Q.tP + (size_t)inst * W.Q.nnz_p;
+                    double pa = 0.0;
+                    for (int i = c8; i < n; i += 8) { const int k = W.Q.pmap[j * n + i]; pa = fma(k >= 0 ? tP[k >= 0 ? k : 0] : 0.0, rx[i], pa); }
+                    as -= pa;
+                }
+            }
+            const double a = group_reduce<8, false>(as);
             if (j < n && c8 == 0) fvec[j] = (W.tq ? W.tq[j * W.stqk + inst * W.stqb] : 0.0) - a;
         }
         for (int i0 = 0; i0 < m; i0 += NTHR / 8) {
@@ -407,7 +450,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[(size_t)inst * T.nnz_aug + k] = 0.0;
             for (int j = tid; j <= n; j += NTHR) dqo[j * sdqk + inst * sdqb] = 0.0;
         }
-        if (tid == 0) { if (adj_status) adj_status[inst] = 2; if (fix) fix[1 + atomicAdd(fix, 1)] = inst; }
+        if (tid == 0) { if (adj_status) adj_status[inst] = QP ? 4 : 2; if (fix) fix[1 + atomicAdd(fix, 1)] = inst; }          // (QP: no re-solve behind the launch, the zeros stand, flagged)
         return;
     }
     // ---- f = dx + A^T u  and  a_z = A_z^T z-hat  in ONE pass over the rows of the boundary cones (4 lanes per column, each takes every 4th cone; fixed summation order)
@@ -676,6 +719,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     }
     __syncthreads();
     NS_STAMP(4);
+    if constexpr (QP) { for (int e = tid; e < neq; e += NTHR) { const int pc = pcol[e]; if (pc >= 0) peq[pc] = e; } }          // (read behind the barrier that ends step 2)
     const int nf = misc[1];
     const int NB = (nf + 3) >> 2, cr = 4 * NB;          // blocks of four that hold a reduced variable; column of the right-hand side
     // ---- 2. null-space transform of the weighted rows and of f (list entry KW), in place, on the matrix cores:
@@ -727,6 +771,30 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                             else if (tcol && q < KW) tvec[q] = tacc[g][r];
                         }
                     }
+            }
+        }
+        if constexpr (QP) {
+            // the rows of P through the same transform, sixteen per pass:  p_j[free] <- p_j[free] - sum_e p_j[p_e] R[e][free],  t_j = sum_e p_j[p_e] d~_e -> ptv.
+            // The pivot columns of P are only read here and stay as loaded (the multipliers need them).
+            if (wave < NCT) {
+                const int colj = 16 * wave + lc, cj = colj < n ? colj : 0;
+                const bool wcol = colj < n && cmap[cj] >= 0, tcol = colj == n;
+                for (int g0 = 0; g0 < n; g0 += 16) {
+                    v4d tacc = v4d{0.0, 0.0, 0.0, 0.0};
+                    const int prw = min(g0 + lc, n - 1) * n;
+                    for (int k0 = 0; k0 < neq; k0 += 4) {
+                        const int kq = min(k0 + lg, neq - 1);
+                        const int pc = (k0 + lg < neq) ? pcol[kq] : -1, er = erow[kq];
+                        const double bop = (pc >= 0 && colj <= n) ? (colj < n ? sm[er + colj] : dB[kq]) : 0.0;
+                        const double aop = Pm[prw + (pc >= 0 ? pc : 0)];
+                        tacc = __builtin_amdgcn_mfma_f64_16x16x4f64(pc >= 0 ? aop : 0.0, bop, tacc, 0, 0, 0);
+                    }
+                    static_for<4>([&](auto rc) {
+                        constexpr int r = decltype(rc)::value;
+                        const int q = g0 + lg + 4 * r;
+                        if (q < n) { if (wcol) Pm[q * n + cj] -= tacc[r]; else if (tcol) ptv[q] = tacc[r]; }
+                    });
+                }
             }
         }
     }
@@ -784,6 +852,25 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
 #pragma unroll
                     for (int J = 0; J < NTILE; J++) if (J < jmax) acc[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(aB[u], bB[u][J], acc[J], 0, 0, 0);
                 }
+            }
+        }
+        if constexpr (QP) {
+            // + Z^T P Z = sum_j z_j p~_j^T over the n rows of P, four per instruction: the A operand is z_j at this lane's strip row (1 at the free column j itself,
+            // -R[e][.] for the pivot column of equality e), the B operands are p~_j at the tile's columns and t_j in the right-hand-side column (+ Z^T P x_p there:
+            // the column is negated below).  Formed by value, not by address: one run of n / 4 steps beside the KW / 4 of the loop above.
+            const int frow = 16 * wave + lc;
+            for (int k0 = 0; k0 < n; k0 += 4) {
+                const bool jv = k0 + lg < n;
+                const int j = jv ? k0 + lg : n - 1;
+                const int cm = cmap[j];
+                double za = 0.0;
+                if (jv && kdw == 0) { if (cm >= 0) za = cm == frow ? 1.0 : 0.0; else za = -sm[erow[peq[j]] + ocw]; }
+                const double tj = ptv[j];
+                double bP[NTILE];
+#pragma unroll
+                for (int J = 0; J < NTILE; J++) { const double pv = Pm[j * n + oc[J]]; bP[J] = kd[J] == 0 ? pv : (kd[J] == 1 ? tj : 0.0); }
+#pragma unroll
+                for (int J = 0; J < NTILE; J++) if (J < jmax) acc[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(za, bP[J], acc[J], 0, 0, 0);
             }
         }
         NS_SUB(1);
@@ -947,12 +1034,13 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     }
     for (int e = tid; e < neq; e += NTHR) { const int pc = pcol[e]; if (pc >= 0) rx[pc] = dB[e]; }      // r_x[p_e] = x_piv
     __syncthreads();
-    // g_e = (H r_x - f)[p_e] = sum over z-rows of theta a_i[p_e] q'_i - f[p_e]   (16 lanes per equality) -> mu[] (as g)
+    // g_e = ((H [+ P]) r_x - f)[p_e] = sum over z-rows of theta a_i[p_e] q'_i - f[p_e]   (16 lanes per equality) -> mu[] (as g)
     for (int e0 = 0; e0 < neq; e0 += NTHR / 16) {
         const int e = e0 + (tid >> 4), part = tid & 15;
         double a = 0.0;
         const int pc = e < neq ? pcol[e] : -1;
         if (pc >= 0) for (int q = part; q < KW; q += 16) { if (wsrc[q] >= 0) a = fma(wgt[q] * sm[wrow[q] + pc], tvec[q], a); }
+        if constexpr (QP) { if (pc >= 0) for (int i = part; i < n; i += 16) a = fma(Pm[i * n + pc], rx[i], a); }          // + (P r_x)[p_e]: column p_e of P is as loaded, and P is symmetric
         a = group_reduce<16, false>(a);
         if (e < neq && part == 0) mu[e] = pc >= 0 ? a - fvec[pc] : 0.0;
     }
@@ -1006,7 +1094,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         __syncthreads();
         if constexpr (REF) {
             // ---- REF epilogue: x+ = x + dx -> rx,  v+ = v + (dy - ds) -> vv,  y+ = Pi(v+) -> tvec,  s+ = y+ - v+.  The elimination overwrote A: the instance's
-            //      value row is scattered again for rho at the new point.  The step is kept only when the elimination raised no flag and rho fell below the
+            //      value row (QP: and its P row) is scattered again for rho at the new point.  The step is kept only when the elimination raised no flag and rho fell below the
             //      rho of the point that came in (as evaluated now AND as recorded when that point was written: the record never increases); else nothing is written.
             const bool flagged = (misc[2] & 4) != 0;
             bool ok = false;
@@ -1024,6 +1112,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
 #pragma unroll
                     for (int u = 0; u < 4; u++) if (c0[u] >= 0) A[r0[u] * lda + c0[u]] = -v0[u];
                 }
+                load_P();          // (step 2 transformed its rows)
                 project_dual(vv, tvec);
                 __syncthreads();
                 rho1 = kkt_residual(rx, tvec, vv, false);

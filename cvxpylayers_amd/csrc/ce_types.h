@@ -73,6 +73,15 @@ struct NsRefine {
     double *resid;           // [B][2] rho before the first step, rho of the returned point
     int first;               // 1: first launch of the call (the record is initialised)
 };
+// k_backward_ns<..., FWD, REF or not, QP = true>: the quadratic objective of the instance beside what the linear-objective kernel takes
+struct NsQp {
+    const double *P;         // [B][nnz_p] values of P in the template's structure order
+    const double *tP;        // [B][nnz_p] their tangent (the forward derivative only; NULL: zero)
+    const int *pmap;         // [n][n]     entry of the structure at (i, j), -1: structural zero; a one-triangle structure maps (i, j) and (j, i) to one entry
+    int nnz_p;
+};
+struct NsJvpQp : NsJvp { NsQp Q; };
+struct NsRefineQp : NsRefine { NsQp Q; };
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -151,6 +160,8 @@ int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const
 int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones)
 int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);      // the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused)
 int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);      // ... and for one Newton refinement step (a.T and a.Abm alone are read)
+int ce_launch_fwd_ns_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQp &w);        // the two above with a quadratic objective (ce_tu_bwd_ns_qp.hip)
+int ce_launch_refine_ns_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineQp &w);
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -167,6 +178,7 @@ hipError_t ce_setattr_fwd_generic(int bytes);
 hipError_t ce_setattr_bwd_rt_plain(int bytes);
 hipError_t ce_setattr_bwd_rt_psd(int bytes);
 hipError_t ce_setattr_bwd_ns(int bytes);
+hipError_t ce_setattr_bwd_ns_qp(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -45,7 +45,7 @@ namespace {
 #include "ce_forward_generic.h" // fwd_lds_bytes (launch planning); k_forward is instantiated in ce_tu_fwd_other.hip
 #include "ce_backward.h"       // k_transpose, k_parammap*  (k_backward is instantiated in ce_tu_bwd_generic.hip)
 #include "ce_backward_rt.h"    // bwd_rt_lds_bytes, BGC (launch planning); kernels in ce_tu_bwd_rt.hip
-#include "ce_backward_ns.h"    // bwd_ns_lds_bytes_of (launch planning); kernels in ce_tu_bwd_rt.hip
+#include "ce_backward_ns.h"    // bwd_ns_lds_bytes_of, bwd_ns_qp_lds_bytes_of (launch planning); kernels in ce_tu_bwd_rt.hip and ce_tu_bwd_ns_qp.hip
 #include "ce_psd_mfma.h"
 #include "ce_const_a.h"
 #include "ce_shared_a.h"      // sa_lsqr_lds_doubles (launch planning); k_sa_lsqr is instantiated in ce_tu_sa_lsqr.hip
@@ -105,6 +105,7 @@ struct CePlan {
     // two-tile plan of the register-tiled adjoint: a smaller tile serves the instances it holds, the worst-case tile re-runs the ones it flagged
     bool two_tile = false; int fast_forced = -1;
     int ns_variant = -1; size_t ns_lds = 0;        // row of CE_NS_VARIANTS: search-free null-space adjoint (-1: not applicable)
+    int qp_ns_variant = -1; size_t qp_ns_lds = 0;  // row of CE_NS_VARIANTS with the QP footprint: forward derivative and refinement of a qp_native template (-1: none)
 };
 
 struct ce_engine {
@@ -412,6 +413,14 @@ static int plan_engine(const ce_template *tpl, const DevT &T, int nnz_p, const P
         }
     }
     if (P.qp_native && P.bwd_mode != 3) P.qp_native = false;      // the adjoint with P lives in the register-tiled backward kernel
+    // The same elimination with P inside (k_backward_ns<..., QP>): the forward derivative and the refinement of a qp_native template, planned on its own
+    // footprint (the dense P on top).  ns_variant stays -1 for such a template: its adjoint keeps k_backward_rt.
+    if (P.qp_native && !E.ns_off) {
+        for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
+            const size_t by = bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
+            if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { P.qp_ns_variant = v; P.qp_ns_lds = by; break; }
+        }
+    }
     return CE_OK;
 }
 
@@ -460,7 +469,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_ns((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_ns_qp((int)LDS_LIMIT));
     return CE_OK;
 }
 
@@ -503,6 +512,7 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
 }
 
 int ce_adjoint_ns_variant(ce_handle h) { return h ? h->plan.ns_variant : -1; }
+int ce_qp_ns_variant(ce_handle h) { return h ? h->plan.qp_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -1169,6 +1179,50 @@ int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
         if (ce_launch_refine_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+// the two calls above for a template whose quadratic objective runs inside the kernels: k_backward_ns<..., QP>, one launch (per step), no re-solve list
+static int qp_ns_check(ce_handle h, const char *who) {
+    if (!h->plan.qp_native) { g_err = std::string(who) + ": this template does not run a quadratic objective inside the kernels (ce_qp_native == 0)"; return CE_E_UNSUPPORTED; }
+    if (h->plan.qp_ns_variant < 0) { g_err = std::string(who) + ": this template has no search-free elimination with a quadratic objective (n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
+    return CE_OK;
+}
+int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+              const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+              double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+    int rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc;
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = "ce_jvp_qp: A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status;
+    const NsJvpQp W{NsJvp{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters},
+                    NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}};
+    if (ce_launch_fwd_ns_qp(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
+                 const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !P_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_qp: null argument or negative step count"; return CE_E_BADARG; }
+    int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc;
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_refine_qp: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
+    for (int k = 0; k < steps; k++) {
+        const NsRefineQp W{NsRefine{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0}, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}};
+        if (ce_launch_refine_ns_qp(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
     }
     HIPCHK(hipGetLastError());
     return CE_OK;

@@ -41,7 +41,7 @@ class ConeEngine:
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
-        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
+        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -331,14 +331,17 @@ class ConeEngine:
                                          "falling back to the direct elimination (rank-deficient instances are flagged in info['adjoint'])")
         return out
 
-    def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "lsqr"):
+    def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "lsqr",
+            P_bm=None, tP_bm=None):
         """Forward-mode derivative of the solution map (diffcp's `derivative`): tangents tA_bm (B, nnz_aug) of the value rows and tq (n+1, B) of q_eval, either may be
         None (zero).  Returns dx (B, n), dy (B, m), ds (B, m), status (B,) -- 1: LSQR hit its iteration limit -- and sets last_lsqr_iters.
         One kernel per call, ce_jvp_lsqr, or ce_jvp_shared_a when `path` is "const_a" (only the b entries of tA_bm are read there: a shared A has no tangent).
         path, lsqr (rule, adjoint_system) and q_eval as vjp(); the LSQR recurrences only.  NotImplementedError when the LSQR vectors of one instance exceed LDS.
         method="direct": ce_jvp on the per-instance path -- the search-free elimination, then LSQR under the same rule for the instances it flags rank deficient
         (status 4 | 8 and iterations > 0 there, status 0 and 0 iterations elsewhere).  Where the library has no elimination for the template, and on the const_a
-        path, the LSQR call runs instead; last_jvp_kernel names the entry point that ran."""
+        path, the LSQR call runs instead; last_jvp_kernel names the entry point that ran.
+        P_bm (B, nnz_p): the quadratic objective of a qp_native engine, with its tangent tP_bm (or None: zero) -- method="direct" only: ce_jvp_qp, the same elimination
+        with P inside and NO LSQR behind it (a flagged instance keeps the elimination's answer, status 4, 0 iterations); NotImplementedError under method="lsqr"."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
@@ -348,6 +351,11 @@ class ConeEngine:
             return torch.empty((0, self.n), **f64), torch.empty((0, self.m), **f64), torch.empty((0, self.m), **f64), torch.empty((0,), dtype=torch.int32, device=dev)
         if path is None:
             path = self.last_path
+        if P_bm is not None:
+            if method != "direct":
+                raise NotImplementedError("ConeEngine.jvp: a quadratic objective inside the kernels has no LSQR forward derivative; use method='direct' "
+                                          "(or the epigraph form, CE_QP_EPIGRAPH=1)")
+            return self._jvp_qp(A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm)
         atol, btol, lim, system, _ = unpack_rule(lsqr, self.n, self.m)
         if q_eval is None and system != "reduced":
             q_eval = self._recent_q(A_bm)
@@ -380,12 +388,32 @@ class ConeEngine:
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
-    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None):
+    def _jvp_qp(self, A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm):
+        """ce_jvp_qp (include/cone_engine.h): one launch of the search-free elimination with P inside"""
+        B = A_bm.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        bm = lambda t: t.detach().to(**f64).contiguous() if t is not None else None      # noqa: E731
+        A_c, P_c, xc, yc, sc_, tA_c, tP_c = (bm(t) for t in (A_bm, P_bm, x, y, s, tA_bm, tP_bm))
+        tqd, tq_args = self._q_args(tq)
+        dx = torch.empty((B, self.n), **f64); dy = torch.empty((B, self.m), **f64); ds = torch.empty((B, self.m), **f64)
+        st = torch.empty((B,), dtype=torch.int32, device=self.device); its = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        rc = _lib.lib().ce_jvp_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                                  ptr(tA_c), self.nnz_aug, *tq_args, ptr(tP_c), dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(), self._stream())
+        if rc == -2:
+            raise NotImplementedError(_lib.lib().ce_last_error().decode())
+        _lib.check(rc, "ce_jvp_qp")
+        self.last_jvp_kernel = "ce_jvp_qp"
+        self.last_lsqr_iters = its
+        return dx, dy, ds, st
+
+    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None, P_bm=None):
         """`steps` safeguarded Newton steps on the KKT residual of (x, y, s) (include/cone_engine.h ce_refine): A_bm (B, nnz_aug), q_eval (n+1, B), x (B, n), y, s
         (B, m); status (B,) int32 or None: instances with a negative forward status are skipped.  Returns x, y, s, info -- contiguous fp64 tensors on this
         engine's device are refined IN PLACE and handed back, others are copied first.  info: "status" (bits 1 a step kept, 2 a step rejected, 4 flagged by the
         elimination, 16 skipped), "steps" (kept per instance), "resid_before" / "resid_after" (rho of the point that came in and of the one returned), "path"
-        "ns" -- or "none", with the other entries None and the point untouched, where the library has no elimination for the template.  No host synchronisation."""
+        "ns" -- or "none", with the other entries None and the point untouched, where the library has no elimination for the template.  No host synchronisation.
+        P_bm (B, nnz_p): the quadratic objective of a qp_native engine (ce_refine_qp: F_x = P x + A^T y^ + c)."""
         B = A_bm.shape[0]
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -398,11 +426,15 @@ class ConeEngine:
         st_c = status.to(device=dev, dtype=torch.int32).contiguous() if status is not None else None
         rst = torch.empty((B,), dtype=torch.int32, device=dev); taken = torch.empty((B,), dtype=torch.int32, device=dev)
         resid = torch.empty((B, 2), **f64)
-        rc = _lib.lib().ce_refine(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(), s.data_ptr(),
-                                  st_c.data_ptr() if st_c is not None else None, int(steps), rst.data_ptr(), taken.data_ptr(), resid.data_ptr(), self._stream())
+        tail = (x.data_ptr(), y.data_ptr(), s.data_ptr(), st_c.data_ptr() if st_c is not None else None, int(steps), rst.data_ptr(), taken.data_ptr(), resid.data_ptr(), self._stream())
+        if P_bm is not None:
+            P_c = P_bm.detach().to(**f64).contiguous()
+            rc, name = _lib.lib().ce_refine_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp"
+        else:
+            rc, name = _lib.lib().ce_refine(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine"
         if rc == -2:
             return x, y, s, none
-        _lib.check(rc, "ce_refine")
+        _lib.check(rc, name)
         return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns"}
 
     # introspection (bench / tests)

@@ -144,7 +144,7 @@ class _Saved(NamedTuple):
     path: str                               # adjoint_path() of this call
     failed: Optional[torch.Tensor]          # raise_on_error=False: mask of the instances returned as NaN
     lsqr: tuple                             # lsqr_rule() of this call
-    q_eval: Optional[torch.Tensor]          # (n+1, B) objective values (linear objective only)
+    q_eval: Optional[torch.Tensor]          # (n+1, B) objective values (linear objective only: ce_jvp_qp and ce_vjp_qp take none)
     jvp_mode: str = "lsqr"                  # jvp_mode() of this call
 
 
@@ -194,11 +194,11 @@ class _ConeLayer(torch.autograd.Function):
             refine_info = None
             if n_refine > 0:
                 refine_info = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
-                if P_bm is None and eng.last_path == "per_instance" and status.numel():
-                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status)
+                if eng.last_path == "per_instance" and status.numel():
+                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm)
                 if refine_info["path"] == "none" and status.numel():
                     _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD / "
-                                              "exponential / power cones, n > 108, a shared A, a quadratic objective inside the kernels); the solver's point is returned "
+                                              "exponential / power cones, n > 108, a shared A); the solver's point is returned "
                                               "unrefined (info['refine']['path'] == 'none')")
             eng._last_solution = (x.detach(), y.detach(), s)
             # The reference raises from forward() when an instance fails (diffcp_if.py:365-372), so the host has to learn the outcome here: one tiny
@@ -267,15 +267,18 @@ class _ConeLayer(torch.autograd.Function):
     def jvp(ctx, tP, tq, tA, *_):
         """Forward-mode derivative (torch.autograd.forward_ad; diffcp's `derivative`, which the reference plugin never calls): the tangents of q_eval / A_eval in,
         the tangents of (primal, dual) out, by one launch of the LSQR kernel on M d = -dQ pi (ConeEngine.jvp) under this call's lsqr_rule -- or, with solver_args
-        jvp_mode="direct", by the direct elimination with LSQR for the rank-deficient instances only.  Fills info["jvp"]: status, iters and the path that ran
+        jvp_mode="direct", by the direct elimination with LSQR for the rank-deficient instances only.  A quadratic objective inside the kernels (tP: the tangent
+        of P_eval) has the direct elimination alone (ce_jvp_qp: no LSQR behind it; NotImplementedError under the default jvp_mode).  Fills info["jvp"]: status, iters and the path that ran
         ("direct" / "lsqr": a template without the elimination runs LSQR and says so)."""
         saved, batch_size, originally_unbatched, in_device = ctx.backward_data
         if saved is None:
             raise RuntimeError("forward-mode derivative requested from a layer evaluated with needs_grad=False")
-        if saved.P_bm is not None:
-            raise NotImplementedError("MI355 solver: the forward-mode derivative is not available with a quadratic objective inside the kernels; "
-                                      "set CE_QP_EPIGRAPH=1 to bring the problem to cone form, where it applies")
-        if tq is None and tA is None:
+        qp = saved.P_bm is not None
+        if qp and saved.jvp_mode != "direct":
+            raise NotImplementedError("MI355 solver: the LSQR forward-mode derivative is not available with a quadratic objective inside the kernels; "
+                                      "pass solver_args jvp_mode='direct' (the elimination with P inside), or set CE_QP_EPIGRAPH=1 to bring the problem "
+                                      "to cone form, where the default applies")
+        if tq is None and tA is None and (tP is None or not qp):
             return None, None, None, None
         eng, x, y, s, failed = saved.eng, saved.x, saved.y, saved.s, saved.failed
         with torch.cuda.device(eng.device):
@@ -289,12 +292,18 @@ class _ConeLayer(torch.autograd.Function):
                 x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
             # a shared-A call whose A values merely coincide may still carry a tangent in A: the shared kernel reads the b entries only
             path = saved.path if (saved.path != "const_a" or tA_bm is None or eng.A_is_constant) else "per_instance"
-            dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode)
+            if qp:          # tP in the P_eval convention (nnz_p, B), symmetrised like the values by _CvxpyLayer.apply's torch ops
+                tP_bm = None
+                if tP is not None:
+                    tP_bm = (tP.unsqueeze(1) if originally_unbatched else tP).detach().to(device=eng.device, dtype=torch.float64).t().contiguous()
+                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, method="direct", P_bm=saved.P_bm, tP_bm=tP_bm)
+            else:
+                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode)
             if failed is not None:
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel == "ce_jvp" else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod

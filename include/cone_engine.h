@@ -92,7 +92,7 @@ void ce_default_settings(ce_settings *s);
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
  * layout, an entry point's signature or the meaning of an argument changes (16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
-#define CE_ABI_VERSION 16
+#define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
 /* The iterative adjoint solver of ce_vjp_shared_a / ce_vjp_lsqr (the calls that solve EVERY instance iteratively): 0 = LSQR (Paige & Saunders; diffcp's default
@@ -342,6 +342,29 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
 int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
               double *x, double *y, double *s /* in/out */, const int *status /* may be NULL */, int steps,
               int *refine_status, int *steps_taken, double *resid, void *stream);
+
+/*
+ * ce_jvp and ce_refine for a template whose QUADRATIC OBJECTIVE runs inside the kernels (ce_qp_native(h) == 1): the same search-free elimination with P in the
+ * stationarity row,  P d_x + A^T D d_v = -g_x,  g_x = tP x + tA^T y + tc  (refinement: F_x = P x + A^T y^ + c), i.e. the reduced Hessian Z^T (H + P) Z.
+ * P_vals, tP_vals (B, nnz_p) batch-major in the structure order of ce_create (a one-triangle structure: one entry stands for both matrix entries, in the values
+ * and in the tangent); tP_vals, tA_vals_bm, tq_vals may each be NULL (zero).  Other arguments as ce_jvp / ce_refine; ce_jvp_qp takes no q_vals and no LSQR
+ * rule: no LSQR has a P term, so NO re-solve runs behind it.  One launch (ce_refine_qp: `steps` launches), never a host synchronisation.
+ * jvp_status[i]: 0 solved; 4 the elimination flagged the instance (a redundant equality row, a vanishing pivot of Z^T (H + P) Z, more active rows than
+ * variables) and its dropped-variable answer stands, finite -- the contract of ce_vjp_qp; bit 8 is never set and lsqr_iters[i] = 0.  With no active row the
+ * reduced Hessian is P alone: regular for a positive definite P.  ce_refine_qp: a flagged instance keeps its point, as in ce_refine.
+ * CE_E_UNSUPPORTED when ce_qp_native(h) == 0 or ce_qp_ns_variant(h) < 0.  ce_jvp, ce_jvp_lsqr and ce_refine keep refusing such a handle.
+ */
+int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals,
+              const double *x, const double *y, const double *s,
+              const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+              double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream);
+int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
+                 double *x, double *y, double *s /* in/out */, const int *status /* may be NULL */, int steps,
+                 int *refine_status, int *steps_taken, double *resid, void *stream);
+/* >= 0: the row of csrc/ce_variants.h CE_NS_VARIANTS that serves ce_jvp_qp / ce_refine_qp (planned on bwd_ns_qp_lds_bytes_of: the dense P on top of
+ * ce_adjoint_ns_variant's footprint, two workgroups per CU at the config-2 shape); -1: none (not qp_native, n > 108, CE_BWD_NS=0).  ce_adjoint_ns_variant stays
+ * -1 for a qp_native template: its adjoint keeps the pivoting kernel. */
+int ce_qp_ns_variant(ce_handle h);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
