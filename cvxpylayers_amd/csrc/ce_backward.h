@@ -4,7 +4,6 @@
 // BACKWARD
 // ================================================================================================
 // row kinds after classifying DPi_{K*}(v), v = y - s
-enum { RK_EQ = 0, RK_FREE = 1, RK_SOCB = 2, RK_MIX = 3 };   // RK_MIX: rotated PSD row with 0 < DPi eigenvalue < 1
 
 // bytes of k_backward<a_lds, k_lds>'s dynamic LDS: the carve at the top of the kernel, term by term (panel: T.gen_blocked_b, the panels of the blocked elimination)
 __host__ __device__ inline size_t bwd_lds_bytes(const DevT &T, bool a_lds, bool k_lds, int nkcap, int ldk, bool panel = false) {

@@ -50,28 +50,8 @@
 // Plain cones (zero / nonnegative / second-order).  PSD / exponential / power cones keep k_backward_rt, and so does the ADJOINT with a quadratic objective.
 #pragma once
 
-// pitch of the sweep's row buffers: 16 mod 32 doubles (conflict-free) with at least 16 doubles of gap behind the 16 NTILE entries of a row (the gaps of the
-// eight buffer rows hold the ORIGINAL diagonal of the reduced Hessian: the rank tolerance of a pivot is relative to its own diagonal entry)
-__host__ __device__ constexpr int bwd_ns_ldp(int NTILE) { return (16 * NTILE + 16) % 32 == 16 ? 16 * NTILE + 16 : 16 * NTILE + 32; }
-__host__ __device__ inline int bwd_ns_kwmax(int m) { return ((m + 4) & ~3) + 4; }                                            // capacity of the weighted-row list (<= m entries + at least one pad, a multiple of 4)
-__host__ __device__ constexpr int bwd_ns_nsl(int NTILE) { return (16 * NTILE - 3 + 63) / 64; }                               // 64-lane slots that hold the columns 0 .. n (n = right-hand side)
-__host__ __device__ inline int bwd_ns_union_doubles(int n, int m, int nqs, int NTILE) {
-    const int npad = n + (n & 1);
-    int a = nqs * npad + 2 * (64 * bwd_ns_nsl(NTILE) + 2), b = 8 * bwd_ns_ldp(NTILE), c = m + (m & 1) + npad;      // {a_z, the row elimination's two publication buffers} | the sweep's row buffers | {q, g}
-    int r = a > b ? a : b;
-    return r > c ? r : c;
-}
-__host__ __device__ inline size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) {
-    const int nqs = nq > 0 ? nq : 1, kw = bwd_ns_kwmax(m), npad = n + (n & 1);
-    size_t d = (size_t)m * n + 1 + 2 * (size_t)m /* vv, dv */ + 3 * (size_t)npad /* rx, fvec, dB */ + 5 * (size_t)nqs + 2 * (size_t)kw /* tvec, wgt */ +
-               (size_t)(NTHR / 64) * 8 + (size_t)nqs /* qaz */ + 1 + (size_t)bwd_ns_union_doubles(n, m, nqs, NTILE);
-    size_t i = 2 * (size_t)m + 3 * (size_t)nqs + 4 * (size_t)n + 2 * (size_t)kw + (size_t)(NTHR / 64) + 1 + 8;
-    return d * 8 + i * 4;
-}
-// QP instantiations: behind the footprint above (rounded to 8 bytes) the dense P (pitch n), t_j = p_j . x_p per row of P, and pivot column -> equality
-__host__ __device__ inline size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) {
-    return ((bwd_ns_lds_bytes_of(n, m, nq, NTILE, NTHR) + 7) & ~(size_t)7) + ((size_t)n * n + (size_t)(n + (n & 1))) * 8 + (size_t)n * 4;
-}
+#include "ce_ns_layout.h"          // ns_layout: the LDS segments of this kernel and its footprint (what the launch plan and tests/test_ns_layout_host.py use); bwd_ns_ldp, bwd_ns_nsl,
+                                   // bwd_ns_kwmax, bwd_ns_union_doubles.  The carve below is still the kernel's own statement of the same layout.
 
 #ifdef CE_TIMING
 #define NS_STAMP(i) do { __syncthreads(); if (threadIdx.x == 0) tstamp[i] = __builtin_readcyclecounter(); } while (0)

@@ -17,6 +17,9 @@ constexpr double TAU_FACTOR = 10.0, ZERO_CONE_FACTOR = 1000.0;
 // consistent system there, diffcp_if.py:73-96), whatever kernel the template's size selects
 constexpr double CE_RANK_TOL = 1e-11;
 
+// row kinds of the adjoint kernels' classification passes (k_backward, k_backward_rt, k_backward_ns)
+enum { RK_EQ = 0, RK_FREE = 1, RK_SOCB = 2, RK_MIX = 3 };   // RK_MIX: rotated PSD row with 0 < DPi eigenvalue < 1
+
 // DevT (the device-side template description) lives in ce_types.h, shared by all translation units
 
 thread_local std::string g_err;

@@ -10,9 +10,6 @@ namespace {
 #include "ce_global_mv.h"
 #include "ce_backward.h"
 #include "ce_backward_rt.h"
-#if CE_BRT_PSD == 0
-#include "ce_backward_ns.h"
-#endif
 }  // namespace
 
 #ifndef CE_BRT_PSD
@@ -46,37 +43,6 @@ hipError_t setattr_brt(int bytes) {
 #if CE_BRT_PSD == 0
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a) { return launch_brt<CE_BRT_PSD != 0>(variant, B, lds, st, a); }
 hipError_t ce_setattr_bwd_rt_plain(int bytes) { return setattr_brt<CE_BRT_PSD != 0>(bytes); }
-// search-free null-space adjoint (ce_backward_ns.h)
-int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a) {
-    switch (variant) {
-#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.fix, NsNoJvp{}); return 0;
-        CE_NS_VARIANTS(X)
-#undef X
-    default: return -1;
-    }
-}
-int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w) {
-    switch (variant) {
-#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR, true>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, nullptr, nullptr, nullptr, nullptr, 0L, 0L, a.adj, a.fix, w); return 0;
-        CE_NS_VARIANTS(X)
-#undef X
-    default: return -1;
-    }
-}
-int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w) {
-    switch (variant) {
-#define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR, true, true>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0L, 0L, nullptr, nullptr, w); return 0;
-        CE_NS_VARIANTS(X)
-#undef X
-    default: return -1;
-    }
-}
-hipError_t ce_setattr_bwd_ns(int bytes) {
-#define X(V, NTILE, NTHR) SETATTR((k_backward_ns<NTILE, NTHR>)); SETATTR((k_backward_ns<NTILE, NTHR, true>)); SETATTR((k_backward_ns<NTILE, NTHR, true, true>));
-    CE_NS_VARIANTS(X)
-#undef X
-    return hipSuccess;
-}
 #else
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a) { return launch_brt<CE_BRT_PSD != 0>(variant, B, lds, st, a); }
 hipError_t ce_setattr_bwd_rt_psd(int bytes) { return setattr_brt<CE_BRT_PSD != 0>(bytes); }

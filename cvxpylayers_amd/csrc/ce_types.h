@@ -157,11 +157,14 @@ int ce_launch_fwd2_qp(int variant, int B, size_t lds, hipStream_t st, const CeFw
 int ce_launch_fwd_rt(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
-int ce_launch_bwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);       // search-free null-space adjoint (plain cones)
-int ce_launch_fwd_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);      // the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused)
-int ce_launch_refine_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);      // ... and for one Newton refinement step (a.T and a.Abm alone are read)
-int ce_launch_fwd_ns_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQp &w);        // the two above with a quadratic objective (ce_tu_bwd_ns_qp.hip)
-int ce_launch_refine_ns_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineQp &w);
+// k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
+// search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement
+// step (a.T and a.Abm alone are read); the last two with a quadratic objective
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsNoJvp &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQp &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineQp &w);
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -177,8 +180,8 @@ hipError_t ce_setattr_fwd_rt(int bytes);
 hipError_t ce_setattr_fwd_generic(int bytes);
 hipError_t ce_setattr_bwd_rt_plain(int bytes);
 hipError_t ce_setattr_bwd_rt_psd(int bytes);
-hipError_t ce_setattr_bwd_ns(int bytes);
-hipError_t ce_setattr_bwd_ns_qp(int bytes);
+hipError_t ce_setattr_ns(int bytes);
+hipError_t ce_setattr_ns_qp(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

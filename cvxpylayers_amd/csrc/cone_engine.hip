@@ -45,7 +45,7 @@ namespace {
 #include "ce_forward_generic.h" // fwd_lds_bytes (launch planning); k_forward is instantiated in ce_tu_fwd_other.hip
 #include "ce_backward.h"       // k_transpose, k_parammap*  (k_backward is instantiated in ce_tu_bwd_generic.hip)
 #include "ce_backward_rt.h"    // bwd_rt_lds_bytes, BGC (launch planning); kernels in ce_tu_bwd_rt.hip
-#include "ce_backward_ns.h"    // bwd_ns_lds_bytes_of, bwd_ns_qp_lds_bytes_of (launch planning); kernels in ce_tu_bwd_rt.hip and ce_tu_bwd_ns_qp.hip
+#include "ce_ns_layout.h"      // bwd_ns_lds_bytes_of, bwd_ns_qp_lds_bytes_of (launch planning): the total of the layout k_backward_ns carves; kernels in ce_tu_ns.hip
 #include "ce_psd_mfma.h"
 #include "ce_const_a.h"
 #include "ce_shared_a.h"      // sa_lsqr_lds_doubles (launch planning); k_sa_lsqr is instantiated in ce_tu_sa_lsqr.hip
@@ -211,6 +211,16 @@ static size_t brt_lds_bytes(const DevT &T, int v) { return bwd_rt_lds_bytes(T, B
 // count sums in another order, and its gradients would differ in the last bits from the single-tile plan's
 static bool brt_tile_holds(const DevT &T, int v) { return T.n <= BGC * BRT_ROWS[v].TH && brt_lds_bytes(T, v) <= LDS_LIMIT; }
 static bool brt_first_tile_ok(const DevT &T, int v, int worst) { return BRT_ROWS[v].TH == BRT_ROWS[worst].TH && BRT_ROWS[v].BGR == BRT_ROWS[worst].BGR && brt_tile_holds(T, v); }
+
+// k_backward_ns: the first row of CE_NS_VARIANTS whose tiles hold the reduced system (4 ceil(n / 4) + 1 columns) and whose layout (with P: the dense P on top) fits LDS;
+// -1: none.  *lds: its footprint
+static int ns_first_fit(const DevT &T, bool qp, size_t *lds) {
+    for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
+        const size_t by = qp ? bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR) : bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
+        if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { *lds = by; return v; }
+    }
+    return -1;
+}
 
 // Row order for k_fwd2's wave-local cone exchange (ce_forward_v2.h, WL): the rows of one wave in the (i2, c2) row layout form a
 // window of W = 64 / CHA rows, and no cone may straddle two windows.  Zero-cone rows stay first (the kernel tells them by i < z);
@@ -406,21 +416,11 @@ static int plan_engine(const ce_template *tpl, const DevT &T, int nnz_p, const P
     }
     // Search-free null-space adjoint (ce_backward_ns.h): plain cones, linear objective, 4 ceil(n / 4) + 1 columns in the variant's tiles.  It serves ce_vjp calls
     // whose LSQR re-solve is armed (rank-deficient instances are detected, flagged and handed to LSQR, not resolved by the elimination).  CE_BWD_NS=0 disables.
-    if (plain && nnz_p == 0 && !E.ns_off && !E.force_generic) {
-        for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
-            const size_t by = bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
-            if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { P.ns_variant = v; P.ns_lds = by; break; }
-        }
-    }
+    if (plain && nnz_p == 0 && !E.ns_off && !E.force_generic) P.ns_variant = ns_first_fit(T, false, &P.ns_lds);
     if (P.qp_native && P.bwd_mode != 3) P.qp_native = false;      // the adjoint with P lives in the register-tiled backward kernel
     // The same elimination with P inside (k_backward_ns<..., QP>): the forward derivative and the refinement of a qp_native template, planned on its own
     // footprint (the dense P on top).  ns_variant stays -1 for such a template: its adjoint keeps k_backward_rt.
-    if (P.qp_native && !E.ns_off) {
-        for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
-            const size_t by = bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
-            if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { P.qp_ns_variant = v; P.qp_ns_lds = by; break; }
-        }
-    }
+    if (P.qp_native && !E.ns_off) P.qp_ns_variant = ns_first_fit(T, true, &P.qp_ns_lds);
     return CE_OK;
 }
 
@@ -469,7 +469,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_ns_qp((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT));
     return CE_OK;
 }
 
@@ -729,7 +729,7 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         h->last_fast = -1;
         if (do_fix && P.ns_variant >= 0) {
             ba.T.lda = T.n;
-            lrc = ce_launch_bwd_ns(P.ns_variant, B, P.ns_lds, st, ba);
+            lrc = ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, NsNoJvp{});
         } else if (P.bwd_mode == 3) {
             ba.T.lda = T.n;
             int fast = -1; size_t fast_lds = 0;
@@ -1132,45 +1132,77 @@ int ce_jvp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const do
     if (sA_b == 0 && B > 1) { g_err = "ce_jvp_lsqr: per-instance values need a batch stride"; return CE_E_BADARG; }
     return jvp_lsqr_launch(h, B, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
 }
-int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
-           const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
-           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
-    // the forward derivative as ce_vjp_qp runs the adjoint: the search-free elimination (k_backward_ns<..., FWD>), then the fixed grid of LSQR workgroups that
-    // re-solves the instances it listed as rank deficient -- the same re-solve list
-    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+// a call that runs the elimination with a quadratic objective inside (`who`): the template must have planned one
+static int qp_ns_check(ce_handle h, const char *who) {
+    if (!h->plan.qp_native) { g_err = std::string(who) + ": this template does not run a quadratic objective inside the kernels (ce_qp_native == 0)"; return CE_E_UNSUPPORTED; }
+    if (h->plan.qp_ns_variant < 0) { g_err = std::string(who) + ": this template has no search-free elimination with a quadratic objective (n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
+    return CE_OK;
+}
+// The forward derivative as ce_vjp_qp runs the adjoint: the search-free elimination (k_backward_ns<..., FWD>), then the fixed grid of LSQR workgroups that
+// re-solves the instances it listed as rank deficient -- the same re-solve list.  With P_vals (ce_jvp_qp: k_backward_ns<..., FWD, QP>) one launch and no re-solve list: no LSQR has a P term.
+static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
+                  const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    const bool qp = P_vals != nullptr;
+    const std::string who = qp ? "ce_jvp_qp" : "ce_jvp";
     const CePlan &P = h->plan;
     const DevT &T = h->T;
-    if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
-    if (P.ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
-    if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
-    if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = "ce_jvp: A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    int rc = CE_OK;
+    if (qp) { rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc; }
+    else {
+        if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
+        if (P.ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+        if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    }
+    const int variant = qp ? P.qp_ns_variant : P.ns_variant; const size_t lds = qp ? P.qp_ns_lds : P.ns_lds;
+    if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = who + ": A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    FixLists fix;
-    int rc = resolve_lists(h, B, st, &fix); if (rc) return rc;
+    FixLists fix{nullptr, nullptr};
+    if (!qp) { rc = resolve_lists(h, B, st, &fix); if (rc) return rc; }
     ProfScope ps(h, 1, st);
     CeBwdArgs ba{};
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
-    if (ce_launch_fwd_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
-    rc = resolve_run(h, B, fix, [&](int grid, const int *sel, int status_or, int *sel_reset) {
-        return jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
-                               atol, btol, conlim, iter_lim, stream, sel, status_or, sel_reset);
-    });
-    if (rc) return rc;
+    const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}}) : ce_launch_ns(variant, B, lds, st, ba, W);
+    if (lrc) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
+    if (!qp) {
+        rc = resolve_run(h, B, fix, [&](int grid, const int *sel, int status_or, int *sel_reset) {
+            return jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
+                                   atol, btol, conlim, iter_lim, stream, sel, status_or, sel_reset);
+        });
+        if (rc) return rc;
+    }
     HIPCHK(hipGetLastError());
     return CE_OK;
 }
-int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
-              const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
-    // `steps` launches of k_backward_ns<..., FWD, REF>, one complete safeguarded Newton step each; the per-instance record (refine_status, steps_taken, resid)
-    // carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
-    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine: null argument or negative step count"; return CE_E_BADARG; }
+int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+           const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+           double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+              const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+              double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, tP_vals, dx, dy, ds, jvp_status, lsqr_iters, 0.0, 0.0, 0.0, 0, stream);
+}
+// `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
+// (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
+static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
+                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    const bool qp = P_vals != nullptr;
+    const std::string who = qp ? "ce_refine_qp" : "ce_refine";
     const CePlan &P = h->plan;
     const DevT &T = h->T;
-    if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
-    if (P.ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
-    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_refine: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    if (qp) { const int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc; }
+    else {
+        if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
+        if (P.ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
+    }
+    const int variant = qp ? P.qp_ns_variant : P.ns_variant; const size_t lds = qp ? P.qp_ns_lds : P.ns_lds;
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = who + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(h, 1, st);
@@ -1178,54 +1210,21 @@ int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
-        if (ce_launch_refine_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
+        const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}}) : ce_launch_ns(variant, B, lds, st, ba, W);
+        if (lrc) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
     }
     HIPCHK(hipGetLastError());
     return CE_OK;
 }
-// the two calls above for a template whose quadratic objective runs inside the kernels: k_backward_ns<..., QP>, one launch (per step), no re-solve list
-static int qp_ns_check(ce_handle h, const char *who) {
-    if (!h->plan.qp_native) { g_err = std::string(who) + ": this template does not run a quadratic objective inside the kernels (ce_qp_native == 0)"; return CE_E_UNSUPPORTED; }
-    if (h->plan.qp_ns_variant < 0) { g_err = std::string(who) + ": this template has no search-free elimination with a quadratic objective (n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
-    return CE_OK;
-}
-int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
-              const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
-              double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
-    if (!h || B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
-    int rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc;
-    const CePlan &P = h->plan;
-    const DevT &T = h->T;
-    if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = "ce_jvp_qp: A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(h, 1, st);
-    CeBwdArgs ba{};
-    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status;
-    const NsJvpQp W{NsJvp{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters},
-                    NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}};
-    if (ce_launch_fwd_ns_qp(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
-    HIPCHK(hipGetLastError());
-    return CE_OK;
+int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+              const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine: null argument or negative step count"; return CE_E_BADARG; }
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream);
 }
 int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
                  const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !q_vals || !P_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_qp: null argument or negative step count"; return CE_E_BADARG; }
-    int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc;
-    const CePlan &P = h->plan;
-    const DevT &T = h->T;
-    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_refine_qp: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(h, 1, st);
-    CeBwdArgs ba{};
-    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
-    for (int k = 0; k < steps; k++) {
-        const NsRefineQp W{NsRefine{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0}, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}};
-        if (ce_launch_refine_ns_qp(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
-    }
-    HIPCHK(hipGetLastError());
-    return CE_OK;
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, P_vals, x, y, s, status, steps, refine_status, steps_taken, resid, stream);
 }
 int ce_ca_triples(ce_handle h, int B, int lp, double *U, double *roots, const int *active, void *stream) {
     if (!h || B <= 0 || !U || !roots || !active) { g_err = "null argument"; return CE_E_BADARG; }

@@ -364,15 +364,11 @@ class ConeEngine:
         shared = path == "const_a"
         fn, name = (_lib.lib().ce_jvp_shared_a, "ce_jvp_shared_a") if shared else (_lib.lib().ce_jvp_lsqr, "ce_jvp_lsqr")
         A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) >= self.nnz_aug)) else A_bm.contiguous()
-        xc, yc, sc_ = (t.detach().to(**f64).contiguous() for t in (x, y, s))
-        tA_c = tA_bm.detach().to(**f64).contiguous() if tA_bm is not None else None
-        tqd, tq_args = self._q_args(tq)
+        point, tangents, outs, keep = self._jvp_buffers(B, x, y, s, tA_bm, tq)
         qd, q_args = self._q_args(q_eval)
-        dx = torch.empty((B, self.n), **f64); dy = torch.empty((B, self.m), **f64); ds = torch.empty((B, self.m), **f64)
-        st = torch.empty((B,), dtype=torch.int32, device=dev); its = torch.empty((B,), dtype=torch.int32, device=dev)
+        dx, dy, ds, st, its = outs
         def call(fn, A_t):
-            return fn(self._h, B, A_t.data_ptr(), A_t.stride(0), *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
-                      tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args, dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(),
+            return fn(self._h, B, A_t.data_ptr(), A_t.stride(0), *q_args, *point, *tangents, *(t.data_ptr() for t in outs),
                       float(atol), float(btol), float(conlim), int(lim), self._stream())
         rc = -2
         if method == "direct" and not shared:
@@ -388,18 +384,29 @@ class ConeEngine:
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
+    def _jvp_buffers(self, B, x, y, s, tA_bm, tq):
+        """What every forward-derivative entry point takes: the pointers of the point (x, y, s), of the tangents (tA, its row stride, tq and its strides), the output
+        tensors dx, dy, ds, status, iterations, and the converted inputs, which the caller keeps alive until the call returns"""
+        f64 = dict(dtype=torch.float64, device=self.device)
+        xc, yc, sc_ = (t.detach().to(**f64).contiguous() for t in (x, y, s))
+        tA_c = tA_bm.detach().to(**f64).contiguous() if tA_bm is not None else None
+        tqd, tq_args = self._q_args(tq)
+        outs = (torch.empty((B, self.n), **f64), torch.empty((B, self.m), **f64), torch.empty((B, self.m), **f64),
+                torch.empty((B,), dtype=torch.int32, device=self.device), torch.empty((B,), dtype=torch.int32, device=self.device))
+        point = (xc.data_ptr(), yc.data_ptr(), sc_.data_ptr())
+        tangents = (tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args)
+        return point, tangents, outs, (xc, yc, sc_, tA_c, tqd)
+
     def _jvp_qp(self, A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm):
         """ce_jvp_qp (include/cone_engine.h): one launch of the search-free elimination with P inside"""
         B = A_bm.shape[0]
         f64 = dict(dtype=torch.float64, device=self.device)
-        bm = lambda t: t.detach().to(**f64).contiguous() if t is not None else None      # noqa: E731
-        A_c, P_c, xc, yc, sc_, tA_c, tP_c = (bm(t) for t in (A_bm, P_bm, x, y, s, tA_bm, tP_bm))
-        tqd, tq_args = self._q_args(tq)
-        dx = torch.empty((B, self.n), **f64); dy = torch.empty((B, self.m), **f64); ds = torch.empty((B, self.m), **f64)
-        st = torch.empty((B,), dtype=torch.int32, device=self.device); its = torch.empty((B,), dtype=torch.int32, device=self.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        rc = _lib.lib().ce_jvp_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
-                                  ptr(tA_c), self.nnz_aug, *tq_args, ptr(tP_c), dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr(), self._stream())
+        A_c, P_c = (t.detach().to(**f64).contiguous() for t in (A_bm, P_bm))
+        tP_c = tP_bm.detach().to(**f64).contiguous() if tP_bm is not None else None
+        point, tangents, outs, keep = self._jvp_buffers(B, x, y, s, tA_bm, tq)
+        dx, dy, ds, st, its = outs
+        rc = _lib.lib().ce_jvp_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), *point, *tangents, tP_c.data_ptr() if tP_c is not None else None,
+                                  *(t.data_ptr() for t in outs), self._stream())
         if rc == -2:
             raise NotImplementedError(_lib.lib().ce_last_error().decode())
         _lib.check(rc, "ce_jvp_qp")
