@@ -49,6 +49,7 @@
 //
 // Plain cones (zero / nonnegative / second-order).  PSD / exponential / power cones keep k_backward_rt, and so does the ADJOINT with a quadratic objective.
 #pragma once
+#include "ce_common.h"
 
 #include "ce_ns_layout.h"          // ns_layout: the LDS segments of this kernel and its footprint (what the launch plan and tests/test_ns_layout_host.py use); bwd_ns_ldp, bwd_ns_nsl,
                                    // bwd_ns_kwmax, bwd_ns_union_doubles.  The carve below is still the kernel's own statement of the same layout.

@@ -13,15 +13,17 @@
 //   * H = sum_c theta_c (A_c^T A_c - a_y a_y^T - a_s a_s^T) is accumulated directly in tile layout with 4x4-style register
 //     blocking (rows {ra+16i} x columns {cb+16j}: TI + TJ LDS reads feed TI*TJ FMAs per cone row).
 #pragma once
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_wave_helpers.h"    // block_reduce_n
+#include "ce_psd_jacobi.h"
+#include "ce_lds_bwd_rt.h"       // BG, BGC, bwd_rt_lds_bytes: the total of the carve at the top of the kernel
 
 // v_max_f64 without the canonicalisation fmax() puts in front of it (operands are finite by construction)
 __device__ __forceinline__ double vmax_raw(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
 // max(a, |b|) with the bare instruction (b's sign bit may carry anything)
 __device__ __forceinline__ double vmax_abs(double a, double b) { double r; asm("v_max_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-constexpr int BG = 16;   // default thread grid is BG x BG
-constexpr int BGC = 16;  // column residues (always one DPP row wide)
 
 #ifdef CE_TIMING   // debug build: phase durations (shader cycles) of every workgroup overwrite the first entries of its dA row
 #define CE_STAMP(i) do { __syncthreads(); if (threadIdx.x == 0) tstamp[i] = __builtin_readcyclecounter(); } while (0)
@@ -31,21 +33,6 @@ constexpr int BGC = 16;  // column residues (always one DPP row wide)
 #define CE_STAMP(i) do { } while (0)
 #define CE_BACC(k) do { } while (0)
 #endif
-
-__host__ __device__ inline int bwd_rt_union_doubles(int n, int m, int nqs, int TI, int TJ, int BGR = 16) {
-    int a = 2 * nqs * n, b = 2 * BGR * TI + 2 * BGC * TJ, c = (NT > m ? NT : m) + m;
-    int r = a > b ? a : b;
-    return r > c ? r : c;
-}
-
-// bytes of k_backward_rt<TI, TJ, *, *, BGR>'s dynamic LDS: the carve at the top of the kernel, term by term (lda = n)
-__host__ __device__ inline size_t bwd_rt_lds_bytes(const DevT &T, int TI, int TJ, int BGR) {
-    const int n = T.n, m = T.m, nqs = imax(T.nq, 1), nwb = BGR * BGC / 64;
-    const size_t d = (size_t)m * n + 3 * (size_t)m + 2 * (size_t)n + 6 * nqs + BGR * TI + 5 /* pinfo: two 16-byte records + alignment */ + nwb * 8 +
-                     bwd_cone_scratch_doubles(T.ns, T.maxs, m, T.nep + T.np, nwb) + bwd_rt_union_doubles(n, m, nqs, TI, TJ, BGR);
-    const size_t ints = 2 * (size_t)m + 2 * nqs + BGC * TJ + BGR * TI + nwb + 1 + 8;
-    return d * 8 + ints * 4 + 16;
-}
 template <int TI, int TJ, int TH, bool PSD = false, int BGR = 16>
 __global__ void __launch_bounds__(BGR * 16, (BGR == 16 ? 3 : 2))
 k_backward_rt(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg,

@@ -1,9 +1,7 @@
 // ce_common.h -- shared device helpers of the cone engine (included inside an anonymous namespace)
 #pragma once
 
-
-constexpr int NT = 256;            // threads per workgroup
-constexpr int NW = NT / 64;        // waves per workgroup
+#include "ce_lds_common.h"    // NT, NW, SOC_SMALL, imax and the LDS doubles of the panels and the cone scratch: what the launch plan shares with the kernels
 constexpr int CONVERGED_INTERVAL = 25;
 constexpr int AA_MAX_REJECT = 10;     // safeguard rejections after which Anderson acceleration is switched off for the instance (oracle/cone_oracle.c)
 constexpr int RESCALING_MIN_ITERS = 100;
@@ -20,9 +18,7 @@ constexpr double CE_RANK_TOL = 1e-11;
 // row kinds of the adjoint kernels' classification passes (k_backward, k_backward_rt, k_backward_ns)
 enum { RK_EQ = 0, RK_FREE = 1, RK_SOCB = 2, RK_MIX = 3 };   // RK_MIX: rotated PSD row with 0 < DPi eigenvalue < 1
 
-// DevT (the device-side template description) lives in ce_types.h, shared by all translation units
-
-thread_local std::string g_err;
+// DevT (the device-side template description) lives in ce_devt.h, shared by all translation units
 
 // compile-time loop: f(std::integral_constant<int, i>{}) for i < N (anything that indexes a register array by the loop variable: a plain `#pragma unroll` of a
 // large body can silently stay rolled and put the array in scratch)
@@ -184,22 +180,6 @@ __device__ __forceinline__ void mv_rows_partial(const double *Mat, int ld, int r
         part[ch * rows + i] = a0 + a1;
     }
 }
-
-// LDS doubles of the blocked Gauss-Jordan panels (G in global memory): column panel NP16 x 17, pivot block 16 x 17
-__host__ __device__ inline size_t generic_gj_panel_doubles(int n) { const int np16 = 16 * ((n + 15) / 16); return (size_t)np16 * 17 + 16 * 17 + 2; }
-
-// LDS doubles of the blocked pivoted elimination (generic backward kernel, K in global memory): column panel nkcap x 17, two 16 x 17 blocks, pivots
-__host__ __device__ inline size_t generic_lu_panel_doubles(int nkcap) { return (size_t)nkcap * 17 + 2 * 16 * 17 + (size_t)nkcap + 2; }
-
-// LDS doubles the forward kernels add for PSD / exponential / power cones: the Jacobi scratch of psd_project (S, V, (c, s, p, q) per pair) and one root per triple
-__host__ __device__ inline size_t fwd_cone_scratch_doubles(int ns, int maxs, int ntri) { return (ns > 0 ? 2 * (size_t)maxs * maxs + 2 * (size_t)maxs + 8 : 0) + (size_t)ntri; }
-// ... and the elimination adjoints (k_backward, k_backward_rt<PSD>): eigenvectors and eigenvalues per PSD cone, the DPi eigenvalue of every row, one (X, W) pair
-// per wave plus the Jacobi scratch, the 3 x 3 eigenvector matrix of every triple
-__host__ __device__ inline size_t bwd_cone_scratch_doubles(int ns, int maxs, int m, int ntri, int nwaves) {
-    if (ns == 0 && ntri == 0) return 0;
-    return (size_t)ns * maxs * maxs + (size_t)ns * maxs + m + 2 * (size_t)nwaves * maxs * maxs + 2 * maxs + 8 + 9 * (size_t)ntri;
-}
-__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
 
 #include "ce_math.h"
 

@@ -10,6 +10,10 @@
 // that, one workgroup per instance, vectors (x | y | tau) of length l = n + m + 1 with row pitch lp; the arithmetic and the
 // order of operations are those of ce_forward_v2.h / oracle/cone_oracle.c.
 #pragma once
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_psd_jacobi.h"
+#include "ce_psd_mfma.h"
 
 // K1: one iteration's elementwise part.  PX (B x n) = p_x, QY (B x m) = A p_x.
 //   update_w  : 1 on ordinary iterations (w += alpha (u - ut)); 0 on check iterations (the check kernel finishes the iteration)

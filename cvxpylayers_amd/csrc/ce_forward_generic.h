@@ -1,19 +1,13 @@
 // ce_forward_generic.h -- size-generic LDS/L2-resident forward kernel (fallback path)
 #pragma once
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_global_mv.h"
+#include "ce_psd_jacobi.h"
+#include "ce_lds_fwd_generic.h"    // fwd_lds_bytes: the total of the carve below
 // ================================================================================================
 // FORWARD
 // ================================================================================================
-// bytes of k_forward<a_lds, g_lds>'s dynamic LDS: the carve at the top of the kernel, term by term (panel: T.gen_blocked_f, the panels of the blocked inversion)
-__host__ __device__ inline size_t fwd_lds_bytes(const DevT &T, bool a_lds, bool g_lds, bool panel = false) {
-    const int n = T.n, m = T.m, l = n + m + 1, PB = imax(NT, imax(n, m));
-    size_t d = 0;
-    if (a_lds) d += (size_t)m * T.lda;
-    if (g_lds) d += (size_t)n * T.ldg;
-    d += 2 * (size_t)m + 2 * (size_t)n + 5 * (size_t)l + imax(n, m) + 2 * (size_t)PB + NW * 8 + 2 * imax(T.nq, 1) + NW + 2 * (size_t)n;
-    d += fwd_cone_scratch_doubles(T.ns, T.maxs, T.nep + T.np) + 1;      // (+ alignment)
-    if (!g_lds && panel) d += generic_gj_panel_doubles(n) + 2;
-    return d * 8 + 16;
-}
 template <bool A_LDS, bool G_LDS>
 __global__ void __launch_bounds__(NT)
 k_forward(DevT T, ce_settings S, const double *__restrict__ Avals, const double *__restrict__ qv, long sqk, long sqb,
@@ -45,7 +39,7 @@ k_forward(DevT T, ce_settings S, const double *__restrict__ Avals, const double 
     double *wpart = p; p += NW;  // per-wave partials of phi . w
     double *sc = p; p += 2 * n;  // refactor() right-hand sides (keeps u / ut intact across a rescale)
     // PSD / exponential / power cones (the size-generic kernel serves every cone type: templates beyond the register-tiled kernels' sizes):
-    // Jacobi scratch S, V, (c, s, p, q) per pair of ce_forward_v2.h's psd_project, and the previous root of every triple (Newton warm start, ce_expcone.h)
+    // Jacobi scratch S, V, (c, s, p, q) per pair of ce_psd_jacobi.h's psd_project, and the previous root of every triple (Newton warm start, ce_expcone.h)
     double *psdS = p, *psdV = p, *psdC = p;
     if (T.ns > 0) { psdS = p; p += T.maxs * T.maxs; psdV = p; p += T.maxs * T.maxs; psdC = p; p += 2 * T.maxs + 8; }
     const int ntri = T.nep + T.np;
@@ -472,7 +466,7 @@ k_forward(DevT T, ce_settings S, const double *__restrict__ Avals, const double 
             }
             __syncthreads();
         }
-        // S8': PSD blocks (workgroup-parallel Jacobi in LDS, ce_forward_v2.h) and exponential / power triples (one thread per cone, ce_expcone.h), in place
+        // S8': PSD blocks (workgroup-parallel Jacobi in LDS, ce_psd_jacobi.h) and exponential / power triples (one thread per cone, ce_expcone.h), in place
         for (int c = 0; c < T.ns; c++) psd_project<NT>(u + n + T.soff[c], T.sord[c], psdS, psdV, psdC, red);
         if (ntri > 0) {
             for (int c = tid; c < ntri; c += NT) {

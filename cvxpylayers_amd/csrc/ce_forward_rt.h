@@ -15,37 +15,9 @@
 // (2 workgroups = 16 waves per CU).
 // Algorithm identical to ce_forward_generic.h / oracle/cone_oracle.c (same iterates up to summation order).
 #pragma once
-
-constexpr int NT2 = 512;
-constexpr int NW2 = NT2 / 64;
-constexpr int SOC_SMALL = 32;   // cones up to this size: every row thread recomputes its cone's norm (no extra barrier)
-constexpr int RT_NVEC = 14;
-constexpr int RT_EXTRA = NW2 * 8 + NW2 + 16;   // red, wpart, scalars
-
-// (dpp_mov, group_reduce, dpp_mov_rows, wave_reduce_dpp: ce_common.h)
-
-template <int K, int NWV>
-__device__ __forceinline__ void block_reduce_n(double (&v)[K], unsigned maxmask, double *red) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = ((maxmask >> k) & 1u) ? wave_reduce_dpp<true>(v[k]) : wave_reduce_dpp<false>(v[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; k++) red[wid * K + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double t[NWV];          // the waves' partial results, requested together (the plain chain waited for each of them: NWV LDS round trips in series behind the barrier)
-#pragma unroll
-        for (int w = 0; w < NWV; w++) t[w] = red[w * K + k];
-        double a = t[0];
-#pragma unroll
-        for (int w = 1; w < NWV; w++) a = ((maxmask >> k) & 1u) ? fmax(a, t[w]) : a + t[w];
-        v[k] = a;
-    }
-    __syncthreads();
-}
+#include "ce_common.h"
+#include "ce_wave_helpers.h"    // block_reduce_n
+#include "ce_lds_fwd_rt.h"      // NT2, RT_NVEC, RT_EXTRA, rt_fits: the footprint of the layout below
 
 // register tile . LDS vector, interleaved assignment: sum_k tile[k] * vec[CH*k]  (vec already offset by the lane's c)
 template <int CH, int TT>
@@ -84,17 +56,6 @@ __device__ __forceinline__ double row_dot(const double *row, const double *vec, 
     return group_reduce<CH, false>(a0 + a1);
 }
 
-// whether a template fits the tiles of k_forward_rt<CH1, T1, TG, CH2, T2, VP>; then also the leading dimension of A and the bytes of the kernel's dynamic LDS
-__host__ __device__ inline bool rt_fits(const DevT &T, int CH1, int T1, int TG, int CH2, int T2, int VP, int *lda_out, size_t *bytes) {
-    if (T.n * CH1 > NT2 || T.m * CH2 > NT2 || CH1 * T1 < T.m || CH1 * TG < T.n || CH2 * T2 < T.n) return false;
-    const int reach = imax(imax(T.n + T.m + 1, T.n + CH1 * T1), imax(imax(CH2 * T2, CH1 * TG), imax(NT2 / CH1, NT2 / CH2)));
-    if (reach > VP) return false;
-    int lda = imax((T.n + 3) & ~3, imax(CH2 * T2, CH1 * TG));
-    while (lda % 8 != 4) lda += 4;      // conflict-free interleaved row reads (ds_read_b64, groups of CH2 lanes per row)
-    *lda_out = lda;
-    *bytes = ((size_t)RT_NVEC * VP + RT_EXTRA + (size_t)T.m * lda) * 8;      // (O_A + m * lda of the layout below)
-    return true;
-}
 template <int CH1, int T1, int TG, int CH2, int T2, int VP, int WPE>
 __global__ void __launch_bounds__(NT2, WPE)
 k_forward_rt(DevT T, ce_settings S, const double *__restrict__ Avals, const double *__restrict__ qv, long sqk, long sqb,

@@ -16,62 +16,11 @@
 // Gauss-Jordan on a register tile (one barrier per pivot, pivot order k = kk + TG*cg so that register slots are static).
 // Algorithm, constants and the order of operations per iterate are those of oracle/cone_oracle.c (SCS 3 restated).
 #pragma once
-
-
-template <int CHT, int T1, int CHA, int T2, int CHG, int TG, int NWARP = 4>
-struct F2 {
-    static constexpr int MP = CHT * T1;                       // padded rows
-    static constexpr int NPa = CHA * T2, NPg = CHG * TG;
-    static constexpr int NP = NPa > NPg ? NPa : NPg;          // padded columns
-    static constexpr int VP = MP + NP + 2;                    // one (y | x | tau) vector
-    static constexpr int OY = 0, OX = MP, OT = MP + NP;
-    static constexpr int O_W = 0, O_UT = VP, O_U = 2 * VP, O_ZB = 3 * VP, O_GV = 4 * VP, O_PHI = 5 * VP;
-    static constexpr int O_BV = 6 * VP, O_DV = O_BV + MP, O_CV = O_DV + MP, O_EV = O_CV + NP, O_TV = O_EV + NP, O_PX = O_TV + NP,
-                         O_S1 = O_PX + NP, O_S2 = O_S1 + NP, O_S3 = O_S2 + NP, O_S4 = O_S3 + NP,
-                         O_RED = O_S4 + NP, O_WP = O_RED + NWARP * 8, O_SC = O_WP + NWARP, O_MT = O_SC + 16, O_G = O_MT + 20;      // O_MT: ce_math.h coefficient table
-    // S = A^T Dy A on the matrix cores: NTILE column tiles of 16, row panels of A-hat staged with pitch LDP (= 16 mod 32 doubles: the
-    // two row groups of a 32-lane LDS pass fall 128 bytes apart).  The G region holds at least one panel of 4 rows.
-    static constexpr int NTILE = (NPg + 15) / 16;
-    static constexpr int LDP = (16 * NTILE) % 32 == 16 ? 16 * NTILE : 16 * NTILE + 16;
-    static_assert(NTILE <= NWARP && LDP >= NPa, "one 16-row strip of S per wave; a panel row holds a whole row tile");
-    static_assert(T1 % 2 == 0 && T2 % 2 == 0 && TG % 2 == 0, "segments must be even for 16-byte LDS reads");
-    static_assert(CHT <= 16 && CHA <= 16 && CHG <= 16, "DPP butterflies stay inside a row of 16 lanes");
-};
-
-// The launch geometry of one variant as plain numbers, for the host's planning table (cone_engine.hip builds one per row of ce_variants.h)
-struct F2Geom { int CHT, T1, CHA, T2, CHG, TG, NTH, MP, NPa, NPg, NP, VP, O_G, LDP; };
-template <int CHT, int T1, int CHA, int T2, int CHG, int TG, int NTH>
-constexpr F2Geom f2_geom() { using L = F2<CHT, T1, CHA, T2, CHG, TG, NTH / 64>; return {CHT, T1, CHA, T2, CHG, TG, NTH, L::MP, L::NPa, L::NPg, L::NP, L::VP, L::O_G, L::LDP}; }
-// leading dimension of G in LDS: smallest even ld >= NPg for which the 16 lanes of an LDS group (CHG segments x 16/CHG rows)
-// read 16 distinct 16-byte bank groups with ds_read_b128
-__host__ __device__ inline int f2_pick_ldg(int CHG, int TG) {
-    const int NPg = CHG * TG;
-    for (int ld = NPg; ld < NPg + 64; ld += 2) {
-        bool used[16] = {false}; bool ok = true;
-        for (int lane = 0; lane < 16 && ok; lane++) {
-            const int jg = lane / CHG, cg = lane % CHG;
-            const int g = ((jg * ld + TG * cg) / 2) % 16;
-            if (used[g]) ok = false; used[g] = true;
-        }
-        if (ok) return ld;
-    }
-    return NPg;
-}
-// whether a template fits the tiles of variant g of k_fwd2; then also ldg and the bytes of the kernel's dynamic LDS without the Anderson-acceleration tail
-// (5 VP more doubles).  The carve: F2's fixed part up to O_G, the SOC row info (2 int arrays = MP doubles), the G region (k_fwd2's gsz), the PSD / triple
-// scratch, P-hat g_x (has_p: the quadratic-objective kind)
-__host__ __device__ inline bool f2_fits(const DevT &T, const F2Geom &g, bool has_p, int *ldg, size_t *bytes) {
-    if ((T.n + 2) * g.CHT > g.NTH || T.m * g.CHA > g.NTH || T.n * g.CHG > g.NTH) return false;   // two extra column groups carry phi
-    if (T.m > g.MP || T.n > g.NPa || T.n > g.NPg || T.n + T.m + 1 > g.NTH) return false;
-    if (T.maxq > SOC_SMALL && T.nq > g.NP) return false;
-    *ldg = f2_pick_ldg(g.CHG, g.TG);
-    if ((size_t)T.n * *ldg < (size_t)g.NPa) return false;
-    size_t gsz = (size_t)T.n * *ldg;                                    // G itself, one 4-row panel of the S formation, the exchange buffers of the blocked inversion
-    if (gsz < (size_t)4 * g.LDP) gsz = (size_t)4 * g.LDP;
-    if (gsz < (size_t)16 * g.NP) gsz = (size_t)16 * g.NP;
-    *bytes = ((size_t)g.O_G + g.MP + gsz + fwd_cone_scratch_doubles(T.ns, T.maxs, T.nep + T.np) + (has_p ? g.NP : 0)) * 8;
-    return true;
-}
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_wave_helpers.h"    // uniform_d, group_reduce_f, sqrt_rsqrt, block_reduce_n
+#include "ce_psd_jacobi.h"      // psd_project (PSD kind)
+#include "ce_lds_fwd2.h"        // F2<>: the fixed part of the layout; f2_fits: the footprint the launch plan uses
 
 // structural zeros of a gathered tile (index -1: the load went through a clamped index, i.e. read entry 0 of THIS instance's values): multiplied by a 0 / 1 mask.
 // The selecting form (-DF2_MASK_MUL=0) costs two v_cndmask per entry against one v_mul_f64: k_fwd2 1.526 against 1.498 ms, the step 2.18-2.22 against
@@ -85,36 +34,6 @@ __host__ __device__ inline bool f2_fits(const DevT &T, const F2Geom &g, bool has
 #else
 #define F2_SEL(ix, expr) ((ix) >= 0 ? (expr) : 0.0)
 #endif
-// a value that is equal in every lane, moved to scalar registers (frees VGPRs in the iteration loop)
-__device__ __forceinline__ double uniform_d(double v) {
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-// FP32 all-reduce inside aligned groups of CH lanes (DPP, same stages as group_reduce)
-template <int CH, bool MAX>
-__device__ __forceinline__ float group_reduce_f(float v) {
-    auto op = [](float a, float b) { return MAX ? fmaxf(a, b) : a + b; };
-    auto mov = [](float x, auto ctrl) { constexpr int CTRL = decltype(ctrl)::value; return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true)); };
-    if constexpr (CH >= 2) v = op(v, mov(v, std::integral_constant<int, 0xB1>{}));
-    if constexpr (CH >= 4) v = op(v, mov(v, std::integral_constant<int, 0x4E>{}));
-    if constexpr (CH >= 8) v = op(v, mov(v, std::integral_constant<int, 0x141>{}));
-    if constexpr (CH >= 16) v = op(v, mov(v, std::integral_constant<int, 0x140>{}));
-    return v;
-}
-
-// sqrt(q) and 1/sqrt(q) to ~1 ulp without the fp64 sqrt + divide expansions (~60 VALU ops): hardware seed (v_rsq_f64) and two
-// coupled Goldschmidt steps.  q > 0 and finite; callers guard q == 0.
-__device__ __forceinline__ void sqrt_rsqrt(double q, double &s, double &rinv) {
-    const double y = __builtin_amdgcn_rsq(q);
-    double g = q * y, h = 0.5 * y;
-    double r = fma(-h, g, 0.5);
-    g = fma(g, r, g); h = fma(h, r, h);
-    r = fma(-h, g, 0.5);
-    g = fma(g, r, g); h = fma(h, r, h);
-    s = g; rinv = 2.0 * h;
-}
-
 // blocked register tile . LDS vector (vec already offset to the lane's segment, 16-byte aligned)
 #ifndef F2_SEG_PARTS
 #define F2_SEG_PARTS 1
@@ -264,7 +183,7 @@ struct F2Co {
     }
 };
 
-// block_reduce_n (ce_forward_rt.h) with the wave index handed in as a scalar and the lane id recomputed on the spot: the
+// block_reduce_n (ce_wave_helpers.h) with the wave index handed in as a scalar and the lane id recomputed on the spot: the
 // per-wave slot address is then scalar, and no VGPR carries the thread id through the main loop for it (it used to be the
 // kernel's last spill: 4 bytes per lane written to scratch at set-up, = 4 MB of HBM writes per launch of the metric batch)
 template <int K, int NWV>
@@ -302,95 +221,6 @@ __device__ __forceinline__ void block_reduce_w(double (&v)[K], unsigned maxmask,
 #define F2_T0() do { } while (0)
 #endif
 
-// ------------------------------------------------------------------------------------------------------------------
-// PSD cone: projection of svec(S) onto the PSD cone by a workgroup-parallel cyclic Jacobi eigensolver in LDS.
-//   Sm, Vm : k x k scratch (row-major), cs : (c, s) per pair.  All NT threads take part; ends synchronised.
-// Rounds follow the round-robin tournament (k-1 rounds of k/2 DISJOINT pairs, whose rotations commute): per round one thread
-// per pair computes the rotation, then all threads apply S <- S J, V <- V J (column pass) and S <- J^T S (row pass).
-// Same rotation formulas and svec convention (lower triangle, column-major, sqrt(2) off-diagonals) as oracle/cone_oracle.c.
-// psd_jacobi: eigendecomposition only -- on return diag(Sm) holds the eigenvalues and the COLUMNS of Vm the eigenvectors.
-template <int NTH = 256>
-__device__ __forceinline__ void psd_jacobi(const double *zsvec, int k, double *Sm, double *Vm, double *cs, double *red) {
-    constexpr int NT = NTH, NW = NTH / 64;
-    const int tid = threadIdx.x;
-    const int K = (k + 1) & ~1;               // players of the tournament (a dummy if k is odd)
-    // svec -> symmetric matrix
-    for (int idx = tid; idx < k * k; idx += NT) {
-        const int i = idx / k, j = idx - i * k;
-        const int a = i >= j ? i : j, b = i >= j ? j : i;                 // lower-triangle entry (a, b), column-major packed
-        const int pos = b * k - (b * (b - 1)) / 2 + (a - b);
-        const double v = zsvec[pos];
-        Sm[idx] = (a == b) ? v : v * M_SQRT1_2;
-        Vm[idx] = (i == j) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    for (int sweep = 0; sweep < 40; sweep++) {
-        double r[2] = {0, 0};                    // off-diagonal and diagonal squared norms
-        for (int idx = tid; idx < k * k; idx += NT) { const int i = idx / k, j = idx - i * k; const double v = Sm[idx]; if (i == j) r[1] = fma(v, v, r[1]); else r[0] = fma(v, v, r[0]); }
-        block_reduce_n<2, NW>(r, 0u, red);
-        if (r[0] <= 1e-30 * (r[0] + r[1]) || r[0] == 0.0) break;          // uniform
-        for (int rd = 0; rd < K - 1; rd++) {
-            if (tid < K / 2) {
-                int p = (tid == 0) ? K - 1 : (rd + tid) % (K - 1);
-                int q = (rd + K - 1 - tid) % (K - 1);
-                if (p > q) { const int t_ = p; p = q; q = t_; }
-                double c = 1.0, sn = 0.0;
-                if (q < k) {
-                    const double apq = Sm[p * k + q];
-                    if (apq != 0.0) {
-                        const double theta = (Sm[q * k + q] - Sm[p * k + p]) / (2 * apq);
-                        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
-                        c = 1 / sqrt(t * t + 1); sn = t * c;
-                    }
-                } else { p = -1; }
-                cs[4 * tid] = c; cs[4 * tid + 1] = sn; cs[4 * tid + 2] = (double)p; cs[4 * tid + 3] = (double)q;
-            }
-            __syncthreads();
-            // column pass on S and V:  (x_p, x_q) <- (c x_p - s x_q, s x_p + c x_q) for every row
-            for (int idx = tid; idx < (K / 2) * k * 2; idx += NT) {
-                const int which = idx / ((K / 2) * k), rem = idx - which * (K / 2) * k;
-                const int pi = rem / k, row = rem - pi * k;
-                const int p = (int)cs[4 * pi + 2], q = (int)cs[4 * pi + 3];
-                if (p < 0) continue;
-                const double c = cs[4 * pi], sn = cs[4 * pi + 1];
-                double *M = which ? Vm : Sm;
-                const double a = M[row * k + p], b = M[row * k + q];
-                M[row * k + p] = c * a - sn * b; M[row * k + q] = sn * a + c * b;
-            }
-            __syncthreads();
-            // row pass on S
-            for (int idx = tid; idx < (K / 2) * k; idx += NT) {
-                const int pi = idx / k, col = idx - pi * k;
-                const int p = (int)cs[4 * pi + 2], q = (int)cs[4 * pi + 3];
-                if (p < 0) continue;
-                const double c = cs[4 * pi], sn = cs[4 * pi + 1];
-                const double a = Sm[p * k + col], b = Sm[q * k + col];
-                Sm[p * k + col] = c * a - sn * b; Sm[q * k + col] = sn * a + c * b;
-            }
-            __syncthreads();
-        }
-    }
-}
-template <int NTH = 256>
-__device__ __forceinline__ void psd_project(double *zsvec, int k, double *Sm, double *Vm, double *cs, double *red) {
-    constexpr int NT = NTH;
-    const int tid = threadIdx.x;
-    psd_jacobi<NTH>(zsvec, k, Sm, Vm, cs, red);
-    // eigenvalues -> cs (clipped at 0), then svec of V diag(w+) V^T
-    for (int i = tid; i < k; i += NT) cs[i] = fmax(Sm[i * k + i], 0.0);
-    __syncthreads();
-    for (int pos = tid; pos < k * (k + 1) / 2; pos += NT) {
-        // unpack pos -> (a, b), a >= b, column-major lower triangle
-        int b = 0, rem = pos;
-        while (rem >= k - b) { rem -= k - b; b++; }
-        const int a = b + rem;
-        double acc = 0;
-        for (int e = 0; e < k; e++) acc = fma(Vm[a * k + e] * cs[e], Vm[b * k + e], acc);
-        zsvec[pos] = (a == b) ? acc : acc * M_SQRT2;
-    }
-    __syncthreads();
-}
-
 #ifndef F2_WPS
 #define F2_WPS 3
 #endif
@@ -404,7 +234,7 @@ __device__ __forceinline__ void psd_project(double *zsvec, int k, double *Sm, do
 // the gap get their P terms.  Pvals: (B, nnzP) values in the template's P structure; idx_p: gather map of the (jg, cg) tile
 // layout of G (row jg, columns TG*cg + k), -1 = structural zero (one-triangle structures map (i,j) and (j,i) to one entry).
 // WL ("wave-local cones"): the host has ordered the rows so that no cone block straddles the rows of two waves in the (i2, c2) row
-// layout (cone_engine.hip pack_rows; nonnegative rows are the filler and count as cones of dimension 1; row_perm maps kernel rows
+// layout (ce_plan.h pack_rows; nonnegative rows are the filler and count as cones of dimension 1; row_perm maps kernel rows
 // back to the template's rows).  A row thread then exchanges its cone's values with lanes of ITS OWN wave only -- LDS is in
 // order per wave, no workgroup barrier -- which removes one of the two barriers of every equilibration pass and fuses the cone
 // projection + relaxed update into the A p_x phase: 3 barriers per iteration instead of 4.

@@ -1,6 +1,6 @@
-// ce_global_mv.h -- products with matrices resident in global memory (size-generic forward / backward kernels).  Needs the DPP helpers of
-// ce_forward_rt.h (group_reduce).
+// ce_global_mv.h -- products with matrices resident in global memory (size-generic forward / backward kernels).
 #pragma once
+#include "ce_common.h"      // group_reduce, chunks_for
 // ------------------------------------------------------------------------------------------------
 // Products with a matrix that lives in GLOBAL memory (L2 / HBM workspace; residency modes 1 and 2).  The LDS versions of
 // ce_common.h walk a row per thread (conflict-free in LDS, but 64 different cache lines per load instruction in global memory) with two

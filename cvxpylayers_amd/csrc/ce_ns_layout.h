@@ -1,5 +1,5 @@
 // ce_ns_layout.h -- the dynamic-LDS layout of k_backward_ns (ce_backward_ns.h) as data: offset and length of every segment and the footprint.  The host plans on
-// its total (cone_engine.hip plan_engine) and tests/test_ns_layout_host.py compiles it with plain g++; the kernel still carves by pointer bumping (its code is
+// its total (ce_plan.h plan_engine) and tests/test_ns_layout_host.py compiles it with plain g++; the kernel still carves by pointer bumping (its code is
 // untouched), segment for segment in the order below.  No device intrinsics; a translation unit without the HIP headers defines __host__ and __device__ away
 // before including it.
 #pragma once          // (size_t: the including translation unit has <cstddef> or the HIP headers)
@@ -110,6 +110,6 @@ __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE
     L.bytes = (size_t)ip * 4;
     return L;
 }
-// what the launch plan asks for (cone_engine.hip plan_engine)
+// what the launch plan asks for (ce_plan.h plan_engine)
 __host__ __device__ constexpr size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, true).bytes; }

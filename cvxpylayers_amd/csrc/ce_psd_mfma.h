@@ -1,9 +1,9 @@
 // ce_psd_mfma.h -- projection of a PSD block onto the cone with the dense contractions on the matrix cores
-// (v_mfma_f64_16x16x4_f64) and a WARM-STARTED Jacobi eigensolver.  Included inside an anonymous namespace after ce_forward_v2.h.
+// (v_mfma_f64_16x16x4_f64) and a WARM-STARTED Jacobi eigensolver.  Included inside an anonymous namespace.
 //
 // The ADMM iterates change little from one iteration to the next, so the eigenvectors V of the previous projection almost
 // diagonalise the new matrix S:   S' = V^T S V   (two k x k x k products, MFMA)   is nearly diagonal and the cyclic Jacobi sweeps
-// of ce_forward_v2.h (psd_jacobi) converge on it in 1-2 sweeps instead of 6-8; they keep accumulating their rotations into V, so
+// of ce_psd_jacobi.h (psd_jacobi) converge on it in 1-2 sweeps instead of 6-8; they keep accumulating their rotations into V, so
 // that S = V diag(w) V^T again, and the projection is   X = V diag(max(w, 0)) V^T   (one more MFMA product).  Callers restart
 // from V = I every check interval, which bounds the loss of orthogonality of the accumulated V.
 //
@@ -12,6 +12,10 @@
 // of column l & 15.  The matrices are tiny (k = 20: 2 x 2 tiles, 8 k-steps per tile), one tile per wave; bank conflicts of the
 // strided operand reads do not matter at this size.
 #pragma once
+#include "ce_common.h"
+#include "ce_wave_helpers.h"    // sqrt_rsqrt, block_reduce_n
+#include "ce_psd_jacobi.h"      // psd_jacobi: the cold start
+#include "ce_lds_psd_mfma.h"    // psd_refine_pitch, psd_refine_scratch_doubles, psd_mfma_kp
 
 typedef double psd_v4d __attribute__((ext_vector_type(4)));
 
@@ -61,7 +65,7 @@ __device__ __forceinline__ void psd_mfma_gemm(int KT, FA &&fa, FB &&fb, FO &&out
 }
 
 // Cyclic Jacobi sweeps on S (k x k, pitch P), rotations accumulated into the columns of V (pitch P); same tournament order and rotation
-// formulas as psd_jacobi (ce_forward_v2.h).  On return diag(S) holds the eigenvalues and the columns of V the eigenvectors.  A round is two
+// formulas as psd_jacobi (ce_psd_jacobi.h).  On return diag(S) holds the eigenvalues and the columns of V the eigenvectors.  A round is two
 // barrier-separated phases: (A) the K / 2 rotation parameters, one lane per pair; (B) the two-sided update S <- J^T S J on the (K / 2)^2
 // disjoint 2 x 2 blocks {p_a, q_a} x {p_b, q_b} together with the column rotations V <- V J.  Stop rule: off-diagonal mass below 1e-15 of the
 // total, or -- the warm-started matrix S' = V^T S V carries rounding noise of a few 1e-16 |S| per entry, so that target can sit below the
@@ -173,10 +177,6 @@ __device__ __forceinline__ void psd_gemm_kk(int k, const double *pA, int sAm, in
         for (int r = 0; r < 4; r++) { const int M = 16 * ti + lg + 4 * r; if (M < k && bn < k) out(M, bn, acc[r]); }
     }
 }
-
-__host__ __device__ inline int psd_refine_pitch(int k) { return k | 1; }                 // odd pitch: the strided operand reads spread over the banks
-// LDS doubles of the scratch shared by all blocks of an instance (S, T / E, D, R + rotation parameters + eigenvalues + lam); every block keeps k P more (V)
-__host__ __device__ inline int psd_refine_scratch_doubles(int kmax) { return 4 * kmax * psd_refine_pitch(kmax) + 4 * kmax + 16; }
 
 // phase timing: debug builds only (-DCE_PSD_TIMING; ticks are accumulated in registers and flushed once per projection -- a global atomic per phase
 // would stall the instrumented wave for longer than the phase itself).  In the product build the macro is empty: the tick registers and clock reads
@@ -423,9 +423,6 @@ __device__ __forceinline__ void psd_project_refine(double *zsvec, int k, double 
     if (stats && tid == 0) for (int q = 0; q < 6; q++) atomicAdd(&stats[8 + q], (unsigned long long)tk[q]);
 #endif
 }
-
-// LDS doubles needed: 3 * KP * (KP + 1) + 2 * k + 8  (+ the reduction scratch of block_reduce_n)
-__host__ __device__ inline int psd_mfma_kp(int k) { return 16 * ((k + 15) / 16); }
 
 // zsvec (svec of S, lower triangle column-major, sqrt(2) off-diagonals) is replaced by svec(Pi_PSD(S)).
 // Vstate: k * k doubles of global memory, the eigenvectors of the previous call (row-major), or NULL; warm != 0: start from them.

@@ -19,7 +19,12 @@
 #else
 #define LS_T(k) do { } while (0)
 #endif
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_wave_helpers.h"    // uniform_d
+#include "ce_psd_mfma.h"
 #include "ce_shared_a_ops.h"
+#include "ce_lds_sa_lsqr.h"     // sa_lsqr_lds_doubles: the total of the carve below
 
 // SaStruct, SaJvp: ce_types.h (the launcher of ce_tu_sa_lsqr.hip takes them from the host)
 
@@ -40,15 +45,6 @@ __device__ __forceinline__ void sa_spmv(const int *__restrict__ ptr, const int *
         a = group_reduce<SA_G, false>(a);
         if (i < nrows && c == 0) out(i, a);
     }
-}
-
-// LDS doubles.  nvv: rows in front of the first PSD block (v = y - s is kept for those only; PSD blocks read y - s once, at the start).
-// The partial sums of the dense-row products (2 NT doubles) share the PSD scratch matrices when the template has PSD blocks.
-// The forward derivative (FWD) runs the same bidiagonalisation on the same vectors: its footprint is this function's with lsmr = 0.
-__host__ __device__ inline size_t sa_lsqr_lds_doubles(int n, int m, int nq, int ns, int maxs, int RP, int nvv, int ntri = 0, int lsmr = 0) {
-    const int kp = ns > 0 ? psd_mfma_kp(maxs) : 0;
-    return (size_t)(RP > 0 ? 2 * RP + (ns > 0 ? 0 : 2 * NT) : 0) + (size_t)(ns > 0 ? (2 * ns + 2) * kp * (kp + 1) + 2 * kp + 8 : 0) + NW * 8 +
-           (size_t)(nvv + (nvv & 1)) + 6 * (size_t)m + 4 * (size_t)n + 5 * (size_t)(nq > 0 ? nq : 1) + 16 + 9 * (size_t)ntri + (ntri & 1) + (lsmr ? (size_t)m + n : 0);      // (LSMR: one more vector, h-bar)
 }
 
 // RP > 0: A is applied through its split into singleton rows and r <= RP dense rows (ce_shared_a_ops.h: balanced, wide loads); RP == 0: through

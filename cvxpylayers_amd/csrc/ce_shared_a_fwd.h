@@ -14,7 +14,13 @@
 // Algorithm, constants and order of operations: oracle/cone_oracle.c (SCS 3 restated) / cvxpylayers_amd/interfaces/const_a.py.
 // Cones: zero / nonnegative / second-order / PSD / exponential / 3-d power.
 #pragma once
+#include "ce_common.h"
+#include "ce_expcone.h"
+#include "ce_wave_helpers.h"    // uniform_d, block_reduce_n
+#include "ce_psd_jacobi.h"
+#include "ce_psd_mfma.h"
 #include "ce_shared_a_ops.h"
+#include "ce_lds_sa_fwd.h"      // sa_fwd_lds_doubles, sa_fwd_cidx_doubles: the totals of the carve below
 
 #ifdef CE_TIMING   // debug build: shader cycles per phase of the iteration (thread 0, accumulated in registers), written over the first entries of the instance's s row
 #define SA_T(k) do { const long long t1_ = __builtin_readcyclecounter(); sa_tacc[k] += t1_ - sa_t0; sa_t0 = t1_; } while (0)
@@ -23,17 +29,6 @@
 #endif
 
 // SaFwd: ce_types.h (the launcher of ce_tu_sa_fwd.hip takes it from the host)
-
-// LDS doubles (see the carve in the kernel)
-__host__ __device__ inline size_t sa_fwd_cidx_doubles(int n, int m, int nq, int r, int nsing) {
-    return 2 * (size_t)m + ((size_t)(n + 1 + (nsing > 0 ? nsing : 1)) + 1) / 2 + ((size_t)(nq + 1 + (r > 0 ? r : 1)) + 1) / 2 + 2;
-}
-__host__ __device__ inline size_t sa_fwd_lds_doubles(int n, int m, int nq, int ns, int maxs, int RP, int nth, int ntri = 0) {
-    const int l = n + m + 1, lp = l + (l & 1), ne = n + (n & 1), me = m + (m & 1);
-    const size_t psd = ns > 0 ? (size_t)ns * maxs * psd_refine_pitch(maxs) + psd_refine_scratch_doubles(maxs) : 0;      // V per block + shared scratch (ce_psd_mfma.h)
-    return 6 * (size_t)lp + 2 * (size_t)ne + 2 * (size_t)me + 2 * (size_t)RP * (RP + 1) + 5 * (size_t)RP + 2 * (size_t)(nq > 0 ? nq : 1) +
-           psd + (psd & 1) + 2 * nth + (nth / 64) * 8 + 32 + (size_t)(ntri + (ntri & 1));
-}
 
 // NTH threads per instance: 256 (two instances per CU when the iterates allow it) or 512 (templates whose iterates fill most of a CU's LDS
 // anyway: eight waves keep more loads of the shared matrix in flight and shorten every elementwise pass).
@@ -88,7 +83,7 @@ k_sa_fwd(DevT T, SaFwd F, ce_settings S, const double *__restrict__ BHg, const d
     }
     const double *ch = CHg + (size_t)inst * n;              // c-hat stays in global memory (read in refresh / checks only)
     const double rho_x = S.rho_x, rtau = TAU_FACTOR, alpha = S.alpha;
-    // loop-carried values that are equal in every lane live in scalar registers (uniform_d = readfirstlane, ce_forward_v2.h): the 256-thread
+    // loop-carried values that are equal in every lane live in scalar registers (uniform_d = readfirstlane, ce_wave_helpers.h): the 256-thread
     // instantiation sits at the 256-VGPR ceiling and every VGPR held across the iteration loop is one more scratch reload per iteration
     const double sigma = uniform_d(sigma_g[inst]), isg = uniform_d(1.0 / sigma);
     double scale = S.scale;

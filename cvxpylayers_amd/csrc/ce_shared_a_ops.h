@@ -3,6 +3,7 @@
 // the launch reads the same matrix); the singleton rows are a gather.  Both directions keep several wide, line-covering loads in flight
 // per lane: with one workgroup per instance the latency of the L2 stream, not its bandwidth, is what the products cost.
 #pragma once
+#include "ce_common.h"
 #ifndef SA_UR64
 #define SA_UR64 2
 #endif

@@ -1,11 +1,6 @@
 // translation unit: size-generic adjoint kernel (k_backward)
 #include "ce_tu_prologue.h"
 namespace {
-#include "ce_common.h"
-#include "ce_expcone.h"
-#include "ce_forward_rt.h"        // group_reduce / DPP helpers
-#include "ce_global_mv.h"
-#include "ce_forward_v2.h"        // (psd_jacobi: the workgroup-parallel Jacobi eigensolver shared with k_fwd2<PSD> / k_backward_rt<PSD>)
 #include "ce_backward.h"
 }  // namespace
 

@@ -3,12 +3,6 @@
 #include "ce_tu_prologue.h"
 #include "ce_variants.h"
 namespace {
-#include "ce_common.h"
-#include "ce_expcone.h"
-#include "ce_forward_rt.h"
-#include "ce_forward_v2.h"
-#include "ce_global_mv.h"
-#include "ce_backward.h"
 #include "ce_backward_rt.h"
 }  // namespace
 

@@ -2,11 +2,7 @@
 #include "ce_tu_prologue.h"
 #include "ce_variants.h"
 namespace {
-#include "ce_common.h"
-#include "ce_expcone.h"
-#include "ce_forward_rt.h"        // (first: group_reduce / DPP helpers used by the size-generic kernel's global-memory products)
-#include "ce_global_mv.h"
-#include "ce_forward_v2.h"        // (psd_project: the workgroup-parallel Jacobi projection shared with k_fwd2<PSD>)
+#include "ce_forward_rt.h"
 #include "ce_forward_generic.h"
 }  // namespace
 

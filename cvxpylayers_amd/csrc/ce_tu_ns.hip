@@ -4,7 +4,6 @@
 #include "ce_tu_prologue.h"
 #include "ce_variants.h"
 namespace {
-#include "ce_common.h"
 #include "ce_backward_ns.h"
 }  // namespace
 

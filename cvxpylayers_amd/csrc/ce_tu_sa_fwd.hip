@@ -2,11 +2,6 @@
 #include "ce_tu_prologue.h"
 #include "ce_variants.h"
 namespace {
-#include "ce_common.h"
-#include "ce_expcone.h"
-#include "ce_forward_rt.h"        // (group_reduce / DPP helpers)
-#include "ce_forward_v2.h"
-#include "ce_psd_mfma.h"
 #include "ce_shared_a_fwd.h"
 }  // namespace
 

@@ -1,5 +1,5 @@
 // ce_variants.h -- the instantiated variants of every kernel family with more than one, stated ONCE.  The launcher translation units
-// expand a list into their `switch` and their set-attribute loop; the host (cone_engine.hip) expands the same list into its planning
+// expand a list into their `switch` and their set-attribute loop; the launch plan (ce_plan.h) expands the same list into its planning
 // table.  A row's first entry is the variant index the planner, ce_get_plan and the tests' ledger name it by; for the tiled families the
 // planner takes the FIRST row that fits, so the order of the rows is part of the plan (the shared-A families are selected by value).  The trailing 0 / 1 columns say for which kinds the
 // row is instantiated: a 0 discards the launch at compile time and the planner skips the row for templates of that kind.
@@ -41,7 +41,7 @@
 
 // k_sa_fwd (ce_shared_a_fwd.h), shared-A forward:  X(index, RP, threads per workgroup, CIDX, HTRI)
 //   RP: dense rows padded;  CIDX: the template's index arrays in LDS (512 threads only);  HTRI: exponential / power triples compiled in
-//   (rows without CIDX serve every cone kind).  The host selects a row by these values (cone_engine.hip sa_fwd_select): the order is free.
+//   (rows without CIDX serve every cone kind).  The host selects a row by these values (ce_plan.h sa_fwd_select): the order is free.
 #define CE_SA_FWD_VARIANTS(X) \
     X(0, 16, 256, 0, 1) \
     X(1, 32, 256, 0, 1) \
@@ -58,7 +58,7 @@
 
 // k_sa_lsqr (ce_shared_a.h), LSQR adjoint and forward derivative:  X(index, RP, HPSD, HTRI, LSMR, FWD)
 //   RP 0: products through the CSR / CSC structure (per-instance values, or no split);  HPSD / HTRI: PSD blocks / triples compiled in;
-//   LSMR: Fong & Saunders' recurrences;  FWD: the forward derivative.  Selected by these values (cone_engine.hip sa_lsqr_select).
+//   LSMR: Fong & Saunders' recurrences;  FWD: the forward derivative.  Selected by these values (ce_plan.h sa_lsqr_select).
 //   (PSD without triples has no RP = 0 row: those calls run the general kernel.)
 #define CE_SA_LSQR_VARIANTS(X) \
     X(0, 0, 1, 1, 0, 0) \

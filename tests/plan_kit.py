@@ -3,8 +3,17 @@
 A FAMILY maps one integer (the swept size) to a template shape (n, cones, pattern); a PLAN FUNCTION maps a swept value to the plan dict of an engine created
 for that shape (create only, no solve) or None when the engine refuses the shape.  find_edges() walks the values in order and records every place where the
 plan changes: the last value before and the first value after.  dedupe() keeps one edge per (plan before, plan after) pair.  The edge logic is host-only
-(tests/test_plan_kit.py checks it on synthetic plan functions); plan_of() is the GPU side."""
+(tests/test_plan_kit.py checks it on synthetic plan functions); plan_of() is the GPU side.
+
+The plan itself makes no HIP call (csrc/ce_plan.h), so it also runs on the host: host_lib() compiles that header with g++ behind a small C shim, host_plan_of() is
+plan_of() without a GPU, and plan_grid() / run_grid() walk the grid of tests/golden/plan_table.json (tests/test_plan_host.py, tests/golden/make_plan_table.py)."""
 from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+import subprocess
+import tempfile
 
 import numpy as np
 
@@ -147,8 +156,6 @@ def all_families(ledger=False):
 
 def variant_rows(name):
     """the rows of a variant list of csrc/ce_variants.h (e.g. "CE_SA_LSQR_VARIANTS") as tuples of ints, the row index first"""
-    import os
-    import re
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cvxpylayers_amd", "csrc", "ce_variants.h")).read()
     body = re.search(r"#define " + name + r"\(X\)((?:\s*\\\n\s*X\([^)]*\))+)", hdr).group(1)
     return [tuple(int(t) for t in row.split(",")) for row in re.findall(r"X\(([^)]*)\)", body)]
@@ -168,3 +175,221 @@ def plan_of(family, v, device=None):
     p = eng.plan()
     del eng
     return p
+
+
+# ---------------------------------------------------------------------------------------------- the plan on the host (csrc/ce_plan.h compiled with g++)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the whole CePlan, then what index_csr_split / index_cones derive beside it (sp_r, sp_RP: ce_get_plan reports them; psd_first: sa_lsqr_select reads it)
+PLAN_FIELDS = ("fwd_mode", "fwd_lds", "rt_variant", "rt_lda", "f2_variant", "f2_ldg", "wl", "aa_ok", "qp_native", "f2_neumann", "gen_blocked_f", "gen_blocked_b",
+               "bwd_mode", "bwd_lds", "nkcap", "ldk", "brt_variant", "two_tile", "fast_forced", "ns_variant", "ns_lds", "qp_ns_variant", "qp_ns_lds", "sp_r", "sp_RP", "psd_first")
+SA_FWD_FIELDS = ("row", "lds", "aa_w_lds")
+SA_LSQR_FIELDS = ("row", "lds", "RP", "a_lds")
+# the create-time switches of tests/test_gpu_plan_edges.py (SWITCHES there is this list)
+SWITCHES = [{}, {"CE_FWD": "rt"}, {"CE_FWD": "generic"}, {"CE_FORCE_GENERIC": "1"}, {"CE_BWD_NS": "0"}, {"CE_GEN_BLOCKED": "0"}, {"CE_WL": "0"},
+            {"CE_FORCE_GENERIC": "1", "CE_GEN_BLOCKED": "0"}]
+# the call-time switches of the shared-A selectors that test_gpu_plan_edges.py::sa_rows_at uses, and the two others sa_lsqr_select reads
+SA_FWD_SWITCHES = [{}, {"CE_SA_NT": "512"}, {"CE_SA_NT": "512", "CE_SA_CIDX": "0"}, {"CE_SA_NT": "256"}]
+SA_LSQR_SWITCHES = [{}, {"CE_SA_LSQR_SPEC": "0"}, {"CE_SA_SPLIT": "0"}, {"CE_LSQR_A_LDS": "0"}]
+SA_DENSE_ROWS = (3, 20, 40)
+PLAN_ENV = ("CE_FWD", "CE_FORCE_GENERIC", "CE_BWD_NS", "CE_GEN_BLOCKED", "CE_WL", "CE_F2_NEUMANN", "CE_BWD_TWO_TILE", "CE_BWD_FAST_VARIANT",
+            "CE_SA_NT", "CE_SA_CIDX", "CE_SA_LSQR_SPEC", "CE_SA_SPLIT", "CE_LSQR_A_LDS", "CE_SA_LSQR_PADLDS")
+
+
+def host_build(out_dir, program=False, extra=()):
+    """compiles tests/plan_host.cpp (the shim around csrc/ce_plan.h) with g++ into out_dir: a shared object for ctypes, or (program) the stand-alone walker; its path"""
+    out = os.path.join(str(out_dir), "plan_walk" if program else "libplan_host.so")
+    mode = ["-DPLAN_WALK_MAIN", "-DENV_NAMES=" + ", ".join(f'"{e}"' for e in PLAN_ENV)] if program else ["-shared", "-fPIC"]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-D__host__=", "-D__device__=", f"-DN_PLAN_FIELDS={len(PLAN_FIELDS)}", *mode, *extra,
+                           "-I", os.path.join(ROOT, "cvxpylayers_amd", "csrc"), "-I", os.path.join(ROOT, "include"), "-o", out, os.path.join(ROOT, "tests", "plan_host.cpp")])
+    return out
+
+
+_HOST = {}
+
+
+def host_lib():
+    """the g++ build of the plan, compiled once per process into a temporary directory"""
+    if "lib" not in _HOST:
+        _HOST["dir"] = tempfile.TemporaryDirectory(prefix="plan_host_")
+        _HOST["lib"] = C.CDLL(host_build(_HOST["dir"].name))
+    return _HOST["lib"]
+
+
+def host_template(family, v):
+    """(ce_template, the arrays it points to) of the shape"""
+    from cvxpylayers_amd import _lib, problems as P
+    n, cones, pat, pstruct = shape_of(family, v)
+    tpl = P.dense_template(n, cones, pattern=pat)
+    keep = [np.ascontiguousarray(tpl.indices, dtype=np.int32), np.ascontiguousarray(tpl.indptr, dtype=np.int32), np.ascontiguousarray(cones.get("q", []), dtype=np.int32),
+            np.ascontiguousarray(cones.get("s", []), dtype=np.int32), np.ascontiguousarray(cones.get("p", []), dtype=np.float64)]
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    t = _lib.CeTemplate()
+    t.n, t.m, t.nnz_aug, t.indices, t.indptr = int(tpl.n), int(tpl.m), int(keep[1][-1]), ip(keep[0]), ip(keep[1])
+    t.z, t.l, t.nq, t.q, t.ns, t.s = int(cones.get("z", 0)), int(cones.get("l", 0)), len(keep[2]), ip(keep[2]), len(keep[3]), ip(keep[3])
+    t.nep, t.np, t.p = int(cones.get("ep", 0)), len(keep[4]), keep[4].ctypes.data_as(C.POINTER(C.c_double))
+    if pstruct is not None:
+        keep += [np.ascontiguousarray(pstruct[0], dtype=np.int32), np.ascontiguousarray(pstruct[1], dtype=np.int32)]
+        t.nnz_p, t.p_indices, t.p_indptr = int(keep[6][-1]), ip(keep[5]), ip(keep[6])
+    return t, keep
+
+
+def host_plan_of(family, v, lib=None):
+    """plan_of() without a GPU: every PLAN_FIELDS entry (ce_get_plan's create-time fields among them) from the g++ build, or None when plan_engine refuses the
+    shape.  The switches are read from the environment, as ce_create reads them."""
+    t, keep = host_template(family, v)
+    buf = (C.c_long * len(PLAN_FIELDS))()
+    return dict(zip(PLAN_FIELDS, buf)) if (lib or host_lib()).h_plan(C.byref(t), buf) == 0 else None
+
+
+def switch_key(sw):
+    return ",".join(f"{k}={v}" for k, v in sorted(sw.items()))
+
+
+def plan_grid():
+    """The grid of tests/golden/plan_table.json as commands (see tests/plan_host.cpp): every value of every family under every entry of SWITCHES -> the plan and pack_rows at the
+    three wave windows; the three shared cone sets at SA_DENSE_ROWS -> both selectors over the call kinds and their switches."""
+    cmds = []
+    for fam in all_families(ledger=True):
+        for v in family_values(fam):
+            cmds.append(("T", fam, v))
+            for sw in SWITCHES:
+                cmds += [("E", sw), ("P",)] + ([("K", W) for W in (8, 16, 32)] if not sw else [])
+    for fam in SHARED_CONE_SETS:
+        for v in SA_DENSE_ROWS:
+            for sw in SA_FWD_SWITCHES:
+                cmds += [("E", sw), ("T", fam, v)] + [("F", aa) for aa in (0, 1)]
+            for sw in SA_LSQR_SWITCHES:
+                cmds += [("E", sw), ("T", fam, v)]
+                # (a re-solve list belongs to calls with per-instance values)
+                cmds += [("L", var, per, listed, fwd) for var in (0, 1) for per in (0, 1) for listed in (0, 1) for fwd in (0, 1) if per or not listed]
+    return cmds
+
+
+def run_grid(cmds, lib=None):
+    """[(command with its template and switches, result tuple)] of every calling command, through the shared object"""
+    L = lib or host_lib()
+    buf = (C.c_long * 32)()
+    saved = {e: os.environ.pop(e, None) for e in PLAN_ENV}
+    out, cur, t, sw = [], None, None, {}
+    try:
+        for c in cmds:
+            if c[0] == "E":
+                for e in PLAN_ENV:
+                    os.environ.pop(e, None)
+                os.environ.update(c[1]); sw = c[1]
+            elif c[0] == "T":
+                if cur != c[1:]:
+                    cur, t = c[1:], host_template(*c[1:])
+            else:
+                if c[0] == "P":
+                    rc = L.h_plan(C.byref(t[0]), buf); res = (rc,) + (tuple(buf[:len(PLAN_FIELDS)]) if rc == 0 else ())
+                elif c[0] == "K":
+                    res = (L.h_pack_rows(C.byref(t[0]), c[1]),)
+                elif c[0] == "F":
+                    L.h_sa_fwd(C.byref(t[0]), c[1], buf); res = tuple(buf[:3])
+                else:
+                    L.h_sa_lsqr(C.byref(t[0]), *c[1:], buf); res = tuple(buf[:4])
+                out.append((cur + (switch_key(sw),) + c, res))
+    finally:
+        for e in PLAN_ENV:
+            os.environ.pop(e, None)
+        os.environ.update({e: v for e, v in saved.items() if v is not None})
+    return out
+
+
+def write_grid(cmds, path):
+    """the commands as the stand-alone walker reads them"""
+    with open(path, "w") as f:
+        for c in cmds:
+            if c[0] == "E":
+                f.write("E " + " ".join(f"{k}={v}" for k, v in c[1].items()) + "\n")
+            elif c[0] == "T":
+                n, cones, pat, pstruct = shape_of(*c[1:])
+                lists = [cones.get("q", []), cones.get("s", []), cones.get("p", [])]
+                f.write(f"T {n} {cones.get('z', 0)} {cones.get('l', 0)} {cones.get('ep', 0)} {int(pstruct is not None)} "
+                        + " ".join(" ".join(str(x) for x in [len(li)] + list(li)) for li in lists)
+                        + (" 0\n" if pat is None else " 1 " + "".join("1" if x else "0" for x in pat.ravel()) + "\n"))
+            else:
+                f.write(" ".join(str(x) for x in c) + "\n")
+
+
+# ---- tests/golden/plan_table.json.  Plans are kept as RUNS, the forward and the backward half of the plan apart (most switches touch one half): per family, half
+# and switch set, the ranges of the swept value over which every field of the half but its sizes is constant, with those fields once and the size fields (LDS bytes among
+# them) at the run's first and last value.  A switch set whose runs equal the default's is "=".  The other calls are few: their results column by column in the
+# grid's order, runs of equal values folded to [value, count].
+HALVES = {"fwd": (("rc", "fwd_mode", "rt_variant", "f2_variant", "f2_ldg", "wl", "aa_ok", "f2_neumann", "gen_blocked_f", "sp_RP"), ("fwd_lds", "rt_lda", "sp_r", "psd_first")),
+          "bwd": (("rc", "qp_native", "gen_blocked_b", "bwd_mode", "brt_variant", "two_tile", "fast_forced", "ns_variant", "qp_ns_variant"), ("bwd_lds", "nkcap", "ldk", "ns_lds", "qp_ns_lds"))}
+assert sorted(f for kinds, sizes in HALVES.values() for f in kinds[1:] + sizes) == sorted(PLAN_FIELDS)
+
+
+def _split(res, half):
+    """(the fields of the half that tell plans apart, its size fields) of a plan_engine result (a refused shape: its return code, zeros)"""
+    d = dict(zip(("rc",) + PLAN_FIELDS, res))
+    return [[int(d.get(f, 0)) for f in fields] for fields in HALVES[half]]
+
+
+def _fold(col):
+    out = []
+    for x in col:
+        if out and isinstance(out[-1], list) and out[-1][0] == x:
+            out[-1][1] += 1
+        elif out and out[-1] == x:
+            out[-1] = [x, 2]
+        else:
+            out.append(x)
+    return out
+
+
+def _unfold(col):
+    return [y for x in col for y in ([x[0]] * x[1] if isinstance(x, list) else [x])]
+
+
+def encode_table(results):
+    """results of run_grid -> the JSON object of the fixture"""
+    plans, cols = {}, {}
+    for (fam, v, sw, kind, *_), res in results:
+        for half in HALVES if kind == "P" else ():
+            runs = plans.setdefault(fam, {}).setdefault(half, {}).setdefault(sw, [])
+            kinds, sizes = _split(res, half)
+            if runs and runs[-1][2] == kinds:
+                runs[-1][1], runs[-1][4] = v, sizes
+            else:
+                runs.append([v, v, kinds, sizes, sizes])
+        for i, x in enumerate(res if kind != "P" else ()):
+            cols.setdefault(kind, [[] for _ in res])[i].append(int(x))
+    for by in (by for halves in plans.values() for by in halves.values()):
+        by.update({sw: "=" for sw, runs in by.items() if sw and runs == by[""]})
+    return {"fields": {**{h: {"kind": list(k), "size": list(z)} for h, (k, z) in HALVES.items()}, "K": ["packed"], "F": list(SA_FWD_FIELDS), "L": list(SA_LSQR_FIELDS)},
+            "runs": "[first value, last value, kind fields, size fields at the first value, at the last]", "plans": plans,
+            "columns": {k: [_fold(c) for c in v] for k, v in cols.items()}}
+
+
+def table_differences(results, obj):
+    """[(call, got, recorded)] where results of run_grid disagree with the fixture: the kind fields of every plan of the grid against its run, the size fields at both
+    ends of every run, every other call result by result.  Also a run or a column the grid did not reach."""
+    assert obj["fields"] == encode_table([])["fields"]
+    cols = {k: list(zip(*[_unfold(c) for c in v])) for k, v in obj["columns"].items()}
+    at, ends, diffs = {k: 0 for k in cols}, set(), []
+    for key, res in results:
+        fam, v, sw, kind = key[:4]
+        for half in HALVES if kind == "P" else ():
+            runs = obj["plans"][fam][half][sw]
+            runs = obj["plans"][fam][half][""] if runs == "=" else runs
+            i = next((i for i, r in enumerate(runs) if r[0] <= v <= r[1]), None)
+            kinds, sizes = _split(res, half)
+            if i is None or runs[i][2] != kinds:
+                diffs.append((key, half, kinds, None if i is None else runs[i][2]))
+            for end, want in ((0, 3), (1, 4)):
+                if i is not None and v == runs[i][end]:
+                    ends.add((fam, half, sw, i, end))
+                    if runs[i][want] != sizes:
+                        diffs.append((key, half, sizes, runs[i][want]))
+        if kind != "P":
+            want = cols[kind][at[kind]] if at[kind] < len(cols[kind]) else None
+            at[kind] += 1
+            if want != tuple(res):
+                diffs.append((key, tuple(res), want))
+    diffs += [((fam, half, sw, "run", i, end), None, "not reached") for fam, halves in obj["plans"].items() for half, by in halves.items() for sw, runs in by.items() if runs != "="
+              for i in range(len(runs)) for end in (0, 1) if (fam, half, sw, i, end) not in ends]
+    diffs += [((k, "calls"), at[k], len(cols[k])) for k in cols if at[k] != len(cols[k])]
+    return diffs
