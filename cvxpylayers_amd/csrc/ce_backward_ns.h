@@ -47,9 +47,19 @@
 // With no active row at all H = 0 and the reduced Hessian is P alone: regular when P is positive definite, where the linear objective flags the instance.
 // A flagged instance keeps the dropped-variable answer with status 4 (no LSQR has a P term, so no re-solve list exists behind a QP launch).
 //
-// Plain cones (zero / nonnegative / second-order).  PSD / exponential / power cones keep k_backward_rt, and so does the ADJOINT with a quadratic objective.
+// TRI = true (with FWD, REF or not, never QP): exponential and 3-d power triples beside the plain cones.  D Pi_K*(v) of a triple is W diag(lambda) W^T (ce_expcone.h
+// exp_dual_eig / pow_dual_eig, one thread per triple in the classification pass; lambda snapped to 0 / 1 within 1e-9 as k_backward_rt does, so both kernels decide
+// alike).  The triple's three rows of A are rotated in place, A_c <- W^T A_c, and gamma = W^T g_y with them: afterwards a rotated row is an ordinary equality
+// (lambda = 1, numbered with the others), a dropped row (lambda = 0, nothing in H) or ONE weighted row of the list (weight theta = lambda / (1 - lambda), theta gamma a~
+// in f), and steps 1-5 run unchanged.  The epilogue computes eta for the three rotated rows and rotates back,  dy = W lambda eta,  ds = -W (1 - lambda) eta.
+// REF: y-hat of a triple is exp_project_dual / pow_project_dual_of_entry from the cold start exp_dual_eig / pow_dual_eig evaluate at -- the same decision, the
+// rule of ns_soc_kind.  W and lambda live behind the index arrays in LDS (ns_layout's TRI mode).
+//
+// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes.  PSD cones keep k_backward_rt, and so does the ADJOINT
+// with triples or with a quadratic objective.
 #pragma once
 #include "ce_common.h"
+#include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
 
 #include "ce_ns_layout.h"          // ns_layout: the LDS segments of this kernel and its footprint (what the launch plan and tests/test_ns_layout_host.py use); bwd_ns_ldp, bwd_ns_nsl,
                                    // bwd_ns_kwmax, bwd_ns_union_doubles.  The carve below is still the kernel's own statement of the same layout.
@@ -72,20 +82,28 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
     return kind;
 }
 
-template <bool FWD, bool REF = false, bool QP = false> struct NsFwdArg { typedef NsNoJvp type; };
+// TRI: the forward derivative hands an instance with a weighted triple row of 1 - lambda below this to the re-solve (the elimination's error at the threshold, by the
+// measured law: 0.03 eps / NS_TRI_STIFF^2 = 3e-8)
+constexpr double NS_TRI_STIFF = 1e-5;
+
+template <bool FWD, bool REF = false, bool QP = false, bool TRI = false> struct NsFwdArg { typedef NsNoJvp type; };
 template <> struct NsFwdArg<true, false> { typedef NsJvp type; };
 template <> struct NsFwdArg<true, true> { typedef NsRefine type; };
 template <> struct NsFwdArg<true, false, true> { typedef NsJvpQp type; };
 template <> struct NsFwdArg<true, true, true> { typedef NsRefineQp type; };
+template <> struct NsFwdArg<true, false, false, true> { typedef NsJvpTri type; };
+template <> struct NsFwdArg<true, true, false, true> { typedef NsRefineTri type; };
 
-// (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two)
-template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false>
-__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? (QP ? 2 : 3) : 1))
+// (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
+// frames of their own, planned for two as well)
+template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false, bool TRI = false>
+__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? ((QP || TRI) ? 2 : 3) : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP>::type W) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP, "the adjoint with a quadratic objective lives in k_backward_rt");
+    static_assert((FWD && !QP) || !TRI, "exponential / power triples: the forward modes with a linear objective (their adjoint lives in k_backward_rt)");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -138,6 +156,13 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         ptv = Pm + n * n;            // per row of P: t_j = p_j . x_p
         peq = (int *)(ptv + npad);   // pivot column j -> its equality e
     }
+    const int ntri = TRI ? T.nep + T.np : 0;
+    double *Wt = nullptr, *lamt = nullptr;
+    if constexpr (TRI) {
+        ip += (ip - (int *)sm) & 1;
+        Wt = (double *)ip;           // per triple: W (row-major 3 x 3, eigenvectors in the columns) of D Pi_K*(v)
+        lamt = Wt + 9 * ntri;        // per rotated triple row: its eigenvalue after the snap
+    }
     // QP: the instance's P row through the template's dense entry map (-1: structural zero; a one-triangle entry stands for both matrix entries)
     auto load_P = [&]() {
         if constexpr (QP) {
@@ -182,6 +207,14 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             if (kind == 0) lam = 1.0;          // Pi(v) = v inside the cone, 0 inside the polar, lam (nz, z) else
             for (int i = r0 + 1 + l16; i < r1; i += 16) yh[i] = lam * vs[i];
             if (cv && l16 == 0) yh[r0] = kind == 2 ? lam * nz : lam * t0;
+        }
+        if constexpr (TRI) {          // one thread per triple, from the cold start exp_dual_eig / pow_dual_eig evaluate at: the decision of the classification pass
+            for (int c = tid; c < ntri; c += NTHR) {
+                const int r0 = T.eoff + 3 * c;
+                double w[3] = {vs[r0], vs[r0 + 1], vs[r0 + 2]};
+                if (c < T.nep) { double rs = 0.0; exp_project_dual(w, &rs); } else { double rs = -1.0; pow_project_dual_of_entry(w, T.pw[c - T.nep], &rs); }
+                yh[r0] = w[0]; yh[r0 + 1] = w[1]; yh[r0 + 2] = w[2];
+            }
         }
         }
     };
@@ -382,7 +415,42 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
         }
     }
+    if constexpr (TRI) {
+        // triples: S = D Pi_K*(v_c) = W diag(lambda) W^T, one thread per triple; lambda snapped as k_backward_rt snaps it (the same constants: both kernels
+        // decide alike).  The rows keep gamma = W^T g_y (dv); a weighted row's share of f, theta gamma, waits in tvec like the u_i of a boundary cone.
+        for (int c = tid; c < ntri; c += NTHR) {
+            const int r0 = T.eoff + 3 * c;
+            double Wl[9], th[3];
+            if (c < T.nep) exp_dual_eig(vv + r0, Wl, th); else pow_dual_eig(vv + r0, T.pw[c - T.nep], Wl, th);
+            const double h0 = dv[r0], h1 = dv[r0 + 1], h2 = dv[r0 + 2];
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                const double t = Wl[a] * h0 + Wl[3 + a] * h1 + Wl[6 + a] * h2;     // (W^T g_y)_a
+                double Bv = th[a];
+                if (Bv < 1e-9) Bv = 0.0; else if (Bv > 1.0 - 1e-9) Bv = 1.0;
+                const bool mix = Bv != 1.0 && Bv != 0.0;
+                // a weighted row that is all but an equality (1 - lambda < NS_TRI_STIFF, theta > 1e5): the reduced Hessian carries theta, the sweep has no pivot search
+                // and eta divides by 1 - lambda again -- measured on the MI355X the error of such an instance grows like 0.03 eps theta^2 (1e-1 at 1 - lambda = 3e-9,
+                // 4e-7 at 8e-7, 1e-10 at 1e-4).  The forward derivative flags it like a rank-deficient instance and the re-solve behind ce_jvp serves it; a Newton
+                // step needs no such accuracy (an inexact step still contracts, and the safeguard judges it by rho): ce_refine takes it.
+                if constexpr (!REF) { if (mix && 1 - Bv < NS_TRI_STIFF) atomicOr(&misc[2], 4); }
+                lamt[3 * c + a] = Bv; dv[r0 + a] = t; tvec[r0 + a] = mix ? Bv / (1 - Bv) * t : 0.0;
+                rkind[r0 + a] = (Bv == 1.0) ? RK_EQ : (Bv == 0.0 ? RK_FREE : RK_MIX);
+            }
+#pragma unroll
+            for (int k = 0; k < 9; k++) Wt[9 * c + k] = Wl[k];
+        }
+    }
     __syncthreads();
+    if constexpr (TRI) {          // A_c <- W^T A_c in place (read again behind the barriers of the numbering below)
+        for (int idx = tid; idx < ntri * n; idx += NTHR) {
+            const int c = idx / n, j = idx - c * n, r0 = T.eoff + 3 * c;
+            const double *Wl = Wt + 9 * c;
+            const double a0 = A[r0 * lda + j], a1 = A[(r0 + 1) * lda + j], a2 = A[(r0 + 2) * lda + j];
+#pragma unroll
+            for (int a = 0; a < 3; a++) A[(r0 + a) * lda + j] = Wl[a] * a0 + Wl[3 + a] * a1 + Wl[6 + a] * a2;
+        }
+    }
     NS_STAMP(2);
     // ---- equality numbering: ballot prefix sums (rows in order, then one e_y row per boundary cone); weighted-row list offsets
     {
@@ -418,6 +486,25 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         if (nq == 0 && tid == 0) { misc[0] = base; misc[3] = 0; }
         __syncthreads();
+        if constexpr (TRI) {
+            // the weighted rows of the triples follow the boundary cones' in the list, one lane per triple: entry, source row and weight theta at once (the rotated
+            // row is in place already); eqrow of such a row keeps its list entry for the epilogue
+            const int kw0 = misc[3];
+            __syncthreads();
+            for (int c = tid; c < ntri; c += NTHR) {
+                int kw = kw0;
+                for (int r = T.eoff; r < T.eoff + 3 * c; r++) kw += rkind[r] == RK_MIX ? 1 : 0;
+                for (int a = 0; a < 3; a++) {
+                    const int i = T.eoff + 3 * c + a;
+                    if (rkind[i] != RK_MIX) continue;
+                    const double lam = lamt[3 * c + a];
+                    wrow[kw] = (int)(A - sm) + i * lda; wsrc[kw] = i; wgt[kw] = lam / (1 - lam); eqrow[i] = kw;
+                    kw++;
+                }
+                if (c == ntri - 1) misc[3] = kw;
+            }
+            __syncthreads();
+        }
     }
     const int neq = misc[0], KW = misc[3], KW4 = (KW + 4) & ~3;          // (at least one pad entry: entry KW stands for f in the null-space transform)
     if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient / zero tangents; the LSQR launch behind this kernel serves it)
@@ -456,6 +543,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 }
                 az[c * npad + j] = (a + a1) / cinfo[5 * c + 1];
                 acc += g + g1;
+            }
+            if constexpr (TRI) {          // + theta gamma a~ of the triples' weighted rows
+                for (int i = T.eoff + part; i < m; i += 4) if (rkind[i] == RK_MIX) acc = fma(A[i * lda + j], tvec[i], acc);
             }
         }
         acc = group_reduce<4, false>(acc);
@@ -1071,6 +1161,26 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 vv[i] = fma(th, pp, zh * etay * M_SQRT1_2); dv[i] = zh * etas * M_SQRT1_2 - pp;
             }
             vv[r0] = etay * M_SQRT1_2; dv[r0] = -etas * M_SQRT1_2;
+        }
+        if constexpr (TRI) {
+            // a triple's weighted row: eta = (a~ . d_x - gamma) / (1 - lambda) with a~ . d_x from the list (tvec), so dy~ = lambda eta, ds~ = gamma - a~ . d_x; its equality
+            // and dropped rows went with the others above.  Behind the barrier one thread per triple rotates back: dy = W dy~, ds = W ds~.
+            for (int i = T.eoff + tid; i < m; i += NTHR) {
+                if (rkind[i] != RK_MIX) continue;
+                const double lam = lamt[i - T.eoff], qd = tvec[eqrow[i]] - dv[i];
+                vv[i] = lam * qd / (1 - lam); dv[i] = -qd;
+            }
+            __syncthreads();
+            for (int c = tid; c < ntri; c += NTHR) {
+                const int r0 = T.eoff + 3 * c;
+                const double *Wl = Wt + 9 * c;
+                const double y0 = vv[r0], y1 = vv[r0 + 1], y2 = vv[r0 + 2], s0 = dv[r0], s1 = dv[r0 + 1], s2 = dv[r0 + 2];
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    vv[r0 + i] = Wl[3 * i] * y0 + Wl[3 * i + 1] * y1 + Wl[3 * i + 2] * y2;
+                    dv[r0 + i] = Wl[3 * i] * s0 + Wl[3 * i + 1] * s1 + Wl[3 * i + 2] * s2;
+                }
+            }
         }
         __syncthreads();
         if constexpr (REF) {

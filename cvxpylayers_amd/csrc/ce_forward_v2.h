@@ -1019,6 +1019,12 @@ k_fwd2(DevT T, ce_settings S, const double *__restrict__ Avals, const double *__
     };
     auto slot_of = [&](int e) -> int { return (e < m) ? OY + e : (e < m + n ? OX + (e - m) : OT); };
 
+    if constexpr (PSD) {
+        // the root state of the exponential / power triples starts at 0 like k_forward's (ce_forward_generic.h troot): read uninitialised, a stale value that
+        // happened to lie inside the bracket became the first Newton start, and two solves of one instance differed in the last bits (barriers: refactor() below)
+        double *expR0 = Gm + gsz + (T.ns > 0 ? 2 * T.maxs * T.maxs + 2 * T.maxs + 8 : 0);
+        for (int c = tid; c < T.nep + T.np; c += NT) expR0[c] = 0.0;
+    }
     for (bool done = false; !done;) {
     refactor();
     if constexpr (HASP) { if (sc[7] != 0.0) { status = -4; break; } }     // SCS_FAILED: the factorisation met a non-positive pivot

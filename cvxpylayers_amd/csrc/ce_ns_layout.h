@@ -7,7 +7,8 @@
 // pitch of the sweep's row buffers: 16 mod 32 doubles (conflict-free) with at least 16 doubles of gap behind the 16 NTILE entries of a row (the gaps of the
 // eight buffer rows hold the ORIGINAL diagonal of the reduced Hessian: the rank tolerance of a pivot is relative to its own diagonal entry)
 __host__ __device__ constexpr int bwd_ns_ldp(int NTILE) { return (16 * NTILE + 16) % 32 == 16 ? 16 * NTILE + 16 : 16 * NTILE + 32; }
-__host__ __device__ constexpr int bwd_ns_kwmax(int m) { return ((m + 4) & ~3) + 4; }                                         // capacity of the weighted-row list (<= m entries + at least one pad, a multiple of 4)
+__host__ __device__ constexpr int bwd_ns_kwmax(int m) { return ((m + 4) & ~3) + 4; }                                         // capacity of the weighted-row list (<= m entries + at least one pad, a multiple of 4;
+                                                                                                                             // a triple adds at most its three rotated rows: still <= m)
 __host__ __device__ constexpr int bwd_ns_nsl(int NTILE) { return (16 * NTILE - 3 + 63) / 64; }                               // 64-lane slots that hold the columns 0 .. n (n = right-hand side)
 
 // doubles of the union region: {a_z, the row elimination's two publication buffers} | the sweep's row buffers | {q, g}   (nqs = max(nq, 1); the kernel's carve uses it)
@@ -54,13 +55,17 @@ struct NsLayout {
     NsSeg Pm;        // doubles: P, dense and symmetric (pitch n); step 2 turns its rows into p~_j = Z^T p_j in the free columns
     NsSeg ptv;       // doubles: per row of P, t_j = p_j . x_p
     NsSeg peq;       // ints: pivot column j -> its equality e
+    // ---- exponential / power triples only (TRI mode; len 0 otherwise), behind the ints rounded to 8 bytes
+    NsSeg Wt;        // doubles: per triple the eigenvectors W (row-major 3 x 3, columns) of D Pi_K*(v): the triple's rows of A are rotated by W^T in place
+    NsSeg lamt;      // doubles: per rotated triple row its eigenvalue lambda after the snap (1: equality, 0: dropped, else a weighted row)
     // ---- ints: the footprint has always counted the two alignment doubles (behind A, in front of U) whether or not the carve takes them, and the launch plan
     //      is decided on the footprint: the ones not taken stay reserved here, at the end (two ints each), and nothing uses them
     NsSeg slack;
     size_t bytes;    // the footprint: the end of the last segment
 };
 
-__host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE, int NTHR, bool qp) {
+// the modes of the layout: the plain one, the one with the dense P behind the ints (qp), and the one with the triples' segments there (ntri > 0 triples; never with qp)
+__host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE, int NTHR, bool qp, int ntri = 0) {
     const int nqs = nq > 0 ? nq : 1, npad = n + (n & 1), kw = bwd_ns_kwmax(m), nwb = NTHR / 64;
     NsLayout L{};
     int p = 0, taken = 0;          // doubles
@@ -106,6 +111,14 @@ __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE
         ip = 2 * p;
         L.peq = {ip, n}; ip += n;
     }
+    L.Wt = {0, 0}; L.lamt = {0, 0};
+    if (ntri > 0) {
+        ip += ip & 1;
+        p = ip / 2;
+        L.Wt = {p, 9 * ntri}; p += 9 * ntri;
+        L.lamt = {p, 3 * ntri}; p += 3 * ntri;
+        ip = 2 * p;
+    }
     L.slack = {ip, 2 * (2 - taken)}; ip += 2 * (2 - taken);
     L.bytes = (size_t)ip * 4;
     return L;
@@ -113,3 +126,4 @@ __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE
 // what the launch plan asks for (ce_plan.h plan_engine)
 __host__ __device__ constexpr size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, true).bytes; }
+__host__ __device__ constexpr size_t bwd_ns_tri_lds_bytes_of(int n, int m, int nq, int ntri, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, ntri).bytes; }

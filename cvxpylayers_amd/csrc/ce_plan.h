@@ -47,6 +47,7 @@ struct CePlan {
     bool two_tile = false; int fast_forced = -1;
     int ns_variant = -1; size_t ns_lds = 0;        // row of CE_NS_VARIANTS: search-free null-space adjoint (-1: not applicable)
     int qp_ns_variant = -1; size_t qp_ns_lds = 0;  // row of CE_NS_VARIANTS with the QP footprint: forward derivative and refinement of a qp_native template (-1: none)
+    int tri_ns_variant = -1; size_t tri_ns_lds = 0;      // row of CE_NS_VARIANTS with the TRI footprint: forward derivative and refinement of a template with exponential / power triples (-1: none)
 };
 
 #ifdef CE_TIMING
@@ -94,11 +95,17 @@ static size_t brt_lds_bytes(const DevT &T, int v) { return bwd_rt_lds_bytes(T, B
 static bool brt_tile_holds(const DevT &T, int v) { return T.n <= BGC * BRT_ROWS[v].TH && brt_lds_bytes(T, v) <= LDS_LIMIT; }
 static bool brt_first_tile_ok(const DevT &T, int v, int worst) { return BRT_ROWS[v].TH == BRT_ROWS[worst].TH && BRT_ROWS[v].BGR == BRT_ROWS[worst].BGR && brt_tile_holds(T, v); }
 
+// the re-solve behind ce_vjp / ce_jvp: the LSQR vectors of one instance (CSR / CSC products: per-instance values) fit LDS.  psd_first: the first row behind the
+// second-order cones (DevT::eoff when the template has no PSD block)
+static bool resolve_lds_fits(const DevT &T, int psd_first) {
+    return sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, psd_first, T.nep + T.np) * 8 <= LDS_LIMIT;
+}
 // k_backward_ns: the first row of CE_NS_VARIANTS whose tiles hold the reduced system (4 ceil(n / 4) + 1 columns) and whose layout (with P: the dense P on top) fits LDS;
 // -1: none.  *lds: its footprint
-static int ns_first_fit(const DevT &T, bool qp, size_t *lds) {
+static int ns_first_fit(const DevT &T, bool qp, size_t *lds, int ntri = 0) {      // (ntri > 0: the layout's TRI mode, the triples' W and lambda on top)
     for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
-        const size_t by = qp ? bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR) : bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
+        const size_t by = ntri > 0 ? bwd_ns_tri_lds_bytes_of(T.n, T.m, T.nq, ntri, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
+                        : qp ? bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR) : bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
         if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { *lds = by; return v; }
     }
     return -1;
@@ -248,6 +255,11 @@ static int plan_engine(const ce_template *tpl, const DevT &T, int nnz_p, const P
     // The same elimination with P inside (k_backward_ns<..., QP>): the forward derivative and the refinement of a qp_native template, planned on its own
     // footprint (the dense P on top).  ns_variant stays -1 for such a template: its adjoint keeps k_backward_rt.
     if (P.qp_native && !E.ns_off) P.qp_ns_variant = ns_first_fit(T, true, &P.qp_ns_lds);
+    // And with exponential / power triples beside the plain cones (k_backward_ns<..., TRI>): the forward derivative and the refinement, linear objective, no PSD
+    // block, planned on the TRI footprint -- when the LSQR vectors of the re-solve behind ce_jvp fit LDS too (with no PSD block, v = y - s is kept for every row in
+    // front of the triples).  ns_variant stays -1: the adjoint of such a template keeps k_backward_rt.
+    if (T.ns == 0 && T.nep + T.np > 0 && nnz_p == 0 && !E.ns_off && !E.force_generic && resolve_lds_fits(T, T.eoff))
+        P.tri_ns_variant = ns_first_fit(T, false, &P.tri_ns_lds, T.nep + T.np);
     return CE_OK;
 }
 

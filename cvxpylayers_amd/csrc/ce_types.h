@@ -68,6 +68,9 @@ struct NsQp {
 };
 struct NsJvpQp : NsJvp { NsQp Q; };
 struct NsRefineQp : NsRefine { NsQp Q; };
+// k_backward_ns<..., FWD, REF or not, QP = false, TRI = true>: the same arguments (the triples are described by DevT); types of their own select the launcher
+struct NsJvpTri : NsJvp {};
+struct NsRefineTri : NsRefine {};
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -151,6 +154,8 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQp &w);
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineQp &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpTri &w);          // (a third object: exponential / power triples)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineTri &w);
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -168,6 +173,7 @@ hipError_t ce_setattr_bwd_rt_plain(int bytes);
 hipError_t ce_setattr_bwd_rt_psd(int bytes);
 hipError_t ce_setattr_ns(int bytes);
 hipError_t ce_setattr_ns_qp(int bytes);
+hipError_t ce_setattr_ns_tri(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

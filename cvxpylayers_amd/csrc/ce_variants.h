@@ -33,7 +33,7 @@
     X(5, 5, 9, 7, 32, 0) \
     X(6, 7, 13, 7, 32, 1)
 
-// k_backward_ns (ce_backward_ns.h), plain cones only:  X(index, tiles of 16 reduced columns, threads per workgroup)
+// k_backward_ns (ce_backward_ns.h), plain cones (the forward modes of its TRI kind: exponential / power triples beside them, on the same rows):  X(index, tiles of 16 reduced columns, threads per workgroup)
 #define CE_NS_VARIANTS(X) \
     X(0, 2, 256) \
     X(1, 4, 256) \

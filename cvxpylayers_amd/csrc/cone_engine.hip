@@ -258,7 +258,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT));
     return CE_OK;
 }
 
@@ -302,6 +302,7 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
 
 int ce_adjoint_ns_variant(ce_handle h) { return h ? h->plan.ns_variant : -1; }
 int ce_qp_ns_variant(ce_handle h) { return h ? h->plan.qp_ns_variant : -1; }
+int ce_tri_ns_variant(ce_handle h) { return h ? h->plan.tri_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -452,8 +453,7 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
 // TWO lists (count | entries) in d_fix, used alternately: the LSQR launch of a call empties the list of the call before -- no memset per call.
 struct FixLists { int *cur, *oth; };
 static bool resolve_fits(const ce_engine *h) {      // the LSQR vectors of one instance (CSR / CSC products: per-instance values) fit LDS
-    const DevT &T = h->T;
-    return sa_lsqr_lds_doubles(T.n, T.m, T.nq, T.ns, T.maxs, 0, h->psd_first, T.nep + T.np) * 8 <= LDS_LIMIT;
+    return resolve_lds_fits(h->T, h->psd_first);          // (ce_plan.h: the plan of the triples' elimination asks the same question)
 }
 // part one, in front of the elimination launch: the list this call appends to and the other one; d_fix grows and is zeroed on first use for a batch size
 static int resolve_lists(ce_handle h, int B, hipStream_t st, FixLists *L) {
@@ -878,10 +878,11 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     if (qp) { rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc; }
     else {
         if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
-        if (P.ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+        if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
         if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
     }
-    const int variant = qp ? P.qp_ns_variant : P.ns_variant; const size_t lds = qp ? P.qp_ns_lds : P.ns_lds;
+    const bool tri = !qp && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, TRI> on its own footprint, the same re-solve list behind it
+    const int variant = qp ? P.qp_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant); const size_t lds = qp ? P.qp_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds);
     if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = who + ": A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -891,7 +892,8 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     CeBwdArgs ba{};
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
-    const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}}) : ce_launch_ns(variant, B, lds, st, ba, W);
+    const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
+                  : tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
     if (lrc) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
     if (!qp) {
         rc = resolve_run(h, B, fix, [&](int grid, const int *sel, int status_or, int *sel_reset) {
@@ -926,9 +928,10 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     if (qp) { const int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc; }
     else {
         if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
-        if (P.ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
+        if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
     }
-    const int variant = qp ? P.qp_ns_variant : P.ns_variant; const size_t lds = qp ? P.qp_ns_lds : P.ns_lds;
+    const bool tri = !qp && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, REF, TRI>
+    const int variant = qp ? P.qp_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant); const size_t lds = qp ? P.qp_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds);
     if (B > 1 && sA_b != T.nnz_aug) { g_err = who + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -937,7 +940,8 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
-        const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}}) : ce_launch_ns(variant, B, lds, st, ba, W);
+        const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
+                      : tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefineTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
         if (lrc) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
     }
     HIPCHK(hipGetLastError());
@@ -1054,7 +1058,7 @@ int ce_get_plan(ce_handle h, int *out, int n_out) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     const CePlan &P = h->plan;
     const int v[] = {P.fwd_mode, P.f2_variant, P.rt_variant, P.wl ? 1 : 0, P.aa_ok ? 1 : 0, h->T.gen_blocked_f, P.qp_native ? 1 : 0,
-                     P.bwd_mode, P.brt_variant, P.two_tile ? 1 : 0, P.ns_variant, h->T.gen_blocked_b, h->sp_r, h->sp_RP, h->last_fast, h->last_sa_fwd, h->last_sa_lsqr};
+                     P.bwd_mode, P.brt_variant, P.two_tile ? 1 : 0, P.ns_variant, h->T.gen_blocked_b, h->sp_r, h->sp_RP, h->last_fast, h->last_sa_fwd, h->last_sa_lsqr, P.tri_ns_variant};
     const int cnt = (int)(sizeof(v) / sizeof(v[0]));
     for (int i = 0; out && i < cnt && i < n_out; i++) out[i] = v[i];
     return cnt;

@@ -463,7 +463,7 @@ class ConeEngine:
 
     PLAN_FIELDS = ("fwd_mode", "f2_variant", "rt_variant", "wl", "aa_ok", "gen_blocked_f", "qp_native",
                    "bwd_mode", "brt_variant", "two_tile", "ns_variant", "gen_blocked_b", "sp_r", "sp_RP", "last_fast",
-                   "last_sa_fwd", "last_sa_lsqr")
+                   "last_sa_fwd", "last_sa_lsqr", "tri_ns_variant")
 
     def plan(self):
         """The whole launch plan (include/cone_engine.h ce_get_plan) as a dict keyed by PLAN_FIELDS.  Read from the library on every call, unlike

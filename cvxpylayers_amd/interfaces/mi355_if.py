@@ -197,8 +197,8 @@ class _ConeLayer(torch.autograd.Function):
                 if eng.last_path == "per_instance" and status.numel():
                     x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm)
                 if refine_info["path"] == "none" and status.numel():
-                    _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD / "
-                                              "exponential / power cones, n > 108, a shared A); the solver's point is returned "
+                    _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD "
+                                              "cones, n > 108, a shared A); the solver's point is returned "
                                               "unrefined (info['refine']['path'] == 'none')")
             eng._last_solution = (x.detach(), y.detach(), s)
             # The reference raises from forward() when an instance fails (diffcp_if.py:365-372), so the host has to learn the outcome here: one tiny

@@ -71,7 +71,7 @@ def jvp_mode(merged_args: dict) -> str:
     """How the forward-mode derivative (torch.autograd.forward_ad) solves diffcp's M d = -dQ pi on PER-INSTANCE-A templates:
     absent / "lsqr" -> diffcp's LSQR for every instance (ce_jvp_lsqr);
     "direct" -> the search-free elimination the default adjoint runs, and behind it on the device LSQR for exactly the instances it finds rank deficient
-    (ce_jvp).  Templates without that elimination (PSD / exponential / power cones, n > 108) and shared-A templates run LSQR whatever this says;
+    (ce_jvp; exponential / power triples included).  Templates without that elimination (PSD cones, n > 108) and shared-A templates run LSQR whatever this says;
     info["jvp"]["path"] tells which one ran.  A quadratic objective inside the kernels has "direct" alone (ce_jvp_qp: the elimination with P inside, no LSQR
     behind it); the default raises NotImplementedError there."""
     mode = str(merged_args.get("jvp_mode", "lsqr"))
@@ -82,8 +82,8 @@ def jvp_mode(merged_args: dict) -> str:
 
 def refine_steps(merged_args: dict) -> int:
     """Newton refinement steps behind the forward solve (ce_refine, ce_refine_qp with a quadratic objective inside the kernels: the search-free elimination on the
-    KKT residual, every step safeguarded so that the residual never grows): an integer >= 0, default 0 = none.  Templates without that elimination (PSD /
-    exponential / power cones, n > 108, shared-A paths) keep the solver's point and say so once; info["refine"]["path"] tells which."""
+    KKT residual, every step safeguarded so that the residual never grows): an integer >= 0, default 0 = none.  Templates without that elimination (PSD
+    cones, n > 108, shared-A paths) keep the solver's point and say so once; info["refine"]["path"] tells which."""
     v = merged_args.get("refine_steps", 0)
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
         raise ValueError(f"MI355 solver: refine_steps must be an integer >= 0, got {v!r}")

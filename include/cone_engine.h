@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -312,7 +312,13 @@ int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const 
  * epilogue), solved by the same kernel; behind it a fixed grid of ce_jvp_lsqr's workgroups re-solves, on the device, the instances the elimination found rank
  * deficient with diffcp's LSQR under atol / btol / conlim / iter_lim (no host round trip).  Arguments, conventions and outputs as ce_jvp_lsqr (per-instance A).
  * jvp_status[i] is ce_vjp's bit field: 0 solved directly (lsqr_iters[i] = 0); 4 | 8 = rank deficient, re-solved by LSQR (bit 0: it hit iter_lim; lsqr_iters[i] > 0).
- * CE_E_UNSUPPORTED when the template has no search-free elimination (ce_adjoint_ns_variant(h) < 0: PSD / exponential / power cones, n > 108, a quadratic
+ * Templates with exponential and / or 3-d power triples (primal and dual entries) beside zero / nonnegative / second-order cones are served by the same kernel with
+ * the triples' code (ce_tri_ns_variant(h) >= 0): a triple's D Pi is diagonalised, its three rows are rotated into that basis and join the equalities, drop out or
+ * enter the reduced Hessian as one weighted row; the re-solve list behind it is the same.  On such a template 4 | 8 has a second meaning: a REGULAR instance with a
+ * weighted triple row whose eigenvalue lies within 1e-5 of 1 (csrc/ce_backward_ns.h NS_TRI_STIFF) is listed too, because the elimination loses accuracy there (its
+ * sweep has no pivot search; error about 0.03 eps / (1 - lambda)^2), and comes back with LSQR's answer, 4 | 8 and lsqr_iters[i] > 0.  The threshold rests on that one
+ * law, measured on one shape (problems.CONFIGS["E"], 48 instances); ce_refine does not apply it (the safeguard judges its steps).
+ * CE_E_UNSUPPORTED when the template has no search-free elimination (ce_adjoint_ns_variant(h) < 0 and ce_tri_ns_variant(h) < 0: PSD cones, n > 108, a quadratic
  * objective inside the kernels) or the LSQR vectors of one instance exceed LDS: callers use ce_jvp_lsqr.
  */
 int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
@@ -336,7 +342,9 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
  * steps_taken[i]: steps kept.  resid (B, 2): rho before the first step, rho of the returned point (NaN, NaN for a skipped instance).
  * Enqueues `steps` launches on `stream` (steps = 0: none, the outputs are not written) and never synchronises the host.
  * With ce_set_profiling on, the launches are bracketed under class 1 (the adjoint's kernel family: it is that kernel), although the plugin calls this inside forward().
- * CE_E_UNSUPPORTED as ce_jvp: no search-free elimination (ce_adjoint_ns_variant(h) < 0: PSD / exponential / power cones, n > 108) or a quadratic objective
+ * Exponential / power triples as ce_jvp (ce_tri_ns_variant(h) >= 0): y^ of a triple is the engine's own projection onto the triple's dual cone, and D comes from
+ * the same evaluation.
+ * CE_E_UNSUPPORTED as ce_jvp: no search-free elimination (ce_adjoint_ns_variant(h) < 0 and ce_tri_ns_variant(h) < 0: PSD cones, n > 108) or a quadratic objective
  * inside the kernels.  CE_E_BADARG for rows that are not contiguous batch-major.
  */
 int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
@@ -365,6 +373,10 @@ int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const d
  * ce_adjoint_ns_variant's footprint, two workgroups per CU at the config-2 shape); -1: none (not qp_native, n > 108, CE_BWD_NS=0).  ce_adjoint_ns_variant stays
  * -1 for a qp_native template: its adjoint keeps the pivoting kernel. */
 int ce_qp_ns_variant(ce_handle h);
+/* >= 0: the row of CE_NS_VARIANTS that serves ce_jvp / ce_refine for a template with exponential / power triples (zero / nonnegative / second-order cones beside
+ * them, no PSD block, linear objective, n <= 108; planned on the footprint with the triples' eigenvectors and eigenvalues on top, and only when the LSQR vectors
+ * of ce_jvp's re-solve fit LDS); -1: none.  ce_adjoint_ns_variant stays -1 for such a template: its adjoint keeps the pivoting kernel. */
+int ce_tri_ns_variant(ce_handle h);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
@@ -418,6 +430,7 @@ int ce_get_launch_info(ce_handle h, int *fwd_lds_bytes, int *bwd_lds_bytes, int 
  *   15 last_sa_fwd    row of CE_SA_FWD_VARIANTS (csrc/ce_variants.h) the last ce_solve_shared_a call launched (-1: none yet)
  *   16 last_sa_lsqr   row of CE_SA_LSQR_VARIANTS the last k_sa_lsqr launch ran: ce_vjp_shared_a, ce_vjp_lsqr, ce_jvp_shared_a, ce_jvp_lsqr, or the re-solve behind
  *                     ce_vjp / ce_jvp (-1: none yet)
+ *   17 tri_ns_variant as ce_tri_ns_variant
  * The plan is fixed by ce_create (environment switches included), except the last_* entries: the shared-A kernels read their switches at the call. */
 int ce_get_plan(ce_handle h, int *out, int n_out);
 
