@@ -138,6 +138,25 @@ struct CeSaLsqrArgs {
     SaJvp W;
 };
 
+// ---- optimal value and its envelope-theorem derivatives (ce_value.h): products and sums over the template's structure, no plan ----
+// k_value<JVP>: x [B][n], y [B][m]; the structure's row / column of every entry and the b entry of every row (engine-owned), the P structure (caller-owned)
+struct CeValueArgs {
+    int B, n, m, nnz_aug, nnz_p;
+    const int *rowidx, *colidx, *bpos, *prow, *pcol;
+    const double *x, *y;
+    const double *A; long sAk, sAb; const double *q; long sqk, sqb; const double *P;      // JVP = false: the values (A: the b entries alone are read)
+    double *pobj, *dobj;
+    const double *tA; long stAb; const double *tq; long stqk, stqb; const double *tP;     // JVP = true: the tangents (each may be null: zero)
+    double *tval;
+};
+// k_value_vjp_rows / k_value_vjp_tile: g [B] upstream cotangent, skip [B] bytes or null; every output may be null (not wanted)
+struct CeValueVjpArgs {
+    int B, n, m, nnz_aug, nnz_p;
+    const int *rowidx, *colidx, *prow, *pcol;
+    const double *x, *y, *g; const unsigned char *skip;
+    double *dA; long sdAk, sdAb; double *dq; long sdqk, sdqb; double *dP;
+};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -163,6 +182,13 @@ int ce_launch_sa_lsqr(int variant, int grid, size_t lds, hipStream_t st, const C
 // k_sa_fill_split (ce_shared_a_ops.h; its arguments in the kernel's order): refills the split's A_d^T (zeroed by the caller) and singleton values from this call's A
 void ce_launch_sa_fill_split(hipStream_t st, int nnzA, int RP, const int *rowidx, const int *colidx, const int *rowslot, const double *vals, double *AdT, double *srow_val,
                              const int *sing_i, double *sing_v);
+// ce_tu_value.hip: one workgroup per instance / per VAL_IPB instances / per (64-instance tile, chunk of kchunk entries); the LDS sizes are the host's (value_lds_*)
+void ce_launch_value(bool jvp, size_t lds, hipStream_t st, const CeValueArgs &a);
+void ce_launch_value_vjp_rows(size_t lds, hipStream_t st, const CeValueVjpArgs &a);
+void ce_launch_value_vjp_tile(bool staged, int chunks, int kchunk, int wdq, size_t lds, hipStream_t st, const CeValueVjpArgs &a);
+size_t ce_value_lds(int n, int m);               // k_value
+size_t ce_value_vjp_rows_lds(int n, int m);      // k_value_vjp_rows
+size_t ce_value_vjp_tile_lds(int n, int m);      // k_value_vjp_tile<STAGED = true>
 // raise the dynamic-LDS limit of every kernel of the family
 hipError_t ce_setattr_fwd2_plain(int bytes);
 hipError_t ce_setattr_fwd2_psd(int bytes);
@@ -177,3 +203,4 @@ hipError_t ce_setattr_ns_tri(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);
+hipError_t ce_setattr_value(int bytes);

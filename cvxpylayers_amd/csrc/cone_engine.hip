@@ -240,6 +240,7 @@ static void build_gather_maps(const ce_template *tpl, const ce_engine &h, Gather
     }
 }
 
+static constexpr size_t VALUE_LDS_MAX = LDS_LIMIT - 1024;      // dynamic LDS of the kernels of ce_value.h (they also hold a few static bytes: the workgroup votes)
 static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &X, const GatherMaps &G) {
     DevT &T = h.T;
     HIPCHK(h.d_pw.upload(tpl->p, tpl->np));
@@ -259,6 +260,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
     HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX));
     return CE_OK;
 }
 
@@ -701,6 +703,83 @@ int ce_transpose(ce_handle h, int rows, int cols, const double *in, double *out,
     {
         ProfScope ps(h, 2, st);
         launch_transpose(st, in, out, rows, cols);
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+
+// ---- optimal value and its envelope-theorem derivatives (ce_value.h): launches under profiling class 2 (no system is solved: not the adjoint's family)
+static int value_check_p(const void *vals, const int *p_rows, const int *p_cols, int nnz_p, bool need_vals) {
+    if (nnz_p < 0 || (nnz_p > 0 && (!p_rows || !p_cols || (need_vals && !vals)))) { g_err = "quadratic objective: nnz_p > 0 needs the values and p_rows, p_cols (device arrays)"; return CE_E_BADARG; }
+    return CE_OK;
+}
+static int value_launch(ce_handle h, bool jvp, CeValueArgs &a, const int *p_rows, const int *p_cols, int nnz_p, void *stream) {
+    const DevT &T = h->T;
+    a.n = T.n; a.m = T.m; a.nnz_aug = T.nnz_aug; a.nnz_p = nnz_p;
+    a.rowidx = h->d_rowidx.get(); a.colidx = h->d_colidx.get(); a.bpos = h->d_bpos.get(); a.prow = p_rows; a.pcol = p_cols;
+    const size_t lds = ce_value_lds(T.n, T.m);
+    if (lds > VALUE_LDS_MAX) { g_err = "ce_value: x and y of one instance exceed LDS"; return CE_E_TOO_LARGE; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(h, 2, st);
+        ce_launch_value(jvp, lds, st, a);
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+int ce_value(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+             const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p, const double *x, const double *y, double *pobj, double *dobj, void *stream) {
+    if (!h || B <= 0 || !A_vals || !q_vals || !x || !y || !pobj || !dobj) { g_err = "null argument"; return CE_E_BADARG; }
+    const int rc = value_check_p(P_vals, p_rows, p_cols, nnz_p, true);
+    if (rc) return rc;
+    CeValueArgs a{};
+    a.B = B; a.x = x; a.y = y; a.A = A_vals; a.sAk = sA_k; a.sAb = sA_b; a.q = q_vals; a.sqk = sq_k; a.sqb = sq_b; a.P = P_vals; a.pobj = pobj; a.dobj = dobj;
+    return value_launch(h, false, a, p_rows, p_cols, nnz_p, stream);
+}
+int ce_value_jvp(ce_handle h, int B, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                 const double *tP_vals, const int *p_rows, const int *p_cols, int nnz_p, const double *x, const double *y, double *tval, void *stream) {
+    if (!h || B <= 0 || !x || !y || !tval) { g_err = "null argument"; return CE_E_BADARG; }
+    const int rc = value_check_p(tP_vals, p_rows, p_cols, tP_vals ? nnz_p : 0, false);
+    if (rc) return rc;
+    if (tA_vals_bm && B > 1 && stA_b < h->T.nnz_aug) { g_err = "ce_value_jvp: tA_vals_bm must be batch-major rows at least nnz_aug apart"; return CE_E_BADARG; }
+    CeValueArgs a{};
+    a.B = B; a.x = x; a.y = y; a.tA = tA_vals_bm; a.stAb = stA_b; a.tq = tq_vals; a.stqk = stq_k; a.stqb = stq_b; a.tP = tP_vals; a.tval = tval;
+    return value_launch(h, true, a, p_rows, p_cols, tP_vals ? nnz_p : 0, stream);
+}
+int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const double *g, const unsigned char *skip,
+                 double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
+                 double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream) {
+    if (!h || B <= 0 || !x || !y || !g) { g_err = "null argument"; return CE_E_BADARG; }
+    int rc = value_check_p(dP_vals, p_rows, p_cols, dP_vals ? nnz_p : 0, false);
+    if (rc) return rc;
+    const DevT &T = h->T;
+    const int K = T.nnz_aug;
+    const bool rows = dA_vals && sdA_k == 1 && (sdA_b >= K || B == 1), tile = dA_vals && !rows && sdA_b == 1 && sdA_k >= B;
+    if (dA_vals && !rows && !tile) { g_err = "dA_vals must be batch-minor (sdA_k >= B, sdA_b = 1) or batch-major (sdA_k = 1, sdA_b >= nnz_aug)"; return CE_E_BADARG; }
+    CeValueVjpArgs a{};
+    a.B = B; a.n = T.n; a.m = T.m; a.nnz_aug = K; a.nnz_p = dP_vals ? nnz_p : 0;
+    a.rowidx = h->d_rowidx.get(); a.colidx = h->d_colidx.get(); a.prow = p_rows; a.pcol = p_cols;
+    a.x = x; a.y = y; a.g = g; a.skip = skip;
+    a.dA = dA_vals; a.sdAk = sdA_k; a.sdAb = sdA_b; a.dq = dq_vals; a.sdqk = sdq_k; a.sdqb = sdq_b; a.dP = dP_vals;
+    const size_t lds_rows = ce_value_vjp_rows_lds(T.n, T.m), lds_tile = ce_value_vjp_tile_lds(T.n, T.m);
+    if (lds_rows > VALUE_LDS_MAX) { g_err = "ce_value_vjp: x and y of four instances exceed LDS"; return CE_E_TOO_LARGE; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(h, 2, st);
+        const bool tile_dq = tile && dq_vals && sdq_b == 1;      // (the tile kernel stores dq coalesced in that layout)
+        if (tile) {
+            // chunks of entries per tile: enough workgroups to fill the device at small tile counts, never below 256 entries (each workgroup stages its tile again)
+            const int tiles = (B + 63) / 64;
+            const int chunks = std::max(1, std::min((1024 + tiles - 1) / tiles, (K + 255) / 256));
+            const int kchunk = (K + chunks - 1) / chunks;
+            ce_launch_value_vjp_tile(lds_tile <= VALUE_LDS_MAX, chunks, kchunk, tile_dq ? 1 : 0, lds_tile, st, a);
+        }
+        CeValueVjpArgs r = a;
+        if (tile) r.dA = nullptr;
+        if (tile_dq) r.dq = nullptr;
+        if (r.dA || r.dq || r.dP) ce_launch_value_vjp_rows(lds_rows, st, r);
     }
     HIPCHK(hipGetLastError());
     return CE_OK;

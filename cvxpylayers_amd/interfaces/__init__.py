@@ -1,6 +1,9 @@
 """Solver-plugin registry, mirroring cvxpylayers/interfaces/__init__.py:13-101 for the one key this
 repository provides.  "MI355" canonicalises exactly like "DIFFCP" (CSC structure of [A_cvx | b_cvx],
-interfaces/__init__.py:26-33) so both see identical (A, b, c, cones)."""
+interfaces/__init__.py:26-33) so both see identical (A, b, c, cones).
+
+`optimal_value` (optimal_value.py) is this repository's own addition behind the plugin: the optimal value of a solved layer as a differentiable output."""
+from cvxpylayers_amd.interfaces.optimal_value import optimal_value  # noqa: F401  (re-exported)
 
 
 def get_solver_ctx(solver, param_prob, cone_dims, data, kwargs, verbose=False):

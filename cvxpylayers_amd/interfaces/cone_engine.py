@@ -444,6 +444,64 @@ class ConeEngine:
         _lib.check(rc, name)
         return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns"}
 
+    # ---- the optimal value and its envelope-theorem derivatives (include/cone_engine.h ce_value ...): streaming passes, no system solved
+    @staticmethod
+    def _p_args(p_structure):
+        """(p_rows, p_cols) int32 device tensors or None -> (rows pointer, cols pointer, nnz_p) as the C ABI takes the P structure"""
+        if p_structure is None or p_structure[0].numel() == 0:
+            return None, None, 0
+        return p_structure[0].data_ptr(), p_structure[1].data_ptr(), int(p_structure[0].numel())
+
+    def value(self, A_eval, q_eval, x, y, P_bm=None, p_structure=None):
+        """pobj, dobj (B,) of the point (x (B, n), y (B, m)): c^T x + d + 1/2 x^T P x and -b^T y - 1/2 x^T P x + d.  A_eval (nnz_aug, B), q_eval (n+1, B) fp64 on
+        this engine's device in ANY strides (nothing is copied); P_bm (B, nnz_p) contiguous with p_structure = (p_rows, p_cols) int32 device tensors."""
+        B = x.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        pobj, dobj = torch.empty((B,), **f64), torch.empty((B,), **f64)
+        if B == 0:
+            return pobj, dobj
+        pr, pc, nnz_p = self._p_args(p_structure if P_bm is not None else None)
+        rc = _lib.lib().ce_value(self._h, B, A_eval.data_ptr(), A_eval.stride(0), A_eval.stride(1), q_eval.data_ptr(), q_eval.stride(0), q_eval.stride(1),
+                                 P_bm.data_ptr() if nnz_p else None, pr, pc, nnz_p, x.data_ptr(), y.data_ptr(), pobj.data_ptr(), dobj.data_ptr(), self._stream())
+        _lib.check(rc, "ce_value")
+        return pobj, dobj
+
+    def value_jvp(self, x, y, tA_bm=None, tq=None, tP_bm=None, p_structure=None):
+        """The tangent (B,) of the optimal value for tangents tA_bm (B, nnz_aug) batch-major rows, tq (n+1, B) in any strides, tP_bm (B, nnz_p); None = zero."""
+        B = x.shape[0]
+        tval = torch.empty((B,), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return tval
+        pr, pc, nnz_p = self._p_args(p_structure if tP_bm is not None else None)
+        tqd, tq_args = self._q_args(tq)
+        rc = _lib.lib().ce_value_jvp(self._h, B, tA_bm.data_ptr() if tA_bm is not None else None, tA_bm.stride(0) if tA_bm is not None else 0, *tq_args,
+                                     tP_bm.data_ptr() if nnz_p else None, pr, pc, nnz_p, x.data_ptr(), y.data_ptr(), tval.data_ptr(), self._stream())
+        _lib.check(rc, "ce_value_jvp")
+        return tval
+
+    def value_vjp(self, x, y, g, skip=None, want=(True, True, True), batch_minor_A: bool = False, batch_minor_q: bool = True, p_structure=None):
+        """dA (nnz_aug, B), dq (n+1, B), dP (B, nnz_p) of the optimal value for the cotangent g (B,); want = (dA, dq, dP): the others come back None.
+        batch_minor_A / batch_minor_q: the tensor is (., B) contiguous; otherwise the transposed view of a batch-major buffer (the engine-native layout).
+        skip (B,) bool / uint8 or None: those instances get exact zeros."""
+        B = x.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        pr, pc, nnz_p = self._p_args(p_structure if want[2] else None)
+        dA = dq = dP = None
+        sA = sq = (0, 0)
+        if want[0]:
+            dA, sA = (torch.empty((self.nnz_aug, B), **f64), (B, 1)) if batch_minor_A else (torch.empty((B, self.nnz_aug), **f64).t(), (1, self.nnz_aug))
+        if want[1]:
+            dq, sq = (torch.empty((self.n + 1, B), **f64), (B, 1)) if batch_minor_q else (torch.empty((B, self.n + 1), **f64).t(), (1, self.n + 1))
+        if nnz_p:
+            dP = torch.empty((B, nnz_p), **f64)
+        if B == 0 or (dA is None and dq is None and dP is None):
+            return dA, dq, dP
+        sk = skip.view(torch.uint8) if (skip is not None and skip.dtype == torch.bool) else skip
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = _lib.lib().ce_value_vjp(self._h, B, x.data_ptr(), y.data_ptr(), g.data_ptr(), ptr(sk), ptr(dA), *sA, ptr(dq), *sq, ptr(dP), pr, pc, nnz_p, self._stream())
+        _lib.check(rc, "ce_value_vjp")
+        return dA, dq, dP
+
     # introspection (bench / tests)
     def set_profiling(self, on):
         """False / True, or a sum of 2 (forward), 4 (adjoint), 8 (layout passes): which launches are bracketed by HIP events (include/cone_engine.h)"""

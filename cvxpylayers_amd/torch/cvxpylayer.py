@@ -34,7 +34,7 @@ import scipy.sparse as sp
 import torch
 
 from cvxpylayers_amd import _lib
-from cvxpylayers_amd.interfaces import get_solver_ctx, get_torch_cvxpylayer
+from cvxpylayers_amd.interfaces import get_solver_ctx, get_torch_cvxpylayer, optimal_value
 
 
 @dataclass
@@ -69,6 +69,7 @@ class CanonTemplate:
     P_structure: Any = None        # (indices, indptr, (n, n)) CSC structure of P (param_prob.reduced_P.problem_data_index)
     gp: bool = False
     gp_log_mask: tuple | None = None
+    objective_sign: int = 1        # -1: the problem was a Maximize (the canonical program minimises the negated objective); forward(return_value=True) returns objective_sign * p*
 
     @property
     def n_params_total(self) -> int:
@@ -91,7 +92,7 @@ class CanonTemplate:
         sc = ctx.solver_ctx
         return CanonTemplate([tuple(p.shape) for p in parameters], col_offsets, ctx.reduced_A.reduced_mat.tocsr(), ctx.q.tocsr(),
                              (sc.A_structure[0], sc.A_structure[1], sc.A_shape), dict(sc.dims) if isinstance(sc.dims, dict) else sc.dims,
-                             rec, gp=gp, gp_log_mask=ctx.gp_log_mask)
+                             rec, gp=gp, gp_log_mask=ctx.gp_log_mask, objective_sign=-1 if type(problem.objective).__name__ == "Maximize" else 1)
 
 
 def _reshape_fortran(x: torch.Tensor, shape: tuple) -> torch.Tensor:
@@ -321,6 +322,8 @@ class CvxpyLayer(torch.nn.Module):
         solver = solver or "MI355"
         if solver != "MI355":
             raise RuntimeError("Unknown solver. Check if your solver is supported by CVXPYlayers")
+        if template.objective_sign not in (1, -1):
+            raise ValueError(f"CanonTemplate.objective_sign must be 1 or -1, got {template.objective_sign!r}")
         self.template = template
         self.solver = solver
         opts = dict(solver_args or {})
@@ -413,7 +416,12 @@ class CvxpyLayer(torch.nn.Module):
             p[:, off:off + flat.shape[1]] = flat
         return p
 
-    def forward(self, *params: torch.Tensor, solver_args: dict | None = None, warm_start: bool = False):
+    def forward(self, *params: torch.Tensor, solver_args: dict | None = None, warm_start: bool = False, return_value: bool = False):
+        """return_value=True appends the optimal value of the problem as the LAST output: (B,) float64, or () when no parameter is batched; its gradients are the
+        envelope theorem's (interfaces/optimal_value.py: no adjoint system is solved for them).  gp=True layers return exp(value) (the log-problem's objective is the
+        log of the original's), Maximize problems the maximum (template.objective_sign).  info["objective"] holds the canonical program's primal and dual objective."""
+        if not isinstance(return_value, bool):
+            raise TypeError(f"return_value must be a bool, got {type(return_value).__name__}")
         solver_args = solver_args or {}
         batch = self.validate_params(list(params))
         if self.template.gp and self.template.gp_log_mask is not None:
@@ -436,9 +444,20 @@ class CvxpyLayer(torch.nn.Module):
         # the same cache for its MOREAU plugin, torch/cvxpylayer.py:464-487)
         primal, dual, info, _ = layer_cls.apply(P_eval, q_eval, A_eval, self.ctx, solver_args, needs_grad, True if warm_start else None)
         self.info = info
-        if self.fused_recovery:
-            return self._recover_results(primal, dual, batch)
-        return self._recover_results_torch(primal, dual, batch)
+        out = self._recover_results(primal, dual, batch) if self.fused_recovery else self._recover_results_torch(primal, dual, batch)
+        if return_value:
+            out = out + (self._value(P_eval, q_eval, A_eval, primal, dual, info, solver_args),)
+        return out
+
+    def _value(self, P_eval, q_eval, A_eval, primal, dual, info, solver_args):
+        """the optimal value behind the plugin call (see forward): masked instances of a raise_on_error=False call are NaN and contribute no gradient"""
+        merged = {**self.ctx.solver_ctx.options, **solver_args}
+        status = info.get("status") if isinstance(info, dict) else None
+        failed = (status < 0) if (not bool(merged.get("raise_on_error", True)) and status is not None and status.numel()) else None
+        val = optimal_value(P_eval, q_eval, A_eval, primal, dual, self.ctx, failed=failed, info=info if isinstance(info, dict) else None)
+        if self.template.objective_sign == -1:
+            val = -val
+        return torch.exp(val) if self.template.gp else val
 
     def _recover_results(self, primal, dual, batch):
         """torch/cvxpylayer.py:225-282 as one map launch per source (see _RecoverMap)."""

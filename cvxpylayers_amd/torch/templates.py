@@ -21,7 +21,9 @@ def template_from_affine_builder(builder: Callable, param_shapes: Sequence[tuple
                                  var_recover: Sequence[VariableRecovery], col_order: Sequence[int] | None = None) -> CanonTemplate:
     """builder(*param_arrays) -> (A (m,n), b (m,), c (n,)) in SOLVER form (A x + s = b), affine in the parameters; a fourth
     return value P (n,n) (symmetric, affine in the parameters) adds the quadratic objective 1/2 x^T P x: its upper triangle becomes
-    the template's P structure / P_map (what plugins in SUPPORTS_QUAD_OBJ receive as P_eval).
+    the template's P structure / P_map (what plugins in SUPPORTS_QUAD_OBJ receive as P_eval).  An optional FIFTH return value d (a scalar, affine in the
+    parameters; the fourth may then be None: linear objective) is the objective's constant: row n of q_map, which the canonical vector q_eval = [c, d] carries
+    and only the optimal value reads.  Builders that return three or four values behave exactly as before (row n of q_map stays empty).
 
     Parameters are flattened in Fortran order (torch/cvxpylayer.py:40-55).  `col_order[i]` = position of user parameter i in
     the canonical parameter vector (CVXPY orders columns by parameter id, not by user order; utils/parse_args.py:330-385);
@@ -43,10 +45,13 @@ def template_from_affine_builder(builder: Callable, param_shapes: Sequence[tuple
         args = [pvec[offs[i]:offs[i] + sizes[i]].reshape(param_shapes[i], order="F") for i in range(npar)]
         out = builder(*args)
         A, b, c = out[:3]
+        if len(out) > 4:          # (A, b, c, P or None, d)
+            Pm = np.asarray(out[3], float) if out[3] is not None else None
+            return np.asarray(A, float), np.asarray(b, float), np.append(np.asarray(c, float), float(out[4])), Pm
         Pm = np.asarray(out[3], float) if len(out) > 3 else None
         return np.asarray(A, float), np.asarray(b, float), np.asarray(c, float), Pm
 
-    A0, b0, c0, P0 = evaluate(np.zeros(ptot))
+    A0, b0, c0, P0 = evaluate(np.zeros(ptot))          # (c0 has n + 1 entries when the builder returns the constant d: the rows of q_map below)
     m, n = A0.shape
     assert m == cone_rows(cones), "cone dims do not add up to the number of rows"
     dA, db, dc, dP = [], [], [], []

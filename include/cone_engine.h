@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -378,6 +378,39 @@ int ce_qp_ns_variant(ce_handle h);
  * of ce_jvp's re-solve fit LDS); -1: none.  ce_adjoint_ns_variant stays -1 for such a template: its adjoint keeps the pivoting kernel. */
 int ce_tri_ns_variant(ce_handle h);
 
+/*
+ * THE OPTIMAL VALUE and its derivatives by the envelope theorem.  No reference call site: the reference's layers return the minimiser and the duals, and users
+ * rebuild the value from x in torch and back-propagate through the adjoint (diffcp_if.py:385-403).  At a solution (x, y) of
+ *        min c^T x + d + 1/2 x^T P x   s.t.  A x + s = b, s in K                (A = -A_vals, b = A_vals[b entries], c = q_vals[:n], d = q_vals[n])
+ * the value p* = c^T x + d + 1/2 x^T P x has the PARTIAL derivatives of the Lagrangian as its total derivatives:  dp/dA = y x^T, dp/db = -y, dp/dc = x,
+ * dp/dd = 1, dp/dP = 1/2 x x^T.  No linear system is solved (nothing can be rank deficient), every cone kind and every path of the engine is served, and the
+ * cost is one streaming pass.  In the boundary convention A_eval = [-A.data, b]:  dp/dA_eval[k] = -y_row x_col for an A entry, -y_row for a b entry.
+ * The A structure comes from the handle; the P STRUCTURE IS PASSED EXPLICITLY: p_rows, p_cols [nnz_p] DEVICE int arrays, row and column of every entry (NULL / 0:
+ * linear objective), so that the same entry points serve a handle with P inside the kernels and the epigraph form, whose engine is built on the augmented
+ * template and does not know the original P.  A structure with every entry on or above (or on or below) the diagonal is read as one triangle: an off-diagonal
+ * entry counts twice, in the value and in dP (ce_vjp_qp's convention); entries out of range count as zero.  P_vals, tP_vals, dP_vals: (B, nnz_p) batch-major.
+ * x [B][n], y [B][m] contiguous; the calls enqueue only, never synchronise the host and need no retained forward state.  With ce_set_profiling on the launches are
+ * bracketed under class 2 (streaming passes), never class 1: they are not the adjoint's kernels.
+ *   ce_value     : pobj[i] = c^T x + d + 1/2 x^T P x,  dobj[i] = -b^T y - 1/2 x^T P x + d  (equal at a solution; A_vals / q_vals with strides as ce_solve, only the
+ *                  b entries of A_vals are read).  The sums run in a fixed order: an instance's result depends neither on B nor on its position in the batch.
+ *   ce_value_jvp : tval[i] = tc^T x + td + 1/2 x^T tP x - sum_k tA_eval[k] (y_row x_col | y_row): the tangent of p* for tangents in the boundary convention,
+ *                  tA_vals_bm (B, nnz_aug) batch-major rows stA_b apart, tq_vals at [k * stq_k + i * stq_b] (ALL n + 1 entries count: d is the last), tP_vals;
+ *                  a NULL tangent is zero.  Same fixed order.
+ *   ce_value_vjp : for an upstream cotangent g [B]:  dA_vals (k, i) at [k*sdA_k + i*sdA_b] = -g_i y[i, row_k] x[i, col_k] (A entry) / -g_i y[i, row_k] (b entry);
+ *                  dq_vals (j, i) at [j*sdq_k + i*sdq_b] = g_i x[i, j], (n, i) = g_i;  dP_vals[i, k] = g_i (1/2 | 1) x_row x_col.  Each output may be NULL (not
+ *                  wanted).  dA: batch-major (sdA_k = 1, sdA_b >= nnz_aug; one workgroup per four instances, lanes over the entries) or batch-minor (sdA_b = 1,
+ *                  sdA_k >= B; tiles of 64 instances, lanes over the instances): both store whole 512-byte runs and neither needs a ce_transpose behind it.
+ *                  skip [B] bytes or NULL: an instance with skip[i] != 0 gets exact zeros in every output, whatever its x, y, g hold (NaN included).
+ * CE_E_TOO_LARGE when x and y of one (ce_value) / four (ce_value_vjp) instances exceed LDS.
+ */
+int ce_value(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+             const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p, const double *x, const double *y, double *pobj, double *dobj, void *stream);
+int ce_value_jvp(ce_handle h, int B, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                 const double *tP_vals, const int *p_rows, const int *p_cols, int nnz_p, const double *x, const double *y, double *tval, void *stream);
+int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const double *g, const unsigned char *skip,
+                 double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
+                 double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream);
+
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
  * on, every ce_solve also records the order "instances by iteration count, largest first" (one tiny kernel behind the solve) and the NEXT ce_solve of the
@@ -401,7 +434,7 @@ int ce_adjoint_ns_variant(ce_handle h);
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
 int ce_set_profiling(ce_handle h, int enable);
-/* which: 0 forward kernel, 1 backward kernel, 2 layout (transpose) kernels.  Returns the mean ms per launch
+/* which: 0 forward kernel, 1 backward kernel, 2 layout (transpose) kernels and the streaming passes of ce_value / ce_value_jvp / ce_value_vjp.  Returns the mean ms per launch
  * since the last ce_reset_profile and the launch count; synchronises the recorded events. */
 int ce_get_profile(ce_handle h, int which, double *mean_ms, int *launches);
 int ce_reset_profile(ce_handle h);
