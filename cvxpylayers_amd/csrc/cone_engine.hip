@@ -57,6 +57,9 @@ namespace {
         }                                                                            \
     } while (0)
 
+// ce_last_error for the entry points that live in a translation unit of their own (ce_tu_cone_proj.hip): g_err has internal linkage
+void ce_set_last_error(const std::string &msg) { g_err = msg; }
+
 // Device memory of the engine: move-only, freed with its owner.  reserve() only ever grows the buffer and does not keep its contents.
 template <class T>
 class DevBuf {

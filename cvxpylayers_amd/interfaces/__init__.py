@@ -2,8 +2,19 @@
 repository provides.  "MI355" canonicalises exactly like "DIFFCP" (CSC structure of [A_cvx | b_cvx],
 interfaces/__init__.py:26-33) so both see identical (A, b, c, cones).
 
-`optimal_value` (optimal_value.py) is this repository's own addition behind the plugin: the optimal value of a solved layer as a differentiable output."""
+`optimal_value` (optimal_value.py) is this repository's own addition behind the plugin: the optimal value of a solved layer as a differentiable output.
+`project`, `ConeProjection`, `svec`, `smat`, `project_psd` (cvxpylayers_amd/cones.py) are the differentiable cone projections underneath every kernel."""
 from cvxpylayers_amd.interfaces.optimal_value import optimal_value  # noqa: F401  (re-exported)
+
+_CONES = ("project", "ConeProjection", "svec", "smat", "project_psd")
+
+
+def __getattr__(name):
+    # re-exported lazily: cvxpylayers_amd.cones itself imports this package's cone_set
+    if name in _CONES:
+        from cvxpylayers_amd import cones
+        return getattr(cones, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def get_solver_ctx(solver, param_prob, cone_dims, data, kwargs, verbose=False):

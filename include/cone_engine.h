@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -466,6 +466,31 @@ int ce_get_launch_info(ce_handle h, int *fwd_lds_bytes, int *bwd_lds_bytes, int 
  *   17 tri_ns_variant as ce_tri_ns_variant
  * The plan is fixed by ce_create (environment switches included), except the last_* entries: the shared-A kernels read their switches at the call. */
 int ce_get_plan(ce_handle h, int *out, int n_out);
+
+/* ---- The projection onto a product of cones and its derivative as an operation of its own (diffcp's cones.pi / cones.dpi) ----
+ * A projection needs no template matrix, so it has a light handle of its own: the cone layout (offsets, orders, exponents), uploaded once.  Rows in the solver's
+ * order z, l, q, s, ep, p; PSD blocks as svec (lower triangle, column-major, sqrt(2) off-diagonals); a negative power-cone entry -a is the dual cone of exponent a.
+ *   ce_cones_create   : validates on the host and checks the LDS footprint of every PSD order BEFORE any HIP call: CE_E_TOO_LARGE for an order above 82
+ *                       (csrc/ce_lds_cone_proj.h; ce_last_error names the order and the bound), CE_E_BADARG for a malformed description.
+ *   ce_cones_rows     : m, the rows of the set.
+ *   ce_cones_state_len: doubles of derivative state per instance: k^2 + k per PSD block (eigenvectors, unclipped eigenvalues) + 9 per exponential / power triple
+ *                       (its Jacobian).  Zero / nonnegative / second-order cones keep none.
+ *   ce_cone_project   : out = Pi_K(v), or Pi_K*(v) for dual != 0 (the zero cone projects to 0, its dual is free; every other dual is the true dual cone).  v and out
+ *                       are (B, m) with row pitches ld_v, ld_out >= m in elements; out must not alias v.  state (B, ce_cones_state_len) or NULL: not wanted, nothing
+ *                       of the derivative is then computed.  A non-finite entry makes the rows of ITS cone NaN and touches nothing else.
+ *   ce_cone_dproject  : out = D Pi(v) dir for the same v, dual, and the state that call wrote (may be NULL when ce_cones_state_len is 0).  D Pi is symmetric for
+ *                       every kind, so this one call is both the forward- and the reverse-mode derivative.  Conventions at kinks: a nonnegative row at exactly 0 has
+ *                       factor 1/2; a second-order cone is the identity on the cone's boundary and 0 on the polar's; PSD divided differences are 1 for two positive
+ *                       eigenvalues, 0 for two non-positive ones.
+ * One launch per cone kind present (rows and second-order cones share one); the calls only enqueue. */
+typedef struct ce_cones *ce_cones_handle;
+int ce_cones_create(int z, int l, int nq, const int *q, int ns, const int *s, int nep, int np, const double *p, int device, ce_cones_handle *out);
+int ce_cones_destroy(ce_cones_handle h);
+int ce_cones_rows(ce_cones_handle h);
+long ce_cones_state_len(ce_cones_handle h);
+int ce_cone_project(ce_cones_handle h, int B, const double *v, long ld_v, int dual, double *out, long ld_out, double *state, void *stream);
+int ce_cone_dproject(ce_cones_handle h, int B, const double *v, long ld_v, int dual, const double *state, const double *dir, long ld_dir,
+                     double *out, long ld_out, void *stream);
 
 #ifdef __cplusplus
 }
