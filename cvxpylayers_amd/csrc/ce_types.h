@@ -157,6 +157,25 @@ struct CeValueVjpArgs {
     double *dA; long sdAk, sdAb; double *dq; long sdqk, sdqb; double *dP;
 };
 
+// ---- LPGD backward (ce_lpgd.h): the perturbed data of one side, and the differenced envelope gradients of two points; no plan ----
+// k_lpgd_perturb: x, dx [B][n], dy [B][m] or null; A [B] rows sAb apart, q and q_out under one stride pair; P, P_out [B][nnz_p]; every output but q_out and
+// flags may be null (not written)
+struct CeLpgdPerturbArgs {
+    int B, n, m, nnz_aug, nnz_p;
+    const int *rowidx, *colidx, *bpos, *prow, *pcol;
+    const double *x, *dx, *dy;
+    const double *A; long sAb; const double *q; long sqk, sqb; const double *P;
+    double tau, rho;
+    double *q_out, *A_out, *P_out; int *flags;
+};
+// k_lpgd_grad_rows / k_lpgd_grad_tile: the points (xa, ya), (xb, yb), the divisor delta, skip [B] bytes or null; outputs as CeValueVjpArgs
+struct CeLpgdGradArgs {
+    int B, n, m, nnz_aug, nnz_p;
+    const int *rowidx, *colidx, *prow, *pcol;
+    const double *xa, *ya, *xb, *yb; double delta; const unsigned char *skip;
+    double *dA; long sdAk, sdAb; double *dq; long sdqk, sdqb; double *dP;
+};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -189,6 +208,12 @@ void ce_launch_value_vjp_tile(bool staged, int chunks, int kchunk, int wdq, size
 size_t ce_value_lds(int n, int m);               // k_value
 size_t ce_value_vjp_rows_lds(int n, int m);      // k_value_vjp_rows
 size_t ce_value_vjp_tile_lds(int n, int m);      // k_value_vjp_tile<STAGED = true>
+// ce_tu_lpgd.hip: one workgroup per VAL_IPB instances (perturb, grad_rows) / per (64-instance tile, chunk of kchunk entries)
+void ce_launch_lpgd_perturb(hipStream_t st, const CeLpgdPerturbArgs &a);
+void ce_launch_lpgd_grad_rows(size_t lds, hipStream_t st, const CeLpgdGradArgs &a);
+void ce_launch_lpgd_grad_tile(bool staged, int chunks, int kchunk, int wdq, size_t lds, hipStream_t st, const CeLpgdGradArgs &a);
+size_t ce_lpgd_grad_rows_lds(int n, int m);      // k_lpgd_grad_rows
+size_t ce_lpgd_grad_tile_lds(int n, int m);      // k_lpgd_grad_tile<STAGED = true>
 // raise the dynamic-LDS limit of every kernel of the family
 hipError_t ce_setattr_fwd2_plain(int bytes);
 hipError_t ce_setattr_fwd2_psd(int bytes);
@@ -204,3 +229,4 @@ hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);
 hipError_t ce_setattr_value(int bytes);
+hipError_t ce_setattr_lpgd(int bytes);

@@ -98,6 +98,7 @@ struct ce_engine {
     DevBuf<double> wsdA;         // batch-major dA              [B][nnz_aug]
     DevBuf<double> gws;          // global residency fallback
     const double *retained_A = nullptr; int retained_B = 0;
+    bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
     DevBuf<int> d_idx_at, d_idx_ar, d_idx_b;       // k_fwd2: gather maps of the two register tiles of A and of b
     DevBuf<int> d_csc_ptr, d_csr_ptr, d_csr_col, d_csr_src;   // sparse structure of the A part (shared-A kernels)
@@ -263,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
     HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX));
+    HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX));
     return CE_OK;
 }
 
@@ -387,9 +388,11 @@ int ce_solve_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, 
     if (!ce_acceleration_available(h)) S.acceleration_lookback = 0;          // k_fwd2 (when its vectors fit LDS) and the size-generic kernel implement it
     if (S.acceleration_interval <= 0) S.acceleration_interval = 10;
     const double *Abm = nullptr;
+    const bool transient = h->transient_solve;          // a solve issued from a backward pass (LPGD): no trace on the handle
+    if (transient && !(sA_k == 1 && sA_b == h->T.nnz_aug)) { g_err = "transient solve: A_vals must be batch-major (the layout workspace may hold the retained forward inputs)"; return CE_E_BADARG; }
     int rc = to_batch_major(h, B, A_vals, sA_k, sA_b, st, &Abm);
     if (rc) return rc;
-    h->retained_A = Abm; h->retained_B = B;
+    if (!transient) { h->retained_A = Abm; h->retained_B = B; }
     const DevT &T = h->T;
     double *gA = nullptr, *gG = nullptr;
     if (P.fwd_mode == FWD_GEN_G_GLOBAL || P.fwd_mode == FWD_GEN_GLOBAL) {
@@ -411,12 +414,12 @@ int ce_solve_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, 
         fa.T = T; fa.S = S; fa.Abm = Abm; fa.q = q_vals; fa.sqk = sq_k; fa.sqb = sq_b; fa.idx_at = h->d_idx_at.get(); fa.idx_ar = h->d_idx_ar.get(); fa.idx_b = h->d_idx_b.get();
         fa.x = x; fa.y = y; fa.s = s; fa.iters = iters; fa.status = status; fa.resid = resid; fa.P = P_vals; fa.nnz_p = h->nnz_p; fa.idx_p = h->d_idx_p.get(); fa.gA = gA; fa.gG = gG;
         int lrc;
-        if (h->dispatch_history && P.fwd_mode == FWD_V2) {
+        if (h->dispatch_history && !transient && P.fwd_mode == FWD_V2) {
             rc = flush_dispatch_order(h, st, nullptr, nullptr); if (rc) return rc;          // (a solve whose status was never summarised: the order is still owed)
             HIPCHK(h->d_iters2.reserve(B));
             fa.iters2 = h->d_iters2.get(); fa_iters2 = true;
         }
-        fa.order = (h->dispatch_history && h->order_B == B && P.fwd_mode == FWD_V2) ? h->d_order.get() : nullptr;
+        fa.order = (h->dispatch_history && !transient && h->order_B == B && P.fwd_mode == FWD_V2) ? h->d_order.get() : nullptr;
         if (P.fwd_mode == FWD_V2) {
             fa.T.ldg = P.f2_ldg;
             if (P.wl) {      // rows packed for the wave-local cone exchange: the kernel sees the cone layout in ITS row order
@@ -783,6 +786,78 @@ int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const dou
         if (tile) r.dA = nullptr;
         if (tile_dq) r.dq = nullptr;
         if (r.dA || r.dq || r.dP) ce_launch_value_vjp_rows(lds_rows, st, r);
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+
+// ---- LPGD backward (ce_lpgd.h): the perturbed data of one side and the differenced envelope gradients; streaming passes under profiling class 2
+int ce_set_transient_solve(ce_handle h, int on) {
+    if (!h) { g_err = "null argument"; return CE_E_BADARG; }
+    h->transient_solve = on != 0;
+    return CE_OK;
+}
+int ce_lpgd_perturb(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p,
+                    const double *x, const double *dx, const double *dy, double tau, double rho,
+                    double *q_out, double *A_out_bm, double *P_out, int *flags, void *stream) {
+    if (!h || B <= 0 || !q_vals || !x || !dx || !q_out || !flags) { g_err = "null argument"; return CE_E_BADARG; }
+    if (!(tau != 0.0) || !(rho >= 0.0)) { g_err = "ce_lpgd_perturb: tau must be nonzero and rho >= 0"; return CE_E_BADARG; }
+    const DevT &T = h->T;
+    if (dy && (!A_vals_bm || !A_out_bm || (B > 1 && sA_b < T.nnz_aug))) { g_err = "ce_lpgd_perturb: dy needs A_vals_bm (batch-major rows at least nnz_aug apart) and A_out_bm"; return CE_E_BADARG; }
+    const bool wP = P_out && nnz_p > 0 && rho != 0.0;
+    const int rc = value_check_p(P_vals, p_rows, p_cols, wP ? nnz_p : 0, true);
+    if (rc) return rc;
+    CeLpgdPerturbArgs a{};
+    a.B = B; a.n = T.n; a.m = T.m; a.nnz_aug = T.nnz_aug; a.nnz_p = wP ? nnz_p : 0;
+    a.rowidx = h->d_rowidx.get(); a.colidx = h->d_colidx.get(); a.bpos = h->d_bpos.get(); a.prow = p_rows; a.pcol = p_cols;
+    a.x = x; a.dx = dx; a.dy = dy; a.A = A_vals_bm; a.sAb = sA_b; a.q = q_vals; a.sqk = sq_k; a.sqb = sq_b; a.P = P_vals; a.tau = tau; a.rho = rho;
+    a.q_out = q_out; a.A_out = dy ? A_out_bm : nullptr; a.P_out = wP ? P_out : nullptr; a.flags = flags;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(h, 2, st);
+        ce_launch_lpgd_perturb(st, a);
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+int ce_lpgd_grad(ce_handle h, int B, const double *x_a, const double *y_a, const double *x_b, const double *y_b, double delta, const unsigned char *skip,
+                 double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
+                 double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream) {
+    if (!h || B <= 0 || !x_a || !y_a || !x_b || !y_b) { g_err = "null argument"; return CE_E_BADARG; }
+    if (!(delta != 0.0)) { g_err = "ce_lpgd_grad: delta must be nonzero"; return CE_E_BADARG; }
+    int rc = value_check_p(dP_vals, p_rows, p_cols, dP_vals ? nnz_p : 0, false);
+    if (rc) return rc;
+    const DevT &T = h->T;
+    const int K = T.nnz_aug;
+    const bool rows = dA_vals && sdA_k == 1 && (sdA_b >= K || B == 1), tile = dA_vals && !rows && sdA_b == 1 && sdA_k >= B;
+    if (dA_vals && !rows && !tile) { g_err = "dA_vals must be batch-minor (sdA_k >= B, sdA_b = 1) or batch-major (sdA_k = 1, sdA_b >= nnz_aug)"; return CE_E_BADARG; }
+    CeLpgdGradArgs a{};
+    a.B = B; a.n = T.n; a.m = T.m; a.nnz_aug = K; a.nnz_p = dP_vals ? nnz_p : 0;
+    a.rowidx = h->d_rowidx.get(); a.colidx = h->d_colidx.get(); a.prow = p_rows; a.pcol = p_cols;
+    a.xa = x_a; a.ya = y_a; a.xb = x_b; a.yb = y_b; a.delta = delta; a.skip = skip;
+    a.dA = dA_vals; a.sdAk = sdA_k; a.sdAb = sdA_b; a.dq = dq_vals; a.sdqk = sdq_k; a.sdqb = sdq_b; a.dP = dP_vals;
+    const size_t lds_rows = ce_lpgd_grad_rows_lds(T.n, T.m), lds_tile = ce_lpgd_grad_tile_lds(T.n, T.m);
+    if (lds_rows > VALUE_LDS_MAX) { g_err = "ce_lpgd_grad: the points of four instances exceed LDS"; return CE_E_TOO_LARGE; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(h, 2, st);
+        const bool tile_dq = tile && dq_vals && sdq_b == 1;      // (the tile kernel stores dq coalesced in that layout)
+        if (tile) {
+            // chunks of entries per tile.  Every chunk workgroup stages its tile's four vectors again, and a staged tile fills most of a CU's LDS (one workgroup
+            // per CU at the metric shape): about one workgroup per CU and at least 1024 entries behind each staging pass (ce_value_vjp's rule -- 1024 workgroups,
+            // at least 256 entries each -- staged four times as often here; DESIGN.md section 3.11 has both measurements)
+            const int tiles = (B + 63) / 64;
+            const int chunks = std::max(1, std::min((256 + tiles - 1) / tiles, (K + 1023) / 1024));
+            const int kchunk = (K + chunks - 1) / chunks;
+            ce_launch_lpgd_grad_tile(lds_tile <= VALUE_LDS_MAX, chunks, kchunk, tile_dq ? 1 : 0, lds_tile, st, a);
+        }
+        CeLpgdGradArgs r = a;
+        if (tile) r.dA = nullptr;
+        if (tile_dq) r.dq = nullptr;
+        if (r.dA || r.dq || r.dP) ce_launch_lpgd_grad_rows(lds_rows, st, r);
     }
     HIPCHK(hipGetLastError());
     return CE_OK;

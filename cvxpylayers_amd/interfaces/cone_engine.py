@@ -120,9 +120,11 @@ class ConeEngine:
         _lib.check(_lib.lib().ce_transpose(self._h, K, B, A_eval.data_ptr(), out.data_ptr(), self._stream()), "ce_transpose")
         return out
 
-    def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None):
+    def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None):
         """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
-        warm = (x, y, s) of shapes (B, n), (B, m), (B, m): initial point (instances with non-finite entries start cold)."""
+        warm = (x, y, s) of shapes (B, n), (B, m), (B, m): initial point (instances with non-finite entries start cold).
+        path: None -- the dispatcher decides (per instance / shared A); "const_a" or "per_instance": the path a caller already knows (solve_transient: the
+        perturbed solves of a backward follow their forward's path without comparing values again)."""
         B = A_bm.shape[0]
         dev = self.device
         if B == 0:        # empty batch: nothing to launch (the C ABI refuses B <= 0)
@@ -139,7 +141,7 @@ class ConeEngine:
         # direct engine users (tests, probes): vjp() without q_eval may use the objective of the most recent solve() -- but only for the SAME value buffer
         # (the plugin always passes q_eval explicitly; a q paired with another call's A would silently change the full adjoint system: ADVICE round 5)
         self._last_q, self._last_q_key = q_eval.detach(), (A_bm.data_ptr(), B)
-        if P_bm is None and self._use_const_a(A_bm):
+        if P_bm is None and (path == "const_a" if path is not None else self._use_const_a(A_bm)):
             from cvxpylayers_amd.interfaces.const_a import solve_const_a
             self.last_path = "const_a"
             return solve_const_a(self, A_bm, q_eval, settings, warm=warm)      # (notes itself whether its kernel honours the acceleration)
@@ -166,6 +168,70 @@ class ConeEngine:
                                      iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
         _lib.check(rc, "ce_solve")
         return x, y, s, iters, status, resid
+
+    # what solve() records on the engine about "the most recent solve" (introspection, _recent_q, the one-time acceleration warning)
+    # (_aa_warned is NOT among them: the once-per-engine acceleration warning stays said when a perturbed solve was the one to say it)
+    _SOLVE_TRACE = ("last_path", "last_acceleration", "last_const_a_kernel", "_last_q", "_last_q_key")
+
+    def solve_transient(self, A_bm, q_eval, settings, warm=None, P_bm=None, path: str | None = None):
+        """solve() that leaves no trace: the handle keeps the retained inputs and the dispatch history of the last ordinary solve (ce_set_transient_solve),
+        this object the attributes of _SOLVE_TRACE; _last_solution and the mailbox are not touched by solve() in the first place.  For solves issued from a
+        backward pass (interfaces/lpgd.py): a later forward or adjoint of another node sees what it would have seen without them.  A_bm must be contiguous."""
+        keep = {k: getattr(self, k) for k in self._SOLVE_TRACE}
+        L = _lib.lib()
+        _lib.check(L.ce_set_transient_solve(self._h, 1), "ce_set_transient_solve")
+        try:
+            return self.solve(A_bm, q_eval, settings, warm=warm, P_bm=P_bm, path=path)
+        finally:
+            L.ce_set_transient_solve(self._h, 0)
+            for k, v in keep.items():
+                setattr(self, k, v)
+
+    def p_structure_dev(self):
+        """(p_rows, p_cols) of this engine's P structure as int32 device tensors in the value order of ce_create (CSC), built once; None without a structure"""
+        if not self.nnz_p:
+            return None
+        if getattr(self, "_p_dev", None) is None:
+            cols = np.repeat(np.arange(self.n, dtype=np.int32), np.diff(self._p_ptr))
+            self._p_dev = (torch.from_numpy(self._p_idx.copy()).to(self.device), torch.from_numpy(np.ascontiguousarray(cols, dtype=np.int32)).to(self.device))
+        return self._p_dev
+
+    def lpgd_perturb(self, A_bm, q_eval, x, dx, dy, tau: float, rho: float, P_bm=None, p_structure=None):
+        """The data of the program perturbed by (tau, rho) at the point x with cotangents dx (B, n), dy (B, m) or None (include/cone_engine.h ce_lpgd_perturb).
+        Returns q_t (q_eval's shape and strides), A_t (B, nnz_aug) or None when dy is None (solve on A_bm itself), P_t (B, nnz_p) or None when no P_bm is given
+        or rho == 0 (use P_bm itself), flags (B,) int32 (bit 0: all-zero cotangent, bit 1: a dy entry without a b slot was dropped).  Enqueues only."""
+        B = x.shape[0]
+        if B == 0:          # empty batch: nothing to launch (the C ABI refuses B <= 0)
+            return (torch.empty_like(q_eval), A_bm.new_empty((0, self.nnz_aug)) if dy is not None else None, None, torch.empty((0,), dtype=torch.int32, device=self.device))
+        q_t = torch.empty_strided(tuple(q_eval.shape), tuple(q_eval.stride()), dtype=torch.float64, device=self.device)
+        A_t = torch.empty((B, self.nnz_aug), dtype=torch.float64, device=self.device) if dy is not None else None
+        pr, pc, nnz_p = self._p_args(p_structure if (P_bm is not None and rho != 0.0) else None)
+        P_t = torch.empty((B, nnz_p), dtype=torch.float64, device=self.device) if nnz_p else None
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = _lib.lib().ce_lpgd_perturb(self._h, B, ptr(A_bm) if dy is not None else None, A_bm.stride(0) if dy is not None else 0,
+                                        q_eval.data_ptr(), q_eval.stride(0), q_eval.stride(1), ptr(P_bm) if nnz_p else None, pr, pc, nnz_p,
+                                        x.data_ptr(), dx.data_ptr(), ptr(dy), float(tau), float(rho), q_t.data_ptr(), ptr(A_t), ptr(P_t), flags.data_ptr(), self._stream())
+        _lib.check(rc, "ce_lpgd_perturb")
+        return q_t, A_t, P_t, flags
+
+    def lpgd_grad(self, xa, ya, xb, yb, delta: float, skip=None, batch_minor_A: bool = False, p_structure=None):
+        """[G(xb, yb) - G(xa, ya)] / delta with G the envelope gradients of value_vjp (ce_lpgd_grad): dA (nnz_aug, B), dq (n+1, B), dP (B, nnz_p) or None.
+        batch_minor_A: dA is (nnz_aug, B) contiguous; otherwise the transposed view of a batch-major buffer.  skip (B,) bool / uint8: exact zeros there."""
+        B = xa.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        pr, pc, nnz_p = self._p_args(p_structure)
+        dA, sA = (torch.empty((self.nnz_aug, B), **f64), (B, 1)) if batch_minor_A else (torch.empty((B, self.nnz_aug), **f64).t(), (1, self.nnz_aug))
+        dq = torch.empty((self.n + 1, B), **f64)
+        dP = torch.empty((B, nnz_p), **f64) if nnz_p else None
+        if B == 0:
+            return dA, dq, dP
+        sk = skip.view(torch.uint8) if (skip is not None and skip.dtype == torch.bool) else skip
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        rc = _lib.lib().ce_lpgd_grad(self._h, B, xa.data_ptr(), ya.data_ptr(), xb.data_ptr(), yb.data_ptr(), float(delta), ptr(sk),
+                                     dA.data_ptr(), *sA, dq.data_ptr(), B, 1, ptr(dP), pr, pc, nnz_p, self._stream())
+        _lib.check(rc, "ce_lpgd_grad")
+        return dA, dq, dP
 
     def _recent_q(self, A_bm):
         return self._last_q if (self._last_q is not None and self._last_q_key == (A_bm.data_ptr(), A_bm.shape[0])) else None

@@ -9,7 +9,7 @@ csrc/libcone_engine.so through the C ABI in include/cone_engine.h.  No CPU fallb
 Not thread-safe (engines are created lazily and cached on MI355_ctx), like moreau_if.py:14-15.
 
 This module holds the context (MI355_ctx) and the autograd function; its parts live next to it and are re-exported here:
-solver_args.py (which solver_args exist and what they mean), cone_engine.py (ConeEngine: the ce_handle wrapper), outcome_mailbox.py
+solver_args.py (which solver_args exist and what they mean), lpgd.py (the LPGD backward: gradients from perturbed re-solves), cone_engine.py (ConeEngine: the ce_handle wrapper), outcome_mailbox.py
 (OutcomeMailbox: how forward outcomes and adjoint flags reach the host), quad_epigraph.py (QuadEpigraph), const_a.py (shared-A paths).
 """
 from __future__ import annotations
@@ -21,11 +21,13 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
+from cvxpylayers_amd import _lib
 from cvxpylayers_amd.interfaces.cone_engine import ConeEngine
+from cvxpylayers_amd.interfaces.lpgd import lpgd_backward
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lsqr_rule, make_settings, note_ignored_args, refine_steps, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, note_ignored_args, refine_steps, unpack_rule)
 
 
 class MI355_ctx:
@@ -146,6 +148,9 @@ class _Saved(NamedTuple):
     lsqr: tuple                             # lsqr_rule() of this call
     q_eval: Optional[torch.Tensor]          # (n+1, B) objective values (linear objective only: ce_jvp_qp and ce_vjp_qp take none)
     jvp_mode: str = "lsqr"                  # jvp_mode() of this call
+    ce_settings: Optional[object] = None    # a copy of the ce_settings of this call: the perturbed solves of an LPGD backward run under the same eps, max_iters, acceleration ...
+    lpgd: Optional[tuple] = None            # lpgd_rule() of this call: (mode, tau, rho), or None -- the implicit-function adjoint differentiates the node
+    fwd_path: str = "per_instance"          # ConeEngine.last_path right after the solve: the path the perturbed solves follow
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -172,6 +177,7 @@ class _ConeLayer(torch.autograd.Function):
         # algorithm here, at the C ABI and in the reference.  The engine keeps a one-pair history whatever the lookback (iteration
         # counts within 2.5 % of lookback 10 on every BASELINE configuration, profiles/r02/aa_memory.json).
         settings = make_settings(merged_args)
+        lpgd = lpgd_rule(merged_args)          # (validated here, with the other arguments: a bad lpgd_tau / lpgd_rho raises before anything is enqueued or remembered)
         note_ignored_args({"acceleration_lookback": settings.acceleration_lookback, **{k: merged_args[k] for k in ("mode", "solve_method", "n_jobs_forward", "n_jobs_backward") if k in merged_args}},
                           explicit_lookback="acceleration_lookback" in merged_args)
         n_refine = refine_steps(merged_args)
@@ -221,7 +227,10 @@ class _ConeLayer(torch.autograd.Function):
                 info["refine"] = refine_info
             lsqr = lsqr_rule(merged_args, eng.n, eng.m)
             fwd_mode = jvp_mode(merged_args)
-            saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if P_bm is None else None, fwd_mode) if needs_grad else None
+            if lpgd is not None:
+                info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
+            saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -318,12 +327,17 @@ class _ConeLayer(torch.autograd.Function):
             return None, None, None, None, None, None, None
         with torch.cuda.device(eng.device):
             dx = dprimal.to(device=eng.device, dtype=torch.float64).contiguous() if dprimal is not None else eng.zeros_like_cached(x)
-            dy = ddual.to(device=eng.device, dtype=torch.float64).contiguous() if ddual is not None else eng.zeros_like_cached(y)
+            dy = ddual.to(device=eng.device, dtype=torch.float64).contiguous() if ddual is not None else (None if saved.lpgd is not None else eng.zeros_like_cached(y))
             if failed is not None:          # masked instances: NaN outputs upstream produce NaN cotangents; they contribute nothing
                 keep = ~failed[:, None]
-                dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy))
+                dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
                 x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
-            if saved.P_bm is not None:
+            lpgd_iters = None
+            if saved.lpgd is not None:          # solver_args mode="lpgd" / "lpgd_left" / "lpgd_right": perturbed re-solves instead of an adjoint system (lpgd.py)
+                dA, dq, dP_bm, adj, lpgd_iters = lpgd_backward(eng, saved.lpgd, saved.ce_settings, saved.fwd_path, saved.A_bm, saved.q_eval, saved.P_bm, x, y, s, dx, dy,
+                                                               failed=failed, batch_minor_out=saved.batch_minor_in)
+                dP = dP_bm.t().to(in_device) if dP_bm is not None else None
+            elif saved.P_bm is not None:
                 dA, dq, adj, dP_bm = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, P_bm=saved.P_bm, path=saved.path, lsqr=saved.lsqr)
                 dP = dP_bm.t().to(in_device)
             else:
@@ -332,8 +346,13 @@ class _ConeLayer(torch.autograd.Function):
         ctx.adj_status = adj
         if isinstance(ctx.info, dict) and isinstance(ctx.info.get("adjoint"), dict):
             ctx.info["adjoint"]["status"] = adj
+            if lpgd_iters is not None:
+                ctx.info["adjoint"]["lpgd_iters"] = lpgd_iters
         with torch.cuda.device(eng.device):
-            eng.mailbox.note_adjoint_flags(adj, batch_size)            # reported by the next forward call (no host sync on the backward path)
+            if lpgd_iters is None:
+                eng.mailbox.note_adjoint_flags(adj, batch_size)
+            else:          # (the summary counts bits 0-1 of what it is given: the two LPGD bits -- 16 a perturbed solve failed, 32 a dy entry was dropped -- travel as bit 0, under their own warning)
+                eng.mailbox.note_adjoint_flags((adj != 0).to(torch.int32), batch_size, lpgd=True)            # reported by the next forward call (no host sync on the backward path)
         dA = dA.to(in_device)
         dq = dq.to(in_device)
         if originally_unbatched:

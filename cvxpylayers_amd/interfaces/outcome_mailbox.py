@@ -35,6 +35,8 @@ class OutcomeMailbox:
         self.adj_pending = []         # (slot, batch size) of backward calls not yet folded
         self.adj_seq = 0
         self.adj_count = self.adj_total = 0     # flagged / all instances of the backward calls folded since the last report
+        self.lpgd_slots = set()       # the adjoint slots whose pending vector came from an LPGD backward (its causes are others: counted and reported apart)
+        self.lpgd_count = self.lpgd_total = 0
         self.async_mode = False       # the most recent forward ran with raise_on_error=False
         self.async_pending = None     # its batch size, until its outcome has been reported
 
@@ -87,12 +89,14 @@ class OutcomeMailbox:
                 self.ensure(slot)
         return self.slots.tolist()
 
-    def note_adjoint_flags(self, adj, bs):
+    def note_adjoint_flags(self, adj, bs, lpgd: bool = False):
         """Called at the END of a backward call: the per-instance flags of the adjoint (more active rows than the direct solve holds, LSQR iteration limit: such
         gradients are zero or inexact) are summarised on the device behind the adjoint kernel -- no host synchronisation on the backward path -- into one of two
         alternating pinned slots.  The NEXT forward call reports them (everything enqueued before its status summary is complete when that is read).  A layer
         applied several times in one graph (the 20 time steps of the supply-chain loop) runs several backward calls between two forwards: the slot a new call is
-        about to reuse is folded into the running count first."""
+        about to reuse is folded into the running count first.
+        lpgd=True: `adj` comes from an LPGD backward (interfaces/lpgd.py) and holds 1 where a perturbed solve failed or a dual cotangent had no b entry to travel
+        in (status bits 16 / 32 brought to bit 0 by the caller: the summary counts bits 0-1); those are counted apart and reported under their own causes."""
         if adj.numel() == 0:
             return
         pend = self.adj_pending
@@ -107,6 +111,7 @@ class OutcomeMailbox:
             self.fold(pend.pop(k))
         self.enqueue(adj, slot)
         pend.append((slot, bs))
+        (self.lpgd_slots.add if lpgd else self.lpgd_slots.discard)(slot)
 
     def fold(self, entry):
         slot, bs = entry
@@ -115,6 +120,9 @@ class OutcomeMailbox:
         if self.slots is not None and self.slots[slot, 3] == 0:
             self._synchronize(all_streams=True)
             self.ensure(slot)
+        if slot in self.lpgd_slots:
+            self.lpgd_count += int(self.slots[slot, 2]); self.lpgd_total += bs
+            return
         self.adj_count += int(self.slots[slot, 2])     # bits 0-1; bit 2 (4) = rank-deficient system, basic solution returned like the reference's LSQR does -- not a failure
         self.adj_total += bs
 
@@ -135,7 +143,7 @@ class OutcomeMailbox:
         """forward side: every backward enqueued before this forward's status summary has finished by the time that summary is read
         (block=False -- the asynchronous forward of raise_on_error=False: only the slots whose ready flag is already set are folded)"""
         pend = self.adj_pending
-        if not pend and not self.adj_total:
+        if not pend and not self.adj_total and not self.lpgd_total:
             return
         if not block:
             ready = [k for k, (sl, _) in enumerate(pend) if self.slots is not None and self.slots[sl, 3] != 0]
@@ -150,3 +158,8 @@ class OutcomeMailbox:
         if nbad:
             warnings.warn(f"MI355 adjoint: {nbad} of {bs} instances of the previous backward pass were flagged (degenerate active "
                           "set or iteration limit); their gradients are unreliable")
+        nbad, bs = self.lpgd_count, self.lpgd_total
+        self.lpgd_count = self.lpgd_total = 0
+        if nbad:
+            warnings.warn(f"MI355 LPGD backward: {nbad} of {bs} instances of the previous backward pass were flagged (a perturbed solve failed: zero gradient; or a "
+                          "dual cotangent sat on a row without a b entry and was dropped); info['adjoint']['status'] bits 16 / 32 say which; their gradients are unreliable")

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -65,6 +65,27 @@ def adjoint_mode(merged_args: dict) -> str:
     "lsqr" -> diffcp's LSQR on the full (n + m + 1) system with its stopping rule for every instance (ce_vjp_lsqr).  Shared-A templates run LSQR whatever the mode says."""
     mode = str(merged_args.get("mode", ""))
     return "lsqr" if mode in ("lsqr", "lsmr") else ("dense" if mode == "dense" else "direct")          # ("lsmr": the iterative path with LSMR's recurrences, lsqr_rule()[4])
+
+
+LPGD_MODES = ("lpgd", "lpgd_left", "lpgd_right")
+LPGD_TAU, LPGD_RHO = 0.1, 0.0
+
+
+def lpgd_rule(merged_args: dict):
+    """(mode, tau, rho) of the LPGD backward (interfaces/lpgd.py; Paulus et al. 2024, diffcp's modes of the same names) when solver_args `mode` is "lpgd"
+    (central difference), "lpgd_left" or "lpgd_right"; None for every other mode.  lpgd_tau: the perturbation step, a float > 0 (default 0.1); lpgd_rho: the
+    proximal weight, a float >= 0 (default 0).  Both are validated whenever they are given, whatever the mode; forward-mode AD ignores them, as diffcp does."""
+    mode = merged_args.get("mode")
+    if mode not in LPGD_MODES and "lpgd_tau" not in merged_args and "lpgd_rho" not in merged_args:          # (every call of a layer that does not use the feature: nothing to do)
+        return None
+    vals = {}
+    for key, default, ok, what in (("lpgd_tau", LPGD_TAU, lambda v: v > 0.0, "a finite number > 0"), ("lpgd_rho", LPGD_RHO, lambda v: v >= 0.0, "a finite number >= 0")):
+        v = merged_args.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)) or not ok(float(v)):
+            raise ValueError(f"MI355 solver: {key} must be {what}, got {v!r}")
+        vals[key] = float(v)
+    mode = str(merged_args.get("mode", ""))
+    return (mode, vals["lpgd_tau"], vals["lpgd_rho"]) if mode in LPGD_MODES else None
 
 
 def jvp_mode(merged_args: dict) -> str:
@@ -111,7 +132,7 @@ def note_ignored_args(merged_args: dict, explicit_lookback: bool):
                    " runs as type-I Anderson acceleration with a ONE-pair history (memory 1), not a " + str(int(lb)) + "-pair history; "
                    "pass acceleration_lookback=1 to say so explicitly, 0 to iterate plainly")
     for k in ("mode", "solve_method", "n_jobs_forward", "n_jobs_backward"):
-        if k == "mode" and str(merged_args.get(k)) in ("lsqr", "lsmr", "dense"):          # acted on: adjoint_mode()
+        if k == "mode" and str(merged_args.get(k)) in ("lsqr", "lsmr", "dense") + LPGD_MODES:          # acted on: adjoint_mode(), lpgd_rule()
             continue
         if k in merged_args:
             _warn_once(k, f"MI355 solver: solver_args[{k!r}]={merged_args[k]!r} is accepted for compatibility with the DIFFCP plugin and ignored "

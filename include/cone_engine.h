@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -410,6 +410,38 @@ int ce_value_jvp(ce_handle h, int B, const double *tA_vals_bm, long stA_b, const
 int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const double *g, const unsigned char *skip,
                  double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
                  double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream);
+
+/* LPGD backward (Lagrangian proximal gradient descent, Paulus et al. 2024; diffcp's modes "lpgd", "lpgd_left", "lpgd_right").  The
+ * gradient of a loss through the solution map is formed from one or two more solves of the SAME cone program with the cotangents added to its data, and a
+ * difference of the Lagrangian's parameter gradient G = dL/dtheta (the envelope gradients of ce_value_vjp) at the solutions: no adjoint system, never rank
+ * deficient.  For cotangents dx on x*, dy on y* (ds = 0), a step tau and a proximal weight rho >= 0 the perturbed program at +tau has
+ *   c+ = c + tau dx - rho x*,   b+ = b - tau dy,   P+ = P + rho I,   A unchanged;          the one at -tau: the same call with -tau.
+ *   lpgd_right: [G(x+, y+) - G(x*, y*)] / tau      lpgd_left: [G(x*, y*) - G(x-, y-)] / tau      lpgd: [G(x+, y+) - G(x-, y-)] / (2 tau)
+ * The caller runs the solves itself (ce_solve / ce_solve_qp / ce_solve_shared_a on the outputs below, warm-started at the forward's point).  Both entry points
+ * enqueue on `stream` only, never synchronise the host and allocate nothing; launches are bracketed under profiling kind 2.
+ *   ce_lpgd_perturb : q_out (j, i) at [j*sq_k + i*sq_b] (q_vals' own strides) = fma(-rho, x[i, j], fma(tau, dx[i, j], q)) for j < n, the last row (d) copied.
+ *                     dy [B][m] or NULL.  Given: A_out_bm [B][nnz_aug] becomes a copy of A_vals_bm (batch-major rows sA_b >= nnz_aug apart) in which the b
+ *                     entry of row r alone moved by -tau dy[i, r] (the stored convention A_eval = [-A.data, b]); every other entry is bit-equal.  NULL: nothing
+ *                     of A is read or written (A_vals_bm, A_out_bm may be NULL) -- solve on the forward's own values.
+ *                     P_out [B][nnz_p] = P_vals + rho on the diagonal entries of the structure, written only when P_out is given, nnz_p > 0 and rho != 0.
+ *                     flags [B]: bit 0 = every entry of dx and dy of the instance is exactly zero (its gradient is zero: skip it), bit 1 = some dy[i, r] != 0
+ *                     sits on a row without a b entry in the template: that perturbation has no slot, it is dropped and reported here.
+ *   ce_lpgd_grad    : from two points (x_a, y_a), (x_b, y_b) ([B][n], [B][m]) and the divisor delta (tau or 2 tau):  dA_vals (k, i) =
+ *                     -(y_b,r Dx_c + Dy_r x_a,c) / delta (A entry) / -Dy_r / delta (b entry),  dq_vals (j, i) = Dx_j / delta, (n, i) = 0,
+ *                     dP_vals[i, k] = (1/2 | 1) (x_b,r Dx_c + Dx_r x_a,c) / delta,  with Dx = x_b - x_a, Dy = y_b - y_a: the difference of two products is formed
+ *                     from the differences of the points, never by cancelling the products.  Layouts, strides, NULL outputs, the P structure and skip as
+ *                     ce_value_vjp: a skipped instance gets exact zeros whatever its inputs hold.  CE_E_TOO_LARGE when the points of four instances exceed LDS.
+ * ce_set_transient_solve(h, 1): until switched off, ce_solve / ce_solve_qp on this handle leave no trace on it -- the batch-major inputs retained for
+ * ce_vjp(A_vals = NULL) and the dispatch history (order, pending order, iteration memory) stay those of the last ordinary solve; A_vals must then be batch-major.
+ * A solve issued from a backward pass runs under it, so a later adjoint or forward of another node sees what it would have seen without that backward. */
+int ce_lpgd_perturb(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p,
+                    const double *x, const double *dx, const double *dy, double tau, double rho,
+                    double *q_out, double *A_out_bm, double *P_out, int *flags, void *stream);
+int ce_lpgd_grad(ce_handle h, int B, const double *x_a, const double *y_a, const double *x_b, const double *y_b, double delta, const unsigned char *skip,
+                 double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
+                 double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream);
+int ce_set_transient_solve(ce_handle h, int on);
 
 /* Longest-first dispatch.  Workgroups are dispatched in index order and one workgroup owns one instance, so the tail of a forward launch is set by the
  * instances that happen to start last: when they are long ones the last slots drain slowly (13 % of the metric configuration's kernel time).  With the switch
