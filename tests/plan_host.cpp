@@ -36,6 +36,24 @@ void h_sa_lsqr(const ce_template *tpl, int lsqr_variant, int per_inst, int liste
     const SaLsqrSel s = sa_lsqr_select(S.T, S.sp_RP, S.psd_first, lsqr_variant, per_inst != 0, listed != 0, fwd != 0);
     out[0] = s.row; out[1] = (long)s.lds; out[2] = s.RP; out[3] = s.a_lds;
 }
+// the three planners of k_backward_ns (plan_kit.NS_FIELDS; outside the recorded table).  out: ns_variant, qp_ns_variant, tri_ns_variant, their three LDS sizes,
+// resolve_lds_fits (the acceptance edge of ce_jvp that no plan field shows)
+int h_plan_ns(const ce_template *tpl, long *out) {
+    const Sizes S(tpl); CePlan P;
+    const int rc = plan_engine(tpl, S.T, tpl->nnz_p, read_plan_env(), P);
+    if (rc) return rc;
+    const long v[] = {P.ns_variant, P.qp_ns_variant, P.tri_ns_variant, (long)P.ns_lds, (long)P.qp_ns_lds, (long)P.tri_ns_lds, resolve_lds_fits(S.T, S.psd_first) ? 1 : 0};
+    for (size_t i = 0; i < sizeof v / sizeof v[0]; i++) out[i] = v[i];
+    return 0;
+}
+// the members of the union region of the layout on row v (ce_ns_layout.h bwd_ns_union_doubles).  out: a, b, c in doubles, the region, NTILE, NTHR
+int h_ns_union(int n, int m, int nq, int v, long *out) {
+    if (v < 0 || v >= (int)std::size(NS_ROWS)) return -1;
+    const int NTILE = NS_ROWS[v].NTILE, nqs = nq > 0 ? nq : 1, npad = n + (n & 1);
+    out[0] = (long)nqs * npad + 2 * (64 * bwd_ns_nsl(NTILE) + 2); out[1] = 8 * bwd_ns_ldp(NTILE); out[2] = m + (m & 1) + npad;
+    out[3] = bwd_ns_union_doubles(n, m, nqs, NTILE); out[4] = NTILE; out[5] = NS_ROWS[v].NTHR;
+    return 0;
+}
 // pack_rows for a wave window of W rows: 1 and the packed order is checked to be a permutation of the rows, 0 when the template cannot be packed, -1 on a bad order
 int h_pack_rows(const ce_template *tpl, int W) {
     std::vector<int> ko, krc, kq;

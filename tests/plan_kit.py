@@ -241,6 +241,128 @@ def host_plan_of(family, v, lib=None):
     return dict(zip(PLAN_FIELDS, buf)) if (lib or host_lib()).h_plan(C.byref(t), buf) == 0 else None
 
 
+# ---------------------------------------------------------------------------------------------- the three planners of k_backward_ns (tests/test_gpu_ns_mode_edges.py)
+# Swept beside the families above and outside tests/golden/plan_table.json: the plain, QP and TRI footprints of csrc/ce_ns_layout.h differ (the dense P; the
+# triples' W and lambda), so each kind has LDS edges of its own.  A KIND is "plain" | "qp" | "tri"; its field says which row of CE_NS_VARIANTS serves it.
+NS_FIELDS = ("ns_variant", "qp_ns_variant", "tri_ns_variant")
+NS_PLAN_FIELDS = NS_FIELDS + ("ns_lds", "qp_ns_lds", "tri_ns_lds", "resolve_fits")
+NS_KIND_FIELD = {"plain": "ns_variant", "qp": "qp_ns_variant", "tri": "tri_ns_variant"}
+NS_SWEEP_END = 1400          # no kind is served past this many rows or triples (asserted by ns_family_values)
+
+
+def ns_shape(kind, n, rows, q=(), states=(), ep=0, p=()):
+    """(kind, n, cones, states of the second-order blocks): `rows` zero + nonnegative + second-order rows (z = min(2, n // 4), the blocks q that fit, the rest
+    nonnegative) and, TRI kind, ep exponential and len(p) power triples behind them"""
+    z = min(2, n // 4)
+    q, states = list(q), list(states)
+    while q and z + sum(q) > rows - 1:
+        q.pop(); states.pop()
+    cones = {"z": z, "l": rows - z - sum(q), "q": q}
+    if kind == "tri":
+        cones.update(ep=ep, p=list(p))
+    return kind, n, cones, tuple(states)
+
+
+def _ns_n(kind):          # n swept at n + 8 plain rows: one second-order block on the boundary (the smallest n have none or a block of 3)
+    tri = dict(ep=1, p=[0.4]) if kind == "tri" else {}
+    return lambda n: ns_shape(kind, n, n + 8, *(([8], ["bd"]) if n >= 10 else ([3], ["bd"]) if n >= 2 else ([], [])), **tri)
+
+
+def _ns_m(kind, n, states):          # plain rows swept at fixed n: two second-order blocks in the given states
+    tri = dict(ep=2, p=[0.4]) if kind == "tri" else {}
+    return lambda m: ns_shape(kind, n, m, [5, 4], states, **tri)
+
+
+def _ns_n_wide_block(kind):          # n swept with ONE boundary block of n + 2 rows: n directions with an eigenvalue in (0, 1), so that about n / 2 columns stay free for the
+    tri = dict(ep=1, p=[0.4]) if kind == "tri" else {}          # sweep (at n + 8 rows a regular point of a linear objective leaves it a handful: ns_edge_kit.py)
+    return lambda n: ns_shape(kind, n, min(2, n // 4) + n + 2 + n // 2 + 4, [n + 2], ["bd"], **tri)
+
+
+# name -> (kind, first value, value -> shape).  The values run from the first one until the kind is refused (ns_family_values)
+NS_FAMILIES = {}
+for _k in NS_KIND_FIELD:
+    NS_FAMILIES[f"{_k}_n"] = (_k, 1, _ns_n(_k))
+    if _k != "qp":          # (a quadratic objective leaves about n / 2 columns free in every family)
+        NS_FAMILIES[f"{_k}_n_wide_block"] = (_k, 1, _ns_n_wide_block(_k))
+    for _n, _st in ((12, ("bd", "in")), (40, ("bd", "out")), (80, ("bd", "bd"))):
+        NS_FAMILIES[f"{_k}_m_n{_n}"] = (_k, _n + 12, _ns_m(_k, _n, _st))
+NS_FAMILIES["qp_n_l2n"] = ("qp", 1, lambda n: ("qp", n, {"z": 0, "l": 2 * n, "q": []}, ()))
+NS_FAMILIES["tri_count_n12"] = ("tri", 1, lambda k: ns_shape("tri", 12, 14, [4], ["bd"], ep=k))
+
+
+def ns_pstruct(kind, n):
+    """dense upper-triangular P structure of the QP kind (shape_of's)"""
+    if kind != "qp":
+        return None
+    return (np.concatenate([np.arange(j + 1) for j in range(n)]).astype(np.int32), np.concatenate([[0], np.cumsum(np.arange(1, n + 1))]).astype(np.int32))
+
+
+def host_ns_plan(shape, lib=None):
+    """{NS_PLAN_FIELDS} of a shape from the g++ build (h_plan_ns of tests/plan_host.cpp), or None when plan_engine refuses the template"""
+    from cvxpylayers_amd import _lib, problems as P
+    kind, n, cones = shape[:3]
+    ck = (kind, n, repr(sorted(cones.items())), tuple(os.environ.get(e) for e in PLAN_ENV))
+    if lib is None and ck in _HOST.setdefault("ns_plans", {}):
+        return _HOST["ns_plans"][ck]
+    out = _host_ns_plan(kind, n, cones, lib, _lib, P)
+    if lib is None:
+        _HOST["ns_plans"][ck] = out
+    return out
+
+
+def _host_ns_plan(kind, n, cones, lib, _lib, P):
+    tpl = P.dense_template(n, cones)
+    keep = [np.ascontiguousarray(tpl.indices, dtype=np.int32), np.ascontiguousarray(tpl.indptr, dtype=np.int32), np.ascontiguousarray(cones.get("q", []), dtype=np.int32),
+            np.ascontiguousarray(cones.get("p", []), dtype=np.float64)]
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))          # noqa: E731
+    t = _lib.CeTemplate()
+    t.n, t.m, t.nnz_aug, t.indices, t.indptr = int(tpl.n), int(tpl.m), int(keep[1][-1]), ip(keep[0]), ip(keep[1])
+    t.z, t.l, t.nq, t.q = int(cones.get("z", 0)), int(cones.get("l", 0)), len(keep[2]), ip(keep[2])
+    t.nep, t.np, t.p = int(cones.get("ep", 0)), len(keep[3]), keep[3].ctypes.data_as(C.POINTER(C.c_double))
+    ps = ns_pstruct(kind, n)
+    if ps is not None:
+        t.nnz_p, t.p_indices, t.p_indptr = int(ps[1][-1]), ip(ps[0]), ip(ps[1])
+    buf = (C.c_long * len(NS_PLAN_FIELDS))()
+    return dict(zip(NS_PLAN_FIELDS, buf)) if (lib or host_lib()).h_plan_ns(C.byref(t), buf) == 0 else None
+
+
+def ns_served(kind, plan):
+    return plan is not None and plan[NS_KIND_FIELD[kind]] >= 0
+
+
+def ns_family_values(family, plan_fn=host_ns_plan):
+    """the swept values of a family: from its first value to the first one at which its kind is no longer served, that one included"""
+    kind, v, fn = NS_FAMILIES[family]
+    seen = False
+    while v < NS_SWEEP_END:
+        ok = ns_served(kind, plan_fn(fn(v)))
+        yield v
+        if seen and not ok:
+            return
+        seen, v = seen or ok, v + 1
+    raise AssertionError(f"{family}: still served at {NS_SWEEP_END}")
+
+
+def ns_edges(family, plan_fn=host_ns_plan):
+    """find_edges of a family on its kind's field and resolve_fits: [(v_before, plan_before, v_after, plan_after)].  A plan in which the kind is not served counts
+    as refused (None), whatever else it holds."""
+    kind, _, fn = NS_FAMILIES[family]
+    fields = (NS_KIND_FIELD[kind], "resolve_fits")
+
+    def served_plan(v):
+        p = plan_fn(fn(v))
+        return p if ns_served(kind, p) else None
+    return find_edges(served_plan, ns_family_values(family, plan_fn), fields)
+
+
+def ns_union_members(n, m, nq, row, lib=None):
+    """(a, b, c) of the union region on a row of CE_NS_VARIANTS, in doubles: {a_z, publication buffers} | the sweep buffers | {q, g}"""
+    out = (C.c_long * 6)()
+    assert (lib or host_lib()).h_ns_union(int(n), int(m), int(nq), int(row), out) == 0
+    assert out[3] == max(out[:3])
+    return tuple(out[:3])
+
+
 def switch_key(sw):
     return ",".join(f"{k}={v}" for k, v in sorted(sw.items()))
 
