@@ -176,6 +176,18 @@ struct CeLpgdGradArgs {
     double *dA; long sdAk, sdAb; double *dq; long sdqk, sdqb; double *dP;
 };
 
+// ---- the termination test at a given point (ce_check.h): two sparse products over the template's structure, no plan ----
+// k_check_solved: x [B][n], y, s [B][m]; CSR of the A part (rptr, rcol, rsrc), its CSC pointers and rows (cptr, rowidx), the b entry of every row (engine-owned),
+// the P structure (caller-owned); gr / gc: threads that share a row / a column (powers of two <= 256, fixed by m and n); eligible [B] or null, tested against emask
+struct CeCheckArgs {
+    int B, n, m, nnz_aug, nnz_p, gr, gc;
+    const int *rptr, *rcol, *rsrc, *cptr, *rowidx, *bpos, *prow, *pcol;
+    const double *A; long sAk, sAb; const double *q; long sqk, sqb; const double *P;
+    const double *x, *y, *s; const int *eligible; int emask;
+    double eps_abs, eps_rel;
+    unsigned char *solved; int *status, *iters; double *resid;
+};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -208,6 +220,9 @@ void ce_launch_value_vjp_tile(bool staged, int chunks, int kchunk, int wdq, size
 size_t ce_value_lds(int n, int m);               // k_value
 size_t ce_value_vjp_rows_lds(int n, int m);      // k_value_vjp_rows
 size_t ce_value_vjp_tile_lds(int n, int m);      // k_value_vjp_tile<STAGED = true>
+// ce_tu_check.hip: one workgroup per instance, then one workgroup that counts; staged: the instance's value row sits in LDS (lds includes it)
+void ce_launch_check_solved(bool staged, size_t lds, hipStream_t st, const CeCheckArgs &a, int *n_unsolved);
+size_t ce_check_lds(int n, int m, int nnz_staged);      // k_check_solved: the vectors of one instance + nnz_staged values
 // ce_tu_lpgd.hip: one workgroup per VAL_IPB instances (perturb, grad_rows) / per (64-instance tile, chunk of kchunk entries)
 void ce_launch_lpgd_perturb(hipStream_t st, const CeLpgdPerturbArgs &a);
 void ce_launch_lpgd_grad_rows(size_t lds, hipStream_t st, const CeLpgdGradArgs &a);
@@ -230,3 +245,4 @@ hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);
 hipError_t ce_setattr_value(int bytes);
 hipError_t ce_setattr_lpgd(int bytes);
+hipError_t ce_setattr_check(int bytes);

@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
     HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX));
+    HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
 
@@ -786,6 +786,37 @@ int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const dou
         if (tile) r.dA = nullptr;
         if (tile_dq) r.dq = nullptr;
         if (r.dA || r.dq || r.dP) ce_launch_value_vjp_rows(lds_rows, st, r);
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+
+// ---- the termination test at a given point (ce_check.h): one launch per instance set + one that counts, under profiling class 2
+static constexpr size_t CHECK_STAGE_MAX = 64 * 1024;      // the value row is staged in LDS while two workgroups still share a CU; beyond, it is read twice (L2)
+static int check_group(int rows) { int g = 1; while (2 * g * rows <= 256 && g < 64) g *= 2; return g; }      // threads per row: the largest power of two with g * rows <= 256
+int ce_check_solved(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p,
+                    const double *x, const double *y, const double *s, const int *eligible, int eligible_mask, double eps_abs, double eps_rel,
+                    unsigned char *solved, int *status, int *iters, double *resid, int *n_unsolved, void *stream) {
+    if (!h || B <= 0 || !A_vals || !q_vals || !x || !y || !s || !solved || !status || !iters || !resid || !n_unsolved) { g_err = "null argument"; return CE_E_BADARG; }
+    const int rc = value_check_p(P_vals, p_rows, p_cols, nnz_p, true);
+    if (rc) return rc;
+    const DevT &T = h->T;
+    CeCheckArgs a{};
+    a.B = B; a.n = T.n; a.m = T.m; a.nnz_aug = T.nnz_aug; a.nnz_p = P_vals ? nnz_p : 0; a.gr = check_group(T.m); a.gc = check_group(T.n);
+    a.rptr = h->d_csr_ptr.get(); a.rcol = h->d_csr_col.get(); a.rsrc = h->d_csr_src.get(); a.cptr = h->d_csc_ptr.get(); a.rowidx = h->d_rowidx.get(); a.bpos = h->d_bpos.get();
+    a.prow = p_rows; a.pcol = p_cols;
+    a.A = A_vals; a.sAk = sA_k; a.sAb = sA_b; a.q = q_vals; a.sqk = sq_k; a.sqb = sq_b; a.P = P_vals;
+    a.x = x; a.y = y; a.s = s; a.eligible = eligible; a.emask = eligible_mask; a.eps_abs = eps_abs; a.eps_rel = eps_rel;
+    a.solved = solved; a.status = status; a.iters = iters; a.resid = resid;
+    const size_t lds0 = ce_check_lds(T.n, T.m, 0), lds1 = ce_check_lds(T.n, T.m, T.nnz_aug);
+    if (lds0 > VALUE_LDS_MAX) { g_err = "ce_check_solved: x, y, s and the products of one instance exceed LDS"; return CE_E_TOO_LARGE; }
+    const bool staged = lds1 <= CHECK_STAGE_MAX;
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps(h, 2, st);
+        ce_launch_check_solved(staged, staged ? lds1 : lds0, st, a, n_unsolved);
     }
     HIPCHK(hipGetLastError());
     return CE_OK;

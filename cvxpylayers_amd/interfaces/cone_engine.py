@@ -510,6 +510,38 @@ class ConeEngine:
         _lib.check(rc, name)
         return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns"}
 
+    def check_solved(self, A_eval, q_eval, x, y, s, eps_abs: float, eps_rel: float, eligible=None, eligible_mask: int = 1, P_bm=None, p_structure=None,
+                     status=None, iters=None, resid=None):
+        """The forward kernels' termination test at the point (x (B, n), y, s (B, m)) (include/cone_engine.h ce_check_solved).  A_eval (nnz_aug, B), q_eval
+        (n+1, B) fp64 on this engine's device in ANY strides (nothing is copied); P_bm (B, nnz_p) contiguous with p_structure = (p_rows, p_cols) int32 device
+        tensors; eligible (B,) int32 or None: an instance with eligible & eligible_mask == 0 is unsolved whatever its residual.  Returns solved (B,) uint8,
+        status, iters (B,) int32, resid (B, 3), n_unsolved (1,) int32 ON THE DEVICE: a solved instance gets status 1, iters 0 and its resid row, every other
+        entry of status / iters / resid keeps what the given tensor held (new tensors: zeros).  Enqueues only."""
+        B = x.shape[0]
+        dev = self.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        solved = torch.empty((B,), dtype=torch.uint8, device=dev)
+        status = torch.zeros((B,), **i32) if status is None else status
+        iters = torch.zeros((B,), **i32) if iters is None else iters
+        resid = torch.zeros((B, 3), dtype=torch.float64, device=dev) if resid is None else resid
+        if B == 0:
+            return solved, status, iters, resid, torch.zeros((1,), **i32)
+        n_uns = torch.empty((1,), **i32)
+        for name, t, dt in (("x", x, torch.float64), ("y", y, torch.float64), ("s", s, torch.float64), ("status", status, torch.int32), ("iters", iters, torch.int32),
+                            ("resid", resid, torch.float64)) + ((("eligible", eligible, torch.int32),) if eligible is not None else ()):
+            if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"ConeEngine.check_solved: {name} must be a contiguous {dt} tensor on {dev}")
+        if tuple(x.shape) != (B, self.n) or tuple(y.shape) != (B, self.m) or tuple(s.shape) != (B, self.m) or tuple(A_eval.shape) != (self.nnz_aug, B) or \
+                tuple(q_eval.shape) != (self.n + 1, B) or status.numel() != B or iters.numel() != B or tuple(resid.shape) != (B, 3) or (eligible is not None and eligible.numel() != B):
+            raise ValueError("ConeEngine.check_solved: shapes do not match the template and the batch size")
+        pr, pc, nnz_p = self._p_args(p_structure if P_bm is not None else None)
+        rc = _lib.lib().ce_check_solved(self._h, B, A_eval.data_ptr(), A_eval.stride(0), A_eval.stride(1), q_eval.data_ptr(), q_eval.stride(0), q_eval.stride(1),
+                                        P_bm.data_ptr() if nnz_p else None, pr, pc, nnz_p, x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                        eligible.data_ptr() if eligible is not None else None, int(eligible_mask), float(eps_abs), float(eps_rel),
+                                        solved.data_ptr(), status.data_ptr(), iters.data_ptr(), resid.data_ptr(), n_uns.data_ptr(), self._stream())
+        _lib.check(rc, "ce_check_solved")
+        return solved, status, iters, resid, n_uns
+
     # ---- the optimal value and its envelope-theorem derivatives (include/cone_engine.h ce_value ...): streaming passes, no system solved
     @staticmethod
     def _p_args(p_structure):

@@ -9,7 +9,7 @@ csrc/libcone_engine.so through the C ABI in include/cone_engine.h.  No CPU fallb
 Not thread-safe (engines are created lazily and cached on MI355_ctx), like moreau_if.py:14-15.
 
 This module holds the context (MI355_ctx) and the autograd function; its parts live next to it and are re-exported here:
-solver_args.py (which solver_args exist and what they mean), lpgd.py (the LPGD backward: gradients from perturbed re-solves), cone_engine.py (ConeEngine: the ce_handle wrapper), outcome_mailbox.py
+solver_args.py (which solver_args exist and what they mean), lpgd.py (the LPGD backward: gradients from perturbed re-solves), newton_first.py (warm-started calls: Newton steps first, the solver for the rest), cone_engine.py (ConeEngine: the ce_handle wrapper), outcome_mailbox.py
 (OutcomeMailbox: how forward outcomes and adjoint flags reach the host), quad_epigraph.py (QuadEpigraph), const_a.py (shared-A paths).
 """
 from __future__ import annotations
@@ -24,10 +24,11 @@ import torch
 from cvxpylayers_amd import _lib
 from cvxpylayers_amd.interfaces.cone_engine import ConeEngine
 from cvxpylayers_amd.interfaces.lpgd import lpgd_backward
+from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_served
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, note_ignored_args, refine_steps, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, refine_steps, unpack_rule)
 
 
 class MI355_ctx:
@@ -181,6 +182,7 @@ class _ConeLayer(torch.autograd.Function):
         note_ignored_args({"acceleration_lookback": settings.acceleration_lookback, **{k: merged_args[k] for k in ("mode", "solve_method", "n_jobs_forward", "n_jobs_backward") if k in merged_args}},
                           explicit_lookback="acceleration_lookback" in merged_args)
         n_refine = refine_steps(merged_args)
+        n_newton = newton_first(merged_args)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
         with torch.cuda.device(dev):
@@ -193,7 +195,18 @@ class _ConeLayer(torch.autograd.Function):
                 if originally_unbatched:
                     P_eval = P_eval.unsqueeze(1)
                 P_bm = P_eval.detach().to(device=dev, dtype=torch.float64).t().contiguous()        # (B, nnz_p)
-            x, y, s, iters, status, resid = eng.solve(A_bm, q_dev, settings, warm=warm, P_bm=P_bm)
+            # solver_args newton_first with a warm start: Newton steps from it, the termination test, and the forward kernels for the instances that miss it
+            # (newton_first.py: one 4-byte host read, also under raise_on_error=False); everything below sees the final full-batch result
+            nf_info = None
+            if n_newton > 0 and warm is not None and batch_size > 0:
+                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm)
+                if nf_info["path"] == "none":
+                    _warn_once("newton_first_none", "MI355 solver: solver_args newton_first needs the search-free elimination, which this template or path does not have "
+                                                    "(PSD cones, n > 108, a shared A); the ordinary warm-started solve ran (info['newton_first']['path'] == 'none')")
+            else:
+                x, y, s, iters, status, resid = eng.solve(A_bm, q_dev, settings, warm=warm, P_bm=P_bm)
+                if n_newton > 0:
+                    nf_info = not_served(n_newton, batch_size)          # (no warm start: nothing to step from, said in info alone)
             path = adjoint_path(eng.last_path, P_bm is not None, merged_args)          # recorded per call: the backward of THIS node must not follow a later solve's path
             # solver_args refine_steps: Newton refinement behind the solve on the same stream, BEFORE the warm-start memory, the saved state and the failure
             # masking are formed: warm starts, backward and jvp all see the refined point.  Failed instances (status < 0) are skipped on the device.
@@ -225,6 +238,8 @@ class _ConeLayer(torch.autograd.Function):
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
             if refine_info is not None:
                 info["refine"] = refine_info
+            if nf_info is not None:
+                info["newton_first"] = nf_info
             lsqr = lsqr_rule(merged_args, eng.n, eng.m)
             fwd_mode = jvp_mode(merged_args)
             if lpgd is not None:

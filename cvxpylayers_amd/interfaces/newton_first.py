@@ -1,0 +1,75 @@
+"""solver_args newton_first: a warm-started batch is solved by Newton steps first, by the ordinary kernels for the rest.
+
+A layer in a training or tracking loop solves the same batch again after its parameters moved a little.  From the previous solution, one or two safeguarded
+Newton steps on the KKT residual (ce_refine / ce_refine_qp: the search-free elimination) usually reach a point that passes the solver's own termination test;
+such an instance needs no ADMM iteration at all.  One forward call with newton_first = k > 0 and a warm start:
+    1. (x, y, s) <- a copy of the warm start;  ConeEngine.refine: at most k steps, a rejected or flagged instance keeps its point bit for bit
+    2. ConeEngine.check_solved: the termination test of the forward kernels at every instance that kept a step (refine_status & 1) -- such a point is a
+       complementary pair in the cones by construction, so the affine test is sufficient; an instance without a kept step is not eligible, whatever its residual
+    3. accepted instances are done: status 1, iters 0, resid = the test's three numbers
+    4. the number of the others reaches the host: 4 bytes through pinned memory and ONE stream synchronisation, also under raise_on_error=False
+    5. none left: no forward kernel is launched.  Otherwise the unaccepted instances are gathered, solved by the ordinary dispatcher warm-started at the point
+       refine left (ConeEngine.solve_transient: the handle's retained inputs and dispatch history stay those of full-batch solves) and scattered back.
+Served where refine_steps is: per-instance-A templates with the search-free elimination.  A batch whose data did not change at all keeps no step (the residual
+cannot decrease) and falls back as a whole: deliberate -- accepting a point no step vouches for would need the cone conditions tested as well.
+"""
+from __future__ import annotations
+
+import torch
+
+from cvxpylayers_amd import _lib
+from cvxpylayers_amd.interfaces.cone_engine import ConeEngine
+
+
+def not_served(steps: int, batch_size: int) -> dict:
+    """info["newton_first"] of a call the feature did not act on (no warm start, or a template / path without the elimination)"""
+    return {"path": "none", "steps": int(steps), "accepted": None, "n_accepted": 0, "n_fallback": int(batch_size), "refine": None}
+
+
+def _read_int(eng: ConeEngine, dev_int: torch.Tensor) -> int:
+    """the one host synchronisation of the feature: a device int through the engine's pinned slot"""
+    slot = getattr(eng, "_nf_pinned", None)
+    if slot is None:
+        slot = eng._nf_pinned = torch.empty((1,), dtype=torch.int32).pin_memory()
+    slot.copy_(dev_int, non_blocking=True)
+    torch.cuda.current_stream(eng.device).synchronize()
+    return int(slot[0])
+
+
+def newton_first_solve(eng: ConeEngine, A_bm, q_eval, settings, warm, steps: int, P_bm=None):
+    """The forward solve of a warm-started call with newton_first = steps > 0.  A_bm (B, nnz_aug) contiguous, q_eval (n+1, B), warm = (x, y, s), P_bm (B, nnz_p)
+    or None, settings the call's ce_settings.  Returns (x, y, s, iters, status, resid), info -- what ConeEngine.solve returns for the whole batch, and
+    info["newton_first"].  Where the feature is not served (a shared A, no elimination for the template) the ordinary warm-started solve runs and info's path is
+    "none".  Leaves on the engine what a full-batch per-instance solve() leaves (last_path, last_acceleration, the remembered objective)."""
+    B = A_bm.shape[0]
+    dev = eng.device
+    if tuple(warm[0].shape) != (B, eng.n) or tuple(warm[1].shape) != (B, eng.m) or tuple(warm[2].shape) != (B, eng.m):
+        raise ValueError(f"warm start: expected x {(B, eng.n)}, y {(B, eng.m)}, s {(B, eng.m)}, got "
+                         f"{tuple(warm[0].shape)}, {tuple(warm[1].shape)}, {tuple(warm[2].shape)}")
+    const_a = P_bm is None and eng._use_const_a(A_bm)          # (the dispatcher's own decision, made once: the solves below are told the path)
+    refine_info = {"path": "none"}
+    if not const_a:
+        x, y, s = (t.detach().to(device=dev, dtype=torch.float64).clone().contiguous() for t in warm)          # (refine works in place: never on the caller's tensors)
+        x, y, s, refine_info = eng.refine(A_bm, q_eval, x, y, s, steps, status=None, P_bm=P_bm)
+    if refine_info["path"] != "ns":
+        return eng.solve(A_bm, q_eval, settings, warm=warm, P_bm=P_bm, path="const_a" if const_a else "per_instance"), not_served(steps, B)
+    # (status, iters, resid: every entry is written below -- by the test for an accepted instance, by the scatter for the others -- so they start uninitialised)
+    outs = (torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B, 3), dtype=torch.float64, device=dev))
+    solved, status, iters, resid, n_uns = eng.check_solved(A_bm.t(), q_eval, x, y, s, settings.eps_abs, settings.eps_rel, eligible=refine_info["status"], eligible_mask=1,
+                                                           P_bm=P_bm, p_structure=eng.p_structure_dev() if P_bm is not None else None,
+                                                           status=outs[0], iters=outs[1], resid=outs[2])
+    accepted = solved.to(torch.bool)
+    n_fallback = _read_int(eng, n_uns)
+    # what a full-batch solve() on the per-instance path records on the engine
+    eng._last_q, eng._last_q_key = q_eval.detach(), (A_bm.data_ptr(), B)
+    eng.last_path = "per_instance"
+    eng._note_acceleration(settings, honoured=bool(_lib.lib().ce_acceleration_available(eng._h)), path="size-generic forward kernels")
+    if n_fallback > 0:
+        # the unaccepted instances in their batch order, without a second host round trip: a stable sort of the accepted flags puts them first
+        idx = torch.argsort(solved.to(torch.int32), stable=True)[:n_fallback]
+        sub = eng.solve_transient(A_bm.index_select(0, idx), q_eval.index_select(1, idx), settings, warm=(x.index_select(0, idx), y.index_select(0, idx), s.index_select(0, idx)),
+                                  P_bm=P_bm.index_select(0, idx) if P_bm is not None else None, path="per_instance")
+        for full, part in zip((x, y, s, iters, status, resid), sub):
+            full.index_copy_(0, idx, part)
+    info = {"path": "ns", "steps": int(steps), "accepted": accepted, "n_accepted": B - n_fallback, "n_fallback": n_fallback, "refine": refine_info}
+    return (x, y, s, iters, status, resid), info

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -108,6 +108,16 @@ def refine_steps(merged_args: dict) -> int:
     v = merged_args.get("refine_steps", 0)
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
         raise ValueError(f"MI355 solver: refine_steps must be an integer >= 0, got {v!r}")
+    return int(v)
+
+
+def newton_first(merged_args: dict) -> int:
+    """Newton steps IN FRONT of the forward solve of a warm-started call (interfaces/newton_first.py: ce_refine / ce_refine_qp from the warm start, then
+    ce_check_solved; instances that pass the solver's own termination test are done, the others are solved by the ordinary kernels from the refined point): an
+    integer >= 0, default 0 = off.  Acts only with a warm start and where refine_steps acts; info["newton_first"]["path"] tells which."""
+    v = merged_args.get("newton_first", 0)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
+        raise ValueError(f"MI355 solver: newton_first must be an integer >= 0, got {v!r}")
     return int(v)
 
 

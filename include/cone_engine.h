@@ -411,6 +411,34 @@ int ce_value_vjp(ce_handle h, int B, const double *x, const double *y, const dou
                  double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b,
                  double *dP_vals, const int *p_rows, const int *p_cols, int nnz_p, void *stream);
 
+/*
+ * THE TERMINATION TEST AT A GIVEN POINT.  The forward kernels stop an instance when (ce_forward_v2.h, oracle/cone_oracle.c; tau = 1 here)
+ *        res_pri  = |A x + s - b|_inf      <=  eps_abs + eps_rel max(|A x|_inf, |s|_inf, |b|_inf)
+ *        res_dual = |P x + A^T y + c|_inf  <=  eps_abs + eps_rel max(|A^T y|_inf, |c|_inf, |P x|_inf)
+ *        gap      = |x^T P x + c^T x + b^T y|  <=  eps_abs + eps_rel max(|c^T x|, |b^T y|, |x^T P x|)
+ * (A = -A_vals, b = A_vals[b entries], 0 on a row without one, c = q_vals[:n]).  ce_check_solved evaluates exactly that at a point the CALLER supplies, so that a
+ * point obtained without the solver -- a warm start moved by ce_refine (solver_args newton_first) -- can be accepted under the solver's own
+ * rule.  The cone conditions are NOT tested: the affine test is sufficient only for a complementary pair in the cones, which is what ce_refine returns for an
+ * instance that kept a step (refine_status & 1).  Pass that vector as `eligible` with eligible_mask = 1: an instance with (eligible[i] & eligible_mask) == 0 is
+ * unsolved whatever its residual (eligible = NULL: every instance is tested).
+ * A_vals, q_vals with strides as ce_solve (any pair; nothing is copied); the P structure explicit, as ce_value (one triangle: an off-diagonal entry counts twice;
+ * NULL / 0: linear objective); P_vals (B, nnz_p) batch-major; x [B][n], y, s [B][m] contiguous.
+ *   solved instance : solved[i] = 1, status[i] = 1, iters[i] = 0, resid[3 i ..] = res_pri, res_dual, gap
+ *   any other       : solved[i] = 0; status[i], iters[i] and its resid row are NOT touched
+ *   n_unsolved[0]   : set (not accumulated) to the number of unsolved instances -- a DEVICE int; the caller copies it where it needs it
+ * A non-finite entry in the point, the values or the products makes its own instance unsolved and nothing else.  One workgroup per instance; every sum runs in an
+ * order fixed by the template and the thread count (no floating-point atomics), so an instance's numbers depend neither on B nor on its position in the batch.
+ * The instance's value row is read from memory once and staged in LDS when the workgroup's footprint stays within 64 KB; a longer row is read twice (L2).  P x is
+ * formed by a scan of the structure, O(n nnz_p / 256) per thread: meant for the small dense P of the native QP path.
+ * Enqueues two launches on `stream` (the test, then the count), allocates nothing, never synchronises the host; bracketed under profiling kind 2.
+ * CE_E_TOO_LARGE when x, y, s and the three products of one instance exceed LDS.
+ */
+int ce_check_solved(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *P_vals, const int *p_rows, const int *p_cols, int nnz_p,
+                    const double *x, const double *y, const double *s, const int *eligible /* NULL: all */, int eligible_mask,
+                    double eps_abs, double eps_rel,
+                    unsigned char *solved, int *status, int *iters, double *resid /* B x 3 */, int *n_unsolved, void *stream);
+
 /* LPGD backward (Lagrangian proximal gradient descent, Paulus et al. 2024; diffcp's modes "lpgd", "lpgd_left", "lpgd_right").  The
  * gradient of a loss through the solution map is formed from one or two more solves of the SAME cone program with the cotangents added to its data, and a
  * difference of the Lagrangian's parameter gradient G = dL/dtheta (the envelope gradients of ce_value_vjp) at the solutions: no adjoint system, never rank
