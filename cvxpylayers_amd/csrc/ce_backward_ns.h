@@ -86,24 +86,26 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
 // measured law: 0.03 eps / NS_TRI_STIFF^2 = 3e-8)
 constexpr double NS_TRI_STIFF = 1e-5;
 
-template <bool FWD, bool REF = false, bool QP = false, bool TRI = false> struct NsFwdArg { typedef NsNoJvp type; };
+template <bool FWD, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false> struct NsFwdArg { typedef NsNoJvp type; };
 template <> struct NsFwdArg<true, false> { typedef NsJvp type; };
 template <> struct NsFwdArg<true, true> { typedef NsRefine type; };
 template <> struct NsFwdArg<true, false, true> { typedef NsJvpQp type; };
 template <> struct NsFwdArg<true, true, true> { typedef NsRefineQp type; };
 template <> struct NsFwdArg<true, false, false, true> { typedef NsJvpTri type; };
 template <> struct NsFwdArg<true, true, false, true> { typedef NsRefineTri type; };
+template <> struct NsFwdArg<false, false, false, false, true> { typedef NsMany type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well)
-template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false, bool TRI = false>
+template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false>
 __global__ void __launch_bounds__(NTHR, (NTHR == 256 ? ((QP || TRI) ? 2 : 3) : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI>::type W) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI, MANY>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP, "the adjoint with a quadratic objective lives in k_backward_rt");
     static_assert((FWD && !QP) || !TRI, "exponential / power triples: the forward modes with a linear objective (their adjoint lives in k_backward_rt)");
+    static_assert(!MANY || (!FWD && !QP && !TRI), "many cotangents on one factorisation: the adjoint with plain cones and a linear objective");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -289,7 +291,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int i = tid; i < m; i += NTHR) { const double yi = yg[(size_t)inst * m + i]; vv[i] = yi - sg[(size_t)inst * m + i]; tvec[i] = yi; }
             for (int j = tid; j < n; j += NTHR) rx[j] = xg[(size_t)inst * n + j];
         } else
-        for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; dv[i] = dyg[(size_t)inst * m + i]; }
+        for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; if constexpr (MANY) dv[i] = 0.0; else dv[i] = dyg[(size_t)inst * m + i]; }
         if (tid < 8) misc[tid] = 0;
         load_P();
         __syncthreads();
@@ -514,11 +516,17 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = 0.0;
             for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = 0.0; if (W.ds) W.ds[(size_t)inst * m + i] = 0.0; }
             if (tid == 0 && W.iters) W.iters[inst] = 0;
+        } else if constexpr (MANY) {          // (for every cotangent; the instance is listed once)
+            for (int kc = 0; kc < W.K; kc++) {
+                for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[kc * W.sAk + (size_t)inst * T.nnz_aug + k] = 0.0;
+                for (int j = tid; j <= n; j += NTHR) dqo[kc * W.sqk + j * sdqk + inst * sdqb] = 0.0;
+                if (tid == 0 && adj_status) adj_status[kc * W.sak + inst] = 2;
+            }
         } else {
             for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[(size_t)inst * T.nnz_aug + k] = 0.0;
             for (int j = tid; j <= n; j += NTHR) dqo[j * sdqk + inst * sdqb] = 0.0;
         }
-        if (tid == 0) { if (adj_status) adj_status[inst] = QP ? 4 : 2; if (fix) fix[1 + atomicAdd(fix, 1)] = inst; }          // (QP: no re-solve behind the launch, the zeros stand, flagged)
+        if (tid == 0) { if constexpr (!MANY) { if (adj_status) adj_status[inst] = QP ? 4 : 2; } if (fix) fix[1 + atomicAdd(fix, 1)] = inst; }          // (QP: no re-solve behind the launch, the zeros stand, flagged)
         return;
     }
     // ---- f = dx + A^T u  and  a_z = A_z^T z-hat  in ONE pass over the rows of the boundary cones (4 lanes per column, each takes every 4th cone; fixed summation order)
@@ -550,6 +558,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         acc = group_reduce<4, false>(acc);
         if constexpr (FWD) { if (j < n && part == 0) fvec[j] = acc - fvec[j]; }          // f = -g_x + sum theta a~^T gamma
+        else if constexpr (MANY) { if (j < n && part == 0) fvec[j] = acc; }          // (steps 1-4 run on a zero right-hand side: every cotangent comes behind the sweep)
         else
         if (j < n && part == 0) fvec[j] = acc + dxg[(size_t)inst * n + j];
     }
@@ -1061,12 +1070,133 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     });
     if (tiny && lane == 0) misc[2] |= 4;          // (every lane of every strip solved the same 4 x 4 blocks: the flag is uniform)
     NS_STAMP(7);
+    // ---- MANY: steps 1-4 ran on a zero right-hand side.  The sweep is an in-place inversion: the accumulator tiles hold -(Z^T H Z)^-1, the pivot columns of the
+    //      eliminated rows B_1^-1, their free columns R, the list rows a~ in the free columns and a in the pivot columns.  Everything a cotangent touches is rebuilt
+    //      from those, one cotangent after the other, and step 5 and the epilogue run per cotangent on the same buffers.
+    int nrhs = 1;
+    if constexpr (MANY) nrhs = W.K;
+    for (int kc = 0; kc < nrhs; kc++) {
+    const double *dxk = dxg, *dyk = dyg;
+    double *dAk = dAo, *dqk = dqo;
+    int *adjk = adj_status;
+    if constexpr (MANY) {
+        dxk += kc * W.sxk; dyk += kc * W.syk; dAk += kc * W.sAk; dqk += kc * W.sqk; if (adjk) adjk += kc * W.sak;
+        const double *const dxi = dxk + (size_t)inst * n;
+        __syncthreads();          // the output pass of the cotangent before has read vv, rx, fvec and dv
+        for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; dv[i] = dyk[(size_t)inst * m + i]; }
+        for (int j = tid; j < n; j += NTHR) rx[j] = 0.0;
+        __syncthreads();
+        // d = DPi(v) dy and the per-cone scalars from the retained classification (ckind, lambda, |z|); the weights u of f = dx + A^T u wait in qv2 BY ROW (the
+        // union region is free behind the sweep; tvec is the list's)
+        for (int i = tid; i < z + T.l; i += NTHR) if (rkind[i] != RK_EQ) dv[i] = 0.0;
+        for (int c0 = 0; c0 < nq; c0 += NTHR / 16) {
+            const int c = c0 + (tid >> 4), l16 = tid & 15;
+            const bool cv = c < nq;
+            const int r0 = cv ? T.qoff[c] : 0, r1 = cv ? T.qoff[c + 1] : 0;
+            const int kind = cv ? ckind[c] : 0;
+            const double lam = cv ? cinfo[5 * c] : 0.0, nz = kind == 2 ? cinfo[5 * c + 1] : 1.0;
+            const double t0 = cv ? vv[r0] : 0.0, h0 = cv ? dv[r0] : 0.0;
+            double zh = 0.0;
+            for (int i = r0 + 1 + l16; i < r1; i += 16) zh = fma(vv[i], dv[i], zh);
+            zh = group_reduce<16, false>(zh);
+            double zd = 0.0;
+            const double i2n = kind == 2 ? 1.0 / (2 * nz) : 0.0, cz = kind == 2 ? t0 * zh / (nz * nz) : 0.0;
+            for (int i = r0 + 1 + l16; i < r1; i += 16) {
+                if (kind == 1) dv[i] = 0.0;
+                else if (kind == 2) { const double w = vv[i]; const double di = (w * h0 + (t0 + nz) * dv[i] - w * cz) * i2n; dv[i] = di; zd = fma(w, di, zd); }
+            }
+            zd = group_reduce<16, false>(zd);
+            if (kind == 2) {
+                const double d0 = (nz * h0 + zh) * i2n, zdn = zd / nz, eyd = (d0 + zdn) * M_SQRT1_2, esd = (d0 - zdn) * M_SQRT1_2;
+                const double il = 1.0 / (1 - lam), k0c = (esd * (1 - il) - eyd * il) * M_SQRT1_2, kzc = (-esd * (1 - il) - eyd * il) * M_SQRT1_2, inz = 1.0 / nz;
+                for (int i = r0 + 1 + l16; i < r1; i += 16) qv2[i] = fma(il, dv[i], vv[i] * inz * kzc);
+                if (l16 == 0) { qv2[r0] = fma(il, d0, k0c); dv[r0] = d0; cinfo[5 * c + 2] = eyd; cinfo[5 * c + 3] = esd; }
+            } else if (kind == 1 && l16 == 0) dv[r0] = 0.0;
+        }
+        __syncthreads();
+        // d_B by equality (the numbering's source array was the elimination's to overwrite: eqrow and ceq are its inverse) -> mu
+        for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
+        for (int c = tid; c < nq; c += NTHR) if (ckind[c] == 2) mu[ceq[c]] = cinfo[5 * c + 2];
+        __syncthreads();
+        // d~ = B_1^-1 d_B from the in-place inverse (entry (e, i) in row e at the pivot column of i; a dropped row has none): 16 lanes per equality
+        for (int e0 = 0; e0 < neq; e0 += NTHR / 16) {
+            const int e = e0 + (tid >> 4), part = tid & 15;
+            double a = 0.0;
+            const int pc = e < neq ? pcol[e] : -1;
+            if (pc >= 0) { const double *row = sm + erow[e]; for (int i = part; i < neq; i += 16) { const int pi = pcol[i]; if (pi >= 0) a = fma(row[pi], mu[i], a); } }
+            a = group_reduce<16, false>(a);
+            if (e < neq && part == 0) dB[e] = pc >= 0 ? a : 0.0;
+        }
+        __syncthreads();
+        // t_q = a_q . x_p = sum_e a_q[p_e] d~_e for the z-rows of the list (the pivot columns of a list row are as loaded): 4 lanes per row
+        auto list_t = [&]() {
+            for (int q0 = 0; q0 < KW; q0 += NTHR / 4) {
+                const int q = q0 + (tid >> 2), part = tid & 3;
+                const bool live = q < KW && wsrc[q < KW ? q : 0] >= 0;
+                double a = 0.0;
+                if (live) { const double *row = sm + wrow[q]; for (int e = part; e < neq; e += 4) { const int pc = pcol[e]; if (pc >= 0) a = fma(row[pc], dB[e], a); } }
+                a = group_reduce<4, false>(a);
+                if (live && part == 0) tvec[q] = a;
+            }
+        };
+        list_t();
+        __syncthreads();
+        // per boundary cone, with a_0 = sqrt 2 a_y - a_z and a_z = sum z-hat_i a_i (neither row is stored any more):  A_c^T u = sqrt 2 u_0 a_y + sum u'_i a_i,
+        // u'_i = u_i - u_0 z-hat_i.  The a_y share is a row of B: it moves the multiplier of the cone's equality by sqrt 2 u_0 (behind step 5) and drops out of
+        // Z^T f.  The list takes theta q'_i = theta (t_i - z-hat_i (z-hat . t)), so that Z^T H x_p = sum theta q'_i a~_i needs no a_z either.
+        for (int c = tid; c < nq; c += NTHR) {
+            if (ckind[c] != 2) continue;
+            const int r0 = T.qoff[c], r1 = T.qoff[c + 1], qb = cbase[c];
+            const double inz = 1.0 / cinfo[5 * c + 1], th = cinfo[5 * c + 4], u0 = qv2[r0];
+            double zt = 0.0;
+            for (int i = r0 + 1; i < r1; i++) zt = fma(vv[i], tvec[qb + i - r0 - 1], zt);
+            zt *= inz;
+            for (int i = r0 + 1; i < r1; i++) { const double zhi = vv[i] * inz; qv2[i] -= u0 * zhi; tvec[qb + i - r0 - 1] = th * (tvec[qb + i - r0 - 1] - zhi * zt); }
+        }
+        __syncthreads();
+        // f' = dx + sum u'_i a_i by column: a pivot column keeps f'[piv] (the multipliers want it), a free column takes  dx + sum (u'_i - theta q'_i) a~_i, which
+        // lacks only -R^T dx[piv] of the reduced right-hand side Z^T (f' - H x_p).  4 lanes per column, fixed summation order.
+        for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
+            const int j = j0 + (tid >> 2), part = tid & 3;
+            double a = 0.0, b = 0.0;
+            if (j < n) for (int q = part; q < KW; q += 4) {
+                const int ws = wsrc[q];
+                if (ws >= 0) { const double av = sm[wrow[q] + j]; a = fma(av, qv2[ws], a); b = fma(av, tvec[q], b); }
+            }
+            a = group_reduce<4, false>(a); b = group_reduce<4, false>(b);
+            if (j < n && part == 0) fvec[j] = dxi[j] + a - (cmap[j] >= 0 ? b : 0.0);
+        }
+        __syncthreads();
+        list_t();          // (tvec holds t again: step 5 adds a~ . x_free to it)
+        for (int j = tid; j < n; j += NTHR) {
+            if (cmap[j] < 0) continue;
+            double a = fvec[j];
+            for (int e = 0; e < neq; e++) { const int pc = pcol[e]; if (pc >= 0) a = fma(-sm[erow[e] + j], dxi[pc], a); }
+            fvec[j] = a;
+        }
+        __syncthreads();
+        // x_free = (Z^T H Z)^-1 rhs out of the accumulator tiles: this lane's entries of its four strip rows against the tile columns, summed over the 16 lanes of a row
+        if (wave < NTILE) {
+            double rr[NTILE];
+#pragma unroll
+            for (int J = 0; J < NTILE; J++) { const int colr = 16 * J + lc; rr[J] = colr < nf ? fvec[fcol[colr < nf ? colr : 0]] : 0.0; }
+            static_for<4>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                double sacc = 0.0;
+                static_for<NTILE>([&](auto Jc) { constexpr int J = decltype(Jc)::value; sacc = fma(acc[J][r], rr[J], sacc); });
+                sacc = group_reduce<16, false>(sacc);
+                const int rowi = 16 * wave + lg + 4 * r;
+                if (lc == 0 && rowi < nf) rx[fcol[rowi]] = -sacc;
+            });
+        }
+    } else {
     // ---- 5. solution: x_free from the right-hand-side column, x_piv = d~ - R x_free
     if (wave < NTILE) {
         static_for<NTILE>([&](auto Jc) {
             constexpr int J = decltype(Jc)::value;
             static_for<4>([&](auto rc) { constexpr int r = decltype(rc)::value; const int rowi = 16 * wave + lg + 4 * r; if (16 * J + lc == cr && rowi < nf) rx[fcol[rowi]] = acc[J][r]; });
         });
+    }
     }
     __syncthreads();
     // q_k = a_k . r_x = t_k + a~_k . x_free for the z-rows of boundary cones (pivot entries of r_x are still 0; the a_z entries of the list are skipped: their
@@ -1232,6 +1362,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         return;
         }
     }
+    if constexpr (MANY) {          // the a_y share of f, taken out of f' above: mu_c = mu'_c - sqrt 2 u_0 (qv2 of a t-row is not step 5's to write)
+        for (int c = tid; c < nq; c += NTHR) if (ckind[c] == 2 && pcol[ceq[c]] >= 0) dB[ceq[c]] -= M_SQRT2 * qv2[T.qoff[c]];
+        __syncthreads();
+    }
     // ---- r_y (as k_backward_rt; the t-row of a boundary cone holds a_y: a_0 . r_x = sqrt 2 (a_y . r_x) - a_z . r_x)
     for (int i = tid; i < z + T.l; i += NTHR) vv[i] = (eqrow[i] >= 0) ? dB[eqrow[i]] : dv[i];
     for (int c = tid; c < nq; c += NTHR) {
@@ -1260,8 +1394,8 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     for (int i = tid; i < m; i += NTHR) ys[i] = yg[(size_t)inst * m + i];
     __syncthreads();
     {
-        constexpr int OU = 8;
-        double *const dArow = dAo + (size_t)inst * T.nnz_aug;
+        constexpr int OU = MANY ? 6 : 8;          // (MANY: the accumulator tiles stay live across the cotangents; eight entries in flight spill beside them)
+        double *const dArow = dAk + (size_t)inst * T.nnz_aug;
         const int nnz = T.nnz_aug;
         for (int k0 = tid; k0 < nnz; k0 += OU * NTHR) {
             int ii[OU], jj[OU];
@@ -1280,12 +1414,13 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
         }
     }
-    for (int j = tid; j <= n; j += NTHR) dqo[j * sdqk + inst * sdqb] = (j < n) ? -rx[j] : 0.0;
+    for (int j = tid; j <= n; j += NTHR) dqk[j * sdqk + inst * sdqb] = (j < n) ? -rx[j] : 0.0;
     if (tid == 0) {
         const int fl = misc[2];
-        if (adj_status) adj_status[inst] = fl;
-        if (fix && (fl & 4)) fix[1 + atomicAdd(fix, 1)] = inst;      // rank-deficient system: diffcp's LSQR element replaces this answer (ce_vjp_qp)
+        if (adjk) adjk[inst] = fl;
+        if (fix && (fl & 4) && kc == 0) fix[1 + atomicAdd(fix, 1)] = inst;      // rank-deficient system: diffcp's LSQR element replaces this answer (ce_vjp_qp); MANY: listed once for all cotangents
     }
+    }          // (the cotangents)
 #ifdef CE_TIMING
     NS_STAMP(10);
     if (tid < 10) dAo[(size_t)inst * T.nnz_aug + tid] = (double)(tstamp[tid + 1] - tstamp[tid]);

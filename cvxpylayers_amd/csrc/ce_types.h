@@ -47,6 +47,12 @@ struct NsJvp {
     int *iters;              // [B] <- 0: a directly solved instance took no LSQR iteration (NULL: not wanted)
 };
 struct NsNoJvp {};
+// k_backward_ns<..., MANY = true> (the adjoint of plain cones with a linear objective): K cotangents on one factorisation of the instance (cone_engine.hip
+// ce_vjp_many).  CeBwdArgs' dx, dy, dA, dq and adj point at cotangent 0; cotangent k lies the strides below further (elements; syk = 0: one dy for all)
+struct NsMany {
+    int K;
+    long sxk, syk, sAk, sqk, sak;
+};
 // k_backward_ns<..., FWD = true, REF = true>: one safeguarded Newton step on the KKT residual (cone_engine.hip ce_refine).  The kernel reads the instance's b through
 // bpos and c from q, updates x, y, s IN PLACE when the step is kept, and keeps the per-instance record of the call (one launch = one step)
 struct NsRefine {
@@ -206,6 +212,7 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineQp &w);
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpTri &w);          // (a third object: exponential / power triples)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineTri &w);
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsMany &w);               // (a fourth object, ce_tu_ns_many.hip: the adjoint for K cotangents)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -240,6 +247,7 @@ hipError_t ce_setattr_bwd_rt_psd(int bytes);
 hipError_t ce_setattr_ns(int bytes);
 hipError_t ce_setattr_ns_qp(int bytes);
 hipError_t ce_setattr_ns_tri(int bytes);
+hipError_t ce_setattr_ns_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

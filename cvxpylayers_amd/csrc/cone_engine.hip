@@ -111,7 +111,8 @@ struct ce_engine {
     int last_sa_fwd = -1, last_sa_lsqr = -1;       // rows of CE_SA_FWD_VARIANTS / CE_SA_LSQR_VARIANTS the last such launch ran (-1: none yet; ce_get_plan)
     int lsqr_variant = 0;                          // 0: LSQR, 1: LSMR (ce_set_lsqr_variant; the calls that solve EVERY instance iteratively: ce_vjp_shared_a, ce_vjp_lsqr)
     DevBuf<int> d_summary; unsigned summary_next = 0;   // ce_status_summary staging (8 slots of 3 ints)
-    DevBuf<double> d_qT;         // batch-major copy of the objective values for the LSQR adjoint kernels (vjp_lsqr_launch)
+    DevBuf<double> d_dy0;        // ce_vjp_many with dy == NULL: one zero dy [B][m] that every cotangent reads
+    DevBuf<double> d_qT;       // batch-major copy of the objective values for the LSQR adjoint kernels (vjp_lsqr_launch)
     DevBuf<double> d_aa_ws;      // Anderson-acceleration history of the shared-A forward kernel ([B][4][lp])
     DevBuf<unsigned long long> d_psd_stats;        // CE_PSD_STATS=1: counters of the PSD projection (printed to stderr by ce_destroy)
     int psd_first = 0;           // first row of the first PSD block (m when the template has none)
@@ -263,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -309,6 +310,9 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
 int ce_adjoint_ns_variant(ce_handle h) { return h ? h->plan.ns_variant : -1; }
 int ce_qp_ns_variant(ce_handle h) { return h ? h->plan.qp_ns_variant : -1; }
 int ce_tri_ns_variant(ce_handle h) { return h ? h->plan.tri_ns_variant : -1; }
+// the many-cotangent mode rebuilds every cotangent's vectors in the buffers of the plain adjoint: its row and footprint are ns_variant's, and like the kernel
+// behind ce_vjp it only runs in front of the LSQR re-solve
+int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -577,6 +581,60 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     }
     HIPCHK(hipGetLastError());
     return flush_dispatch_order(h, st, nullptr, nullptr);
+}
+
+// K cotangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., MANY> factors every instance once and writes all K answers; the instances
+// it lists as rank deficient are listed ONCE, and the LSQR kernel walks that list once per cotangent with the cotangent's pointers.  The list parity flips once.
+// Without an armed re-solve (q_vals == NULL, ce_set_adjoint_resolve(h, 0)) ce_vjp itself does not run the elimination: K calls of it then, the same rule.
+int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (ce_vjp_many_variant(h) < 0) {
+        g_err = "ce_vjp_many: this template has no many-cotangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, "
+                "CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp once per cotangent";
+        return CE_E_UNSUPPORTED;
+    }
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_vjp_many: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = T.n, m = T.m, nnz = T.nnz_aug;
+    long syk = (long)((size_t)B * m);
+    if (!dy) {
+        HIPCHK(h->d_dy0.reserve((size_t)B * m));
+        HIPCHK(hipMemsetAsync(h->d_dy0.get(), 0, sizeof(double) * (size_t)B * m, st));
+        dy = h->d_dy0.get(); syk = 0;
+    }
+    const NsMany W{K, (long)((size_t)B * n), syk, (long)((size_t)B * nnz), (long)((size_t)B * (n + 1)), (long)B};
+    if (!(h->resolve && q_vals)) {
+        for (int k = 0; k < K; k++) {
+            const int rc = ce_vjp(h, B, A_vals_bm, 1, (long)nnz, q_vals, sq_k, sq_b, x, y, s, dx + k * W.sxk, dy + k * W.syk, dA_vals + k * W.sAk, 1, (long)nnz,
+                                  dq_vals + k * W.sqk, 1, (long)(n + 1), adj_status ? adj_status + k * W.sak : nullptr, stream);
+            if (rc) return rc;
+        }
+        return CE_OK;
+    }
+    FixLists fix{nullptr, nullptr};
+    int rc = resolve_lists(h, B, st, &fix);
+    if (rc) return rc;
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
+    ba.adj = adj_status; ba.fix = fix.cur;
+    h->last_fast = -1;
+    if (ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG; }
+    const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
+    const int prof_keep = h->prof; h->prof = 0;
+    for (int k = 0; k < K && !rc; k++)
+        rc = vjp_lsqr_launch(h, grid, A_vals_bm, (long)nnz, 1, q_vals, sq_k, sq_b, x, y, s, dx + k * W.sxk, dy + k * W.syk, dA_vals + k * W.sAk, dq_vals + k * W.sqk, 1, (long)(n + 1),
+                             adj_status ? adj_status + k * W.sak : nullptr, nullptr, h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, fix.cur, 4 | 8, fix.oth);
+    h->fix_par ^= 1;
+    h->prof = prof_keep;
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return CE_OK;
 }
 
 // summary of an int32 vector v[B] (status of a forward call, or adj_status of a backward call): out[0] = min v, out[1] = #{v == 2} ("solved,

@@ -38,6 +38,7 @@ class ConeEngine:
         self.A_is_constant = A_is_constant          # structural answer of MI355_ctx (parameter map), when the layer supplied it; None: decided per call from the values
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
+        self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
@@ -353,6 +354,44 @@ class ConeEngine:
                                dq.data_ptr(), B, 1, adj.data_ptr(), self._stream())
         _lib.check(rc, "ce_vjp")
         return (dA if batch_minor_out else dA.t()), dq, adj
+
+    def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False):
+        """K cotangents at one solution: dx (K, B, n), dy (K, B, m) or None (zero).  Returns dA (K, B, nnz_aug), dq (K, B, n+1), adj (K, B) -- and dP (K, B, nnz_p) when
+        P_bm is given -- all batch-major.  For every k the result is what vjp returns for (dx[k], dy[k]).
+        One ce_vjp_many call (each instance factored once, last_vjp_many_path == "many") under the rule that sends vjp to the search-free elimination: path
+        "per_instance", q_eval given, no P, and a template with the mode (ce_vjp_many_variant >= 0).  Every other case -- the dense / LSQR / shared-A paths, a quadratic
+        objective inside the kernels, templates without the mode, force_loop -- is K calls of vjp, stacked ("loop"): the method is total, and the loop is the comparator."""
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        K, B = int(dx.shape[0]), int(A_bm.shape[0])
+        if path is None:
+            path = self.last_path
+        many = (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
+        self.last_vjp_many_path = "many" if many else "loop"
+        if B == 0 or K == 0:
+            out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
+            return out + ((torch.empty((K, B, self.nnz_p), **f64),) if P_bm is not None else ())
+        dx = dx.to(**f64).contiguous()
+        dy = None if dy is None else dy.to(**f64).contiguous()
+        if not many:
+            zero_dy = torch.zeros((B, self.m), **f64) if dy is None else None
+            outs = [self.vjp(A_bm, x, y, s, dx[k], zero_dy if dy is None else dy[k], P_bm=P_bm, path=path, lsqr=lsqr, q_eval=q_eval) for k in range(K)]
+            res = (torch.stack([o[0].t() for o in outs]).contiguous(), torch.stack([o[1].t() for o in outs]).contiguous(), torch.stack([o[2] for o in outs]))
+            return res + ((torch.stack([o[3] for o in outs]),) if P_bm is not None else ())
+        A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
+        xc, yc, sc_ = (t.to(torch.float64).contiguous() for t in (x, y, s))
+        qd, q_args = self._q_args(q_eval)
+        rule = unpack_rule(lsqr, self.n, self.m)[:4]
+        if rule[:3] != self._resolve_rule:
+            _lib.check(_lib.lib().ce_set_adjoint_resolve(self._h, 1, float(rule[0]), float(rule[1]), 1e8, int(rule[2])), "ce_set_adjoint_resolve")
+            self._resolve_rule = rule[:3]
+        dA = torch.empty((K, B, self.nnz_aug), **f64)
+        dq = torch.empty((K, B, self.n + 1), **f64)
+        adj = torch.empty((K, B), dtype=torch.int32, device=dev)
+        rc = _lib.lib().ce_vjp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                    None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
+        _lib.check(rc, "ce_vjp_many")
+        return dA, dq, adj
 
     def _q_args(self, q_eval):
         """(tensor to keep alive, (pointer, stride0, stride1)) of an optional (n+1, B) objective as the C ABI takes it; None -> (None, (None, 0, 0))"""

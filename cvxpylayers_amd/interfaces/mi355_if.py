@@ -377,6 +377,41 @@ class _ConeLayer(torch.autograd.Function):
         return dP, dq, dA, None, None, None, None
 
 
+def adjoint_many(backward_data, dprimal, ddual, info=None):
+    """K cotangents through the node whose forward returned `backward_data` (its fourth output), with no autograd graph: dprimal (K, B, n) and / or ddual (K, B, m),
+    either may be None.  Applies what _ConeLayer.backward applies -- device moves, the `failed` mask of a raise_on_error=False call (a zero cotangent at a zero point:
+    the caller turns those instances' rows into NaN like their outputs), the saved path / lsqr rule / q_eval, note_adjoint_flags on the OR over the cotangents,
+    info["adjoint"]["status"] as (K, B) -- and calls ConeEngine.vjp_many.  Returns dA (K, B, nnz_aug), dq (K, B, n + 1), dP (K, B, nnz_p) or None, all batch-major
+    on the engine's device, and the `failed` mask or None."""
+    saved, batch_size, _unbatched, _in_device = backward_data
+    if saved is None:
+        raise RuntimeError("adjoint_many called on a layer evaluated with needs_grad=False")
+    if saved.lpgd is not None:
+        raise NotImplementedError("MI355 solver: solver_args mode='lpgd' / 'lpgd_left' / 'lpgd_right' has no Jacobian: its gradient is not linear in the cotangent")
+    eng, x, y, s, failed = saved.eng, saved.x, saved.y, saved.s, saved.failed
+    ref = dprimal if dprimal is not None else ddual
+    K = int(ref.shape[0])
+    with torch.cuda.device(eng.device):
+        f64 = dict(device=eng.device, dtype=torch.float64)
+        dx = dprimal.to(**f64).contiguous() if dprimal is not None else torch.zeros((K, batch_size, eng.n), **f64)
+        dy = ddual.to(**f64).contiguous() if ddual is not None else None
+        if failed is not None:
+            keep = ~failed[:, None]
+            dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
+            x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
+        out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm)
+        dA, dq, adj = out[:3]
+        dP = out[3] if saved.P_bm is not None else None
+        if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
+            info["adjoint"]["status"] = adj
+        if K > 0 and batch_size > 0:
+            any_k = adj[0].clone()
+            for k in range(1, K):
+                any_k |= adj[k]
+            eng.mailbox.note_adjoint_flags(any_k, batch_size)
+    return dA, dq, dP, failed
+
+
 class _CvxpyLayer:
     """What get_torch_cvxpylayer("MI355") returns: `apply(P_eval, q_eval, A_eval, cl_ctx, solver_args, needs_grad, warm_start)
     -> (primal, dual, aux, data)` like every reference plugin (torch/cvxpylayer.py:475-483).  A linear objective goes straight to

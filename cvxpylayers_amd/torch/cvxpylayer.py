@@ -449,6 +449,81 @@ class CvxpyLayer(torch.nn.Module):
             out = out + (self._value(P_eval, q_eval, A_eval, primal, dual, info, solver_args),)
         return out
 
+    def jacobian(self, *params: torch.Tensor, solver_args: dict | None = None, max_bytes: int = 1 << 30):
+        """outs, jac = layer.jacobian(*params): `outs` is what forward returns, detached; jac[i][j] = d outs[i] / d params[j] per instance, of shape
+        batch + var_i.shape + param_j.shape (both index groups in torch's row-major order), float64, on the parameters' device.  A parameter passed unbatched into a
+        batched call is differentiated per instance (its expanded copy), not summed over the batch.
+
+        No autograd graph anywhere: one plugin forward, then one cotangent per output element (the rows of the transposed recovery maps, the same for every instance)
+        through interfaces.mi355_if.adjoint_many -- ConeEngine.vjp_many: each instance is factored once per chunk, not once per output element -- and the transposed
+        parameter maps on the (K B, .) views.  The cotangents go in chunks whose dA stays within max_bytes (K_chunk B nnz_aug 8 bytes, at least one cotangent); a
+        cotangent's result does not depend on the chunk it travels in.  Instances a raise_on_error=False call masks return NaN rows, like their outputs.
+        Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family."""
+        from cvxpylayers_amd.interfaces.mi355_if import adjoint_many
+        from cvxpylayers_amd.interfaces.solver_args import LPGD_MODES
+        solver_args = solver_args or {}
+        if self.template.gp:
+            raise NotImplementedError("CvxpyLayer.jacobian: gp=True layers are not served (the log / exp maps around the cone program are outside the Jacobian assembled here)")
+        merged = {**self.ctx.solver_ctx.options, **solver_args}
+        if merged.get("mode") in LPGD_MODES:
+            raise NotImplementedError(f"CvxpyLayer.jacobian: solver_args mode={merged.get('mode')!r} has no Jacobian: the LPGD gradient is not linear in the cotangent")
+        if int(max_bytes) <= 0:
+            raise ValueError(f"max_bytes must be positive, got {max_bytes!r}")
+        batch = self.validate_params(list(params))
+        if params[0].device.type != "cuda":
+            raise RuntimeError("MI355 solver needs parameters on a ROCm device; there is no CPU fallback (use solver='DIFFCP' on CPU)")
+        dev = params[0].device
+        tpl = self.template
+        with torch.no_grad(), torch.cuda.device(dev):
+            p_bm = self._flatten_params([p.detach() for p in params], batch).contiguous()
+            (fA, bA), (fq, bq) = self._A.on(dev), self._q.on(dev)
+            A_bm, q_bm = _spmm_bm(fA, p_bm), _spmm_bm(fq, p_bm)
+            P_eval = _spmm_bm(self._P.on(dev)[0], p_bm).t() if self._P is not None else None
+            A_eval, q_eval = A_bm.t(), q_bm.t()
+            if not batch:
+                A_eval, q_eval = A_eval.squeeze(1), q_eval.squeeze(1)
+                P_eval = P_eval.squeeze(1) if P_eval is not None else None
+            primal, dual, info, data = get_torch_cvxpylayer(self.solver).apply(P_eval, q_eval, A_eval, self.ctx, solver_args, True, None)
+            self.info = info
+            saved = data[0]
+            if self._P is not None and saved.P_bm is None:
+                raise NotImplementedError("CvxpyLayer.jacobian: this quadratic objective reaches the engine as a torch-op epigraph (QuadEpigraph), whose derivative "
+                                          "lives in autograd; only a quadratic objective inside the kernels is served")
+            outs = self._recover_results(primal, dual, batch) if self.fused_recovery else self._recover_results_torch(primal, dual, batch)
+            B = batch[0] if batch else 1
+            eng = saved.eng
+            sizes = [int(np.prod(s)) if len(s) else 1 for s in tpl.param_shapes]
+            k_chunk = max(1, int(max_bytes) // max(1, B * eng.nnz_aug * 8))
+            sym_perm = None
+            if saved.P_bm is not None and not self.ctx.solver_ctx.quad.one_triangle:          # (the plugin symmetrises P_eval in front of the kernels: its transpose here)
+                sym_perm = torch.from_numpy(self.ctx.solver_ctx.quad.sym_perm).to(eng.device)
+            jac: list = [None] * len(tpl.var_recover)
+            for source in ("primal", "dual"):
+                if source not in self._rec:
+                    continue
+                csr, layout = self._rec[source]
+                total = int(csr.mat.shape[0])
+                g_all = torch.empty((total, B, tpl.n_params_total + 1), dtype=torch.float64, device=eng.device)
+                for t0 in range(0, total, k_chunk):
+                    t1 = min(total, t0 + k_chunk)
+                    rows = torch.from_numpy(csr.mat[t0:t1].toarray()).to(eng.device)          # one cotangent per output element: a row of the recovery map
+                    cot = rows[:, None, :].expand(t1 - t0, B, rows.shape[1]).contiguous()
+                    dA, dq, dP, failed = adjoint_many(data, cot if source == "primal" else None, cot if source == "dual" else None, info)
+                    g = g_all[t0:t1].view((t1 - t0) * B, -1)
+                    _spmm_bm(bA, dA.view((t1 - t0) * B, -1), out=g.zero_())
+                    _spmm_bm(bq, dq.view((t1 - t0) * B, -1), out=g)
+                    if dP is not None:
+                        if sym_perm is not None:
+                            dP = 0.5 * (dP + dP.index_select(2, sym_perm))
+                        _spmm_bm(self._P.on(dev)[1], dP.contiguous().view((t1 - t0) * B, -1), out=g)
+                if saved.failed is not None:
+                    g_all = torch.where(saved.failed[None, :, None], float("nan"), g_all)
+                for pos, off, size in layout:
+                    vshape = tuple(tpl.var_recover[pos].shape)
+                    jac[pos] = tuple(g_all[off:off + size, :, po:po + ps].permute(1, 0, 2).reshape(batch + vshape + tuple(pshape)).to(dev)
+                                     for po, ps, pshape in zip(tpl.col_offsets, sizes, tpl.param_shapes))
+        return tuple(o.detach() for o in outs), tuple(jac)
+
     def _value(self, P_eval, q_eval, A_eval, primal, dual, info, solver_args):
         """the optimal value behind the plugin call (see forward): masked instances of a raise_on_error=False call are NaN and contribute no gradient"""
         merged = {**self.ctx.solver_ctx.options, **solver_args}

@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -490,6 +490,25 @@ int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, do
  * vanishing pivot flags the instance for the LSQR re-solve) -- plain-cone templates with a linear objective and n <= 108; the value is the tile variant.
  * -1: the pivoting elimination kernels (k_backward_rt / k_backward) serve every call.  Introspection for tests / bench. */
 int ce_adjoint_ns_variant(ce_handle h);
+
+/* MANY COTANGENTS AT ONE SOLUTION: for every k < K what ce_vjp returns for (dx[k], dy[k]) under the same ce_set_adjoint_resolve rule, from ONE factorisation per
+ * instance.  The matrix work of the search-free elimination (row-echelon form of the equality rows, null-space transform, reduced Hessian, blocked sweep) depends on
+ * (A, x, y, s) alone; the sweep is an in-place inversion, so the kernel keeps (Z^T H Z)^-1 and B_1^-1 and rebuilds per cotangent only the classification-weighted
+ * vectors, two short triangular replays, one product with the stored inverse and the dA row (csrc/ce_backward_ns.h, MANY).  A Jacobian of the solution map, several
+ * loss heads on one layer and Gauss-Newton outer loops are K cotangents at one solution.
+ *   A_vals_bm  batch-major rows, sA_b = nnz_aug apart (as ce_jvp takes them);  q_vals as ce_vjp (NULL: no re-solve, K plain ce_vjp calls inside)
+ *   dx [K][B][n], dy [K][B][m] contiguous (dy NULL: zero);  dA_vals [K][B][nnz_aug] and dq_vals [K][B][n + 1] contiguous batch-major, boundary convention of ce_vjp;
+ *   adj_status [K][B] (or NULL): the bit field of ce_vjp.  Rank deficiency is a property of the matrix: bits 4 and 8 are equal across k for an instance, which is
+ *   listed for the LSQR re-solve once; the LSQR kernel walks that list once per cotangent.  Bit 1 is per cotangent.
+ * K == 1 is legal.  CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0.  CE_E_UNSUPPORTED with a ce_last_error that names the reason
+ * when ce_vjp_many_variant(h) < 0.  Batch-minor outputs are not served.  No host synchronisation, no allocation after the first call of a batch size. */
+int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                double *dA_vals, double *dq_vals, int *adj_status, void *stream);
+/* >= 0: the template has the many-cotangent mode; the value is the tile variant, ce_adjoint_ns_variant's (the mode rebuilds every cotangent's vectors in the plain
+ * adjoint's buffers: same footprint, the launch plan is unchanged).  -1: PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108,
+ * CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS. */
+int ce_vjp_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
