@@ -55,6 +55,17 @@
 // REF: y-hat of a triple is exp_project_dual / pow_project_dual_of_entry from the cold start exp_dual_eig / pow_dual_eig evaluate at -- the same decision, the
 // rule of ns_soc_kind.  W and lambda live behind the index arrays in LDS (ns_layout's TRI mode).
 //
+// MANY = true: K right-hand sides on ONE factorisation of the instance.  Steps 1-4 depend on (A, x, y, s [, P]) alone and run once, on a zero right-hand side; the sweep is an
+// in-place inversion, so -(Z^T (H [+ P]) Z)^-1 stays in the accumulator tiles and B_1^-1 in the pivot columns, and each right-hand side is rebuilt behind the sweep, then
+// step 5 and the mode's epilogue run on the same buffers.  Without FWD (cone_engine.hip ce_vjp_many): K cotangents of the plain adjoint.  With FWD, QP or not
+// (ce_jvp_many, ce_jvp_qp_many): K tangents -- per tangent the forward PROLOGUE again (x and y re-read from global memory: the tangent products need the tangent's values
+// and the point, not A, which is transformed by now; a tangent's row lies at k * stride_k + inst * stride_b, stride_b == 0 being one row for the whole batch), gamma and
+// the weights of f from the retained classification, d~ from the in-place inverse, t_q for the list rows (QP: Z^T P x_p from the transformed rows of P, whose pivot
+// columns are untouched), f with the treatment of the two rows that are gone (a_z, and the t-row a_y overwrote), x_free from the tiles, step 5 and the forward EPILOGUE
+// unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  TRI templates keep K launches of the single-tangent kernel:
+// NS_TRI_STIFF below lists an instance for a stiff weighted triple row, a rule of the forward derivative alone that rides on the triples' own footprint and frames --
+// `flagged` is still the matrix's there, but no many-mode is planned on that footprint.  REF never comes with MANY.
+//
 // Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes.  PSD cones keep k_backward_rt, and so does the ADJOINT
 // with triples or with a quadratic objective.
 #pragma once
@@ -94,6 +105,8 @@ template <> struct NsFwdArg<true, true, true> { typedef NsRefineQp type; };
 template <> struct NsFwdArg<true, false, false, true> { typedef NsJvpTri type; };
 template <> struct NsFwdArg<true, true, false, true> { typedef NsRefineTri type; };
 template <> struct NsFwdArg<false, false, false, false, true> { typedef NsMany type; };
+template <> struct NsFwdArg<true, false, false, false, true> { typedef NsJvpMany type; };
+template <> struct NsFwdArg<true, false, true, false, true> { typedef NsJvpQpMany type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well)
@@ -105,7 +118,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP, "the adjoint with a quadratic objective lives in k_backward_rt");
     static_assert((FWD && !QP) || !TRI, "exponential / power triples: the forward modes with a linear objective (their adjoint lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !QP && !TRI), "many cotangents on one factorisation: the adjoint with plain cones and a linear objective");
+    static_assert(!MANY || (!FWD && !QP && !TRI) || (FWD && !REF && !TRI),
+                  "many right-hand sides on one factorisation: the adjoint with plain cones and a linear objective (K cotangents), or the forward derivative with plain "
+                  "cones, P or not (K tangents); templates with triples keep K launches");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -274,6 +289,55 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         return mxa / (1.0 + sca);
         }
     };
+    // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y [+ dP x] -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
+    //      (k_sa_lsqr<FWD>'s prologue: dA = -tA_eval, db = +tA_eval[bpos], dc = tq_eval[:n]).  The instance's tangent row is read through the template's CSC
+    //      (the value order itself) and CSR structure, 8 lanes per column / row, four entries in flight per lane; fixed summation order.
+    //      tA, tP: the instance's tangent rows; tq: its tangent of q_eval, entry j at tq[j * tqs]; NULL: zero.  MANY calls it once per tangent.
+    auto fwd_prologue = [&](const double *tA, const double *tq, long tqs, const double *tP) {
+        if constexpr (!FWD || REF) return;
+        else {
+        for (int j0 = 0; j0 < n; j0 += NTHR / 8) {
+            const int j = j0 + (tid >> 3), c8 = tid & 7;
+            double a0 = 0.0, a1 = 0.0;
+            if (tA && j < n) {
+                const int k1 = W.csc_ptr[j + 1];
+                for (int k = W.csc_ptr[j] + c8; k < k1; k += 32) {
+                    double tv[4]; int ri[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[kk]; ri[u] = T.rowidx[kk]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, tvec[ri[u]], a1); else a0 = fma(t, tvec[ri[u]], a0); }
+                }
+            }
+            double as = a0 + a1;
+            if constexpr (QP) {          // - (tP x)_j: row j of the tangent of P through the dense entry map
+                if (tP && j < n) {
+                    double pa = 0.0;
+                    for (int i = c8; i < n; i += 8) { const int k = W.Q.pmap[j * n + i]; pa = fma(k >= 0 ? tP[k >= 0 ? k : 0] : 0.0, rx[i], pa); }
+                    as -= pa;
+                }
+            }
+            const double a = group_reduce<8, false>(as);
+            if (j < n && c8 == 0) fvec[j] = (tq ? tq[j * tqs] : 0.0) - a;
+        }
+        for (int i0 = 0; i0 < m; i0 += NTHR / 8) {
+            const int i = i0 + (tid >> 3), c8 = tid & 7;
+            double a0 = 0.0, a1 = 0.0;
+            if (tA && i < m) {
+                const int k1 = W.csr_ptr[i + 1];
+                for (int k = W.csr_ptr[i] + c8; k < k1; k += 32) {
+                    double tv[4]; int ci[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[W.csr_src[kk]]; ci[u] = W.csr_col[kk]; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, rx[ci[u]], a1); else a0 = fma(t, rx[ci[u]], a0); }
+                }
+            }
+            const double a = group_reduce<8, false>(a0 + a1);
+            if (i < m && c8 == 0) { const int pb = tA ? W.bpos[i] : -1; dv[i] = (pb >= 0 ? tA[pb] : 0.0) + a; }
+        }
+        }
+    };
     NS_STAMP(0);
     // ---- load: the instance's values scattered into dense solver form A = -A_cvx (b is not needed: r_tau is pinned)
     {
@@ -287,6 +351,8 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         if constexpr (REF) {          // (in / out arrays: read through the pointers they are written through)
             for (int i = tid; i < m; i += NTHR) vv[i] = W.y[(size_t)inst * m + i] - W.s[(size_t)inst * m + i];
             for (int j = tid; j < n; j += NTHR) rx[j] = W.x[(size_t)inst * n + j];
+        } else if constexpr (FWD && MANY) {          // (steps 1-4 on a zero right-hand side: g_y = 0 here, f = 0 below; every tangent comes behind the sweep)
+            for (int i = tid; i < m; i += NTHR) { vv[i] = yg[(size_t)inst * m + i] - sg[(size_t)inst * m + i]; dv[i] = 0.0; }
         } else if constexpr (FWD) {          // (y and x wait in tvec and rx for the tangent products of the prologue below)
             for (int i = tid; i < m; i += NTHR) { const double yi = yg[(size_t)inst * m + i]; vv[i] = yi - sg[(size_t)inst * m + i]; tvec[i] = yi; }
             for (int j = tid; j < n; j += NTHR) rx[j] = xg[(size_t)inst * n + j];
@@ -312,52 +378,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         __syncthreads();
         rho0 = kkt_residual(rx, tvec, vv, true);
         if (W.first) rho_cur = rho0;
-    } else if constexpr (FWD) {
-        // ---- FWD prologue: g = dQ pi without its tau entry,  g_x = dc + dA^T y [+ dP x] -> fvec,  g_y = db - dA x -> dv,  with the tangents in the boundary convention
-        //      (k_sa_lsqr<FWD>'s prologue: dA = -tA_eval, db = +tA_eval[bpos], dc = tq_eval[:n]).  The instance's tangent row is read through the template's CSC
-        //      (the value order itself) and CSR structure, 8 lanes per column / row, four entries in flight per lane; fixed summation order.
-        const double *tA = W.tA ? W.tA + (size_t)inst * T.nnz_aug : nullptr;
-        for (int j0 = 0; j0 < n; j0 += NTHR / 8) {
-            const int j = j0 + (tid >> 3), c8 = tid & 7;
-            double a0 = 0.0, a1 = 0.0;
-            if (tA && j < n) {
-                const int k1 = W.csc_ptr[j + 1];
-                for (int k = W.csc_ptr[j] + c8; k < k1; k += 32) {
-                    double tv[4]; int ri[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[kk]; ri[u] = T.rowidx[kk]; }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, tvec[ri[u]], a1); else a0 = fma(t, tvec[ri[u]], a0); }
-                }
-            }
-            double as = a0 + a1;
-            if constexpr (QP) {          // - (tP x)_j: row j of the tangent of P through the dense entry map
-                if (W.Q.tP && j < n) {
-                    const double *tP = W.Q.tP + (size_t)inst * W.Q.nnz_p;
-                    double pa = 0.0;
-                    for (int i = c8; i < n; i += 8) { const int k = W.Q.pmap[j * n + i]; pa = fma(k >= 0 ? tP[k >= 0 ? k : 0] : 0.0, rx[i], pa); }
-                    as -= pa;
-                }
-            }
-            const double a = group_reduce<8, false>(as);
-            if (j < n && c8 == 0) fvec[j] = (W.tq ? W.tq[j * W.stqk + inst * W.stqb] : 0.0) - a;
-        }
-        for (int i0 = 0; i0 < m; i0 += NTHR / 8) {
-            const int i = i0 + (tid >> 3), c8 = tid & 7;
-            double a0 = 0.0, a1 = 0.0;
-            if (tA && i < m) {
-                const int k1 = W.csr_ptr[i + 1];
-                for (int k = W.csr_ptr[i] + c8; k < k1; k += 32) {
-                    double tv[4]; int ci[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const int kk = min(k + 8 * u, k1 - 1); tv[u] = tA[W.csr_src[kk]]; ci[u] = W.csr_col[kk]; }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) { const double t = (k + 8 * u < k1) ? tv[u] : 0.0; if (u & 1) a1 = fma(t, rx[ci[u]], a1); else a0 = fma(t, rx[ci[u]], a0); }
-                }
-            }
-            const double a = group_reduce<8, false>(a0 + a1);
-            if (i < m && c8 == 0) { const int pb = tA ? W.bpos[i] : -1; dv[i] = (pb >= 0 ? tA[pb] : 0.0) + a; }
-        }
+    } else if constexpr (FWD && !MANY) {
+        fwd_prologue(W.tA ? W.tA + (size_t)inst * T.nnz_aug : nullptr, W.tq ? W.tq + inst * W.stqb : nullptr, W.stqk, [&]() -> const double * {
+            if constexpr (QP) return W.Q.tP ? W.Q.tP + (size_t)inst * W.Q.nnz_p : nullptr; else return nullptr; }());
         __syncthreads();
     }
     NS_STAMP(1);
@@ -512,6 +535,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient / zero tangents; the LSQR launch behind this kernel serves it)
         if constexpr (REF) {
             if (tid == 0) { W.rstatus[inst] = rst0 | 4; if (W.first) W.resid[2 * (size_t)inst] = rho0; W.resid[2 * (size_t)inst + 1] = rho_cur; }
+        } else if constexpr (FWD && MANY) {          // (for every tangent; the instance is listed once)
+            for (int kc = 0; kc < W.K; kc++) {
+                for (int j = tid; j < n; j += NTHR) W.dx[kc * W.sxk + (size_t)inst * n + j] = 0.0;
+                for (int i = tid; i < m; i += NTHR) { W.dy[kc * W.syk + (size_t)inst * m + i] = 0.0; if (W.ds) W.ds[kc * W.syk + (size_t)inst * m + i] = 0.0; }
+                if (tid == 0) { if (W.iters) W.iters[kc * W.sak + inst] = 0; if (adj_status) adj_status[kc * W.sak + inst] = QP ? 4 : 2; }
+            }
         } else if constexpr (FWD) {
             for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = 0.0;
             for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = 0.0; if (W.ds) W.ds[(size_t)inst * m + i] = 0.0; }
@@ -557,7 +586,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
         }
         acc = group_reduce<4, false>(acc);
-        if constexpr (FWD) { if (j < n && part == 0) fvec[j] = acc - fvec[j]; }          // f = -g_x + sum theta a~^T gamma
+        if constexpr (FWD && !MANY) { if (j < n && part == 0) fvec[j] = acc - fvec[j]; }          // f = -g_x + sum theta a~^T gamma
         else if constexpr (MANY) { if (j < n && part == 0) fvec[j] = acc; }          // (steps 1-4 run on a zero right-hand side: every cotangent comes behind the sweep)
         else
         if (j < n && part == 0) fvec[j] = acc + dxg[(size_t)inst * n + j];
@@ -1079,7 +1108,127 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     const double *dxk = dxg, *dyk = dyg;
     double *dAk = dAo, *dqk = dqo;
     int *adjk = adj_status;
-    if constexpr (MANY) {
+    if constexpr (MANY && FWD) {
+        // ---- K tangents: what the forward prologue, the classification pass and the passes in front of step 1 leave in the buffers, rebuilt for tangent kc from the
+        //      retained state (rkind, ckind, cinfo's lambda, |z| and theta, eqrow / ceq, the in-place inverses, the list rows).  x and y come from global memory again (y
+        //      waits in tvec, x in rx, as in the single-tangent load): the tangent products need the tangent's values and the point, not A, which is transformed by now.
+        if (adjk) adjk += kc * W.sak;
+        const double *const tAk = W.tA ? W.tA + kc * W.stAk + (size_t)inst * W.stAb : nullptr;          // (stAb == 0: one tangent row for the whole batch; tq, tP alike)
+        const double *const tqk = W.tq ? W.tq + kc * W.stqk + (size_t)inst * W.stqb : nullptr;
+        const double *tPk = nullptr;
+        if constexpr (QP) tPk = W.Q.tP ? W.Q.tP + kc * W.stPk + (size_t)inst * W.stPb : nullptr;
+        __syncthreads();          // the output pass of the tangent before has read vv, rx and dv
+        for (int i = tid; i < m; i += NTHR) { const double yi = yg[(size_t)inst * m + i]; vv[i] = yi - sg[(size_t)inst * m + i]; tvec[i] = yi; }
+        for (int j = tid; j < n; j += NTHR) rx[j] = xg[(size_t)inst * n + j];
+        __syncthreads();
+        fwd_prologue(tAk, tqk, 1, tPk);          // g_x -> fvec, g_y -> dv (dv keeps it unrotated up to the epilogue)
+        __syncthreads();
+        // per boundary cone gamma_y, gamma_s and the weights u_i = theta (g_i - z-hat_i (z-hat . g_z)) of its z-rows, from the retained lambda, |z|, theta; the weights
+        // wait in qv2 BY ROW (the union region is free behind the sweep; tvec is the list's).  The t-row has weight 0: f has no a_y share here.
+        for (int c0 = 0; c0 < nq; c0 += NTHR / 16) {
+            const int c = c0 + (tid >> 4), l16 = tid & 15;
+            const bool cv = c < nq && ckind[c < nq ? c : 0] == 2;
+            const int r0 = cv ? T.qoff[c] : 0, r1 = cv ? T.qoff[c + 1] : 0;
+            const double h0 = cv ? dv[r0] : 0.0, nz = cv ? cinfo[5 * c + 1] : 1.0, th = cv ? cinfo[5 * c + 4] : 0.0;
+            double zh = 0.0;
+            for (int i = r0 + 1 + l16; i < r1; i += 16) zh = fma(vv[i], dv[i], zh);
+            zh = group_reduce<16, false>(zh);
+            const double zeta = zh / nz, inz = 1.0 / nz;
+            for (int i = r0 + 1 + l16; i < r1; i += 16) qv2[i] = th * (dv[i] - vv[i] * inz * zeta);
+            if (cv && l16 == 0) { cinfo[5 * c + 2] = (h0 + zeta) * M_SQRT1_2; cinfo[5 * c + 3] = (h0 - zeta) * M_SQRT1_2; }
+        }
+        __syncthreads();
+        // d_B = gamma_B by equality (eqrow and ceq are the numbering's inverse) -> mu
+        for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
+        for (int c = tid; c < nq; c += NTHR) if (ckind[c] == 2) mu[ceq[c]] = cinfo[5 * c + 2];
+        __syncthreads();
+        // d~ = B_1^-1 d_B from the in-place inverse: 16 lanes per equality
+        for (int e0 = 0; e0 < neq; e0 += NTHR / 16) {
+            const int e = e0 + (tid >> 4), part = tid & 15;
+            double a = 0.0;
+            const int pc = e < neq ? pcol[e] : -1;
+            if (pc >= 0) { const double *row = sm + erow[e]; for (int i = part; i < neq; i += 16) { const int pi = pcol[i]; if (pi >= 0) a = fma(row[pi], mu[i], a); } }
+            a = group_reduce<16, false>(a);
+            if (e < neq && part == 0) dB[e] = pc >= 0 ? a : 0.0;
+        }
+        __syncthreads();
+        // t_q = a_q . x_p for the z-rows of the list (their pivot columns are as loaded); QP: t_j = p_j . x_p for the rows of P (its pivot columns are untouched) -> ptv
+        auto list_t = [&]() {
+            for (int q0 = 0; q0 < KW; q0 += NTHR / 4) {
+                const int q = q0 + (tid >> 2), part = tid & 3;
+                const bool live = q < KW && wsrc[q < KW ? q : 0] >= 0;
+                double a = 0.0;
+                if (live) { const double *row = sm + wrow[q]; for (int e = part; e < neq; e += 4) { const int pc = pcol[e]; if (pc >= 0) a = fma(row[pc], dB[e], a); } }
+                a = group_reduce<4, false>(a);
+                if (live && part == 0) tvec[q] = a;
+            }
+        };
+        list_t();
+        if constexpr (QP) {
+            for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
+                const int j = j0 + (tid >> 2), part = tid & 3;
+                double a = 0.0;
+                if (j < n) for (int e = part; e < neq; e += 4) { const int pc = pcol[e]; if (pc >= 0) a = fma(Pm[j * n + pc], dB[e], a); }
+                a = group_reduce<4, false>(a);
+                if (j < n && part == 0) ptv[j] = a;
+            }
+        }
+        __syncthreads();
+        // the list takes theta q'_i = theta (t_i - z-hat_i (z-hat . t)): Z^T H x_p = sum theta q'_i a~_i needs no a_z (whose storage was the sweep's)
+        for (int c = tid; c < nq; c += NTHR) {
+            if (ckind[c] != 2) continue;
+            const int r0 = T.qoff[c], r1 = T.qoff[c + 1], qb = cbase[c];
+            const double inz = 1.0 / cinfo[5 * c + 1], th = cinfo[5 * c + 4];
+            double zt = 0.0;
+            for (int i = r0 + 1; i < r1; i++) zt = fma(vv[i], tvec[qb + i - r0 - 1], zt);
+            zt *= inz;
+            for (int i = r0 + 1; i < r1; i++) { const double zhi = vv[i] * inz; tvec[qb + i - r0 - 1] = th * (tvec[qb + i - r0 - 1] - zhi * zt); }
+        }
+        __syncthreads();
+        // f = -g_x + sum u_i a_i by column.  A pivot column keeps f[piv] (the multipliers want it); a free column takes  h + sum (u_i - theta q'_i) a~_i  with
+        // h = -g_x [- P x_p], which lacks only -R^T h[piv] of the reduced right-hand side Z^T (f - (H [+ P]) x_p).  h waits in rx.  4 lanes per column, fixed order.
+        for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
+            const int j = j0 + (tid >> 2), part = tid & 3;
+            double a = 0.0, b = 0.0;
+            if (j < n) for (int q = part; q < KW; q += 4) {
+                const int ws = wsrc[q];
+                if (ws >= 0) { const double av = sm[wrow[q] + j]; a = fma(av, qv2[ws], a); b = fma(av, tvec[q], b); }
+            }
+            a = group_reduce<4, false>(a); b = group_reduce<4, false>(b);
+            if (j < n && part == 0) {
+                const double gx = fvec[j];
+                double hj = -gx;
+                if constexpr (QP) hj -= ptv[j];
+                rx[j] = hj;
+                fvec[j] = cmap[j] >= 0 ? hj + a - b : a - gx;
+            }
+        }
+        __syncthreads();
+        list_t();          // (tvec holds t again: step 5 adds a~ . x_free to it)
+        for (int j = tid; j < n; j += NTHR) {
+            if (cmap[j] < 0) continue;
+            double a = fvec[j];
+            for (int e = 0; e < neq; e++) { const int pc = pcol[e]; if (pc >= 0) a = fma(-sm[erow[e] + j], rx[pc], a); }
+            fvec[j] = a;
+        }
+        __syncthreads();
+        for (int j = tid; j < n; j += NTHR) rx[j] = 0.0;          // (step 5 wants zeros in the pivot entries; the free ones are written next)
+        __syncthreads();
+        // x_free = (Z^T (H [+ P]) Z)^-1 rhs out of the accumulator tiles, as the many-cotangent adjoint takes it
+        if (wave < NTILE) {
+            double rr[NTILE];
+#pragma unroll
+            for (int J = 0; J < NTILE; J++) { const int colr = 16 * J + lc; rr[J] = colr < nf ? fvec[fcol[colr < nf ? colr : 0]] : 0.0; }
+            static_for<4>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                double sacc = 0.0;
+                static_for<NTILE>([&](auto Jc) { constexpr int J = decltype(Jc)::value; sacc = fma(acc[J][r], rr[J], sacc); });
+                sacc = group_reduce<16, false>(sacc);
+                const int rowi = 16 * wave + lg + 4 * r;
+                if (lc == 0 && rowi < nf) rx[fcol[rowi]] = -sacc;
+            });
+        }
+    } else if constexpr (MANY) {
         dxk += kc * W.sxk; dyk += kc * W.syk; dAk += kc * W.sAk; dqk += kc * W.sqk; if (adjk) adjk += kc * W.sak;
         const double *const dxi = dxk + (size_t)inst * n;
         __syncthreads();          // the output pass of the cotangent before has read vv, rx, fvec and dv
@@ -1351,6 +1500,17 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
             return;
         } else {
+        if constexpr (MANY) {
+            for (int j = tid; j < n; j += NTHR) W.dx[kc * W.sxk + (size_t)inst * n + j] = rx[j];
+            for (int i = tid; i < m; i += NTHR) { W.dy[kc * W.syk + (size_t)inst * m + i] = vv[i]; if (W.ds) W.ds[kc * W.syk + (size_t)inst * m + i] = dv[i]; }
+            if (tid == 0) {
+                const int fl = misc[2];
+                if (adjk) adjk[inst] = fl;
+                if (W.iters) W.iters[kc * W.sak + inst] = 0;
+                if (fix && (fl & 4) && kc == 0) fix[1 + atomicAdd(fix, 1)] = inst;      // listed once for all tangents (ce_jvp_many walks the list once per tangent)
+            }
+            continue;
+        } else {
         for (int j = tid; j < n; j += NTHR) W.dx[(size_t)inst * n + j] = rx[j];
         for (int i = tid; i < m; i += NTHR) { W.dy[(size_t)inst * m + i] = vv[i]; if (W.ds) W.ds[(size_t)inst * m + i] = dv[i]; }
         if (tid == 0) {
@@ -1361,8 +1521,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         return;
         }
+        }
     }
-    if constexpr (MANY) {          // the a_y share of f, taken out of f' above: mu_c = mu'_c - sqrt 2 u_0 (qv2 of a t-row is not step 5's to write)
+    if constexpr (MANY && !FWD) {          // the a_y share of f, taken out of f' above: mu_c = mu'_c - sqrt 2 u_0 (qv2 of a t-row is not step 5's to write)
         for (int c = tid; c < nq; c += NTHR) if (ckind[c] == 2 && pcol[ceq[c]] >= 0) dB[ceq[c]] -= M_SQRT2 * qv2[T.qoff[c]];
         __syncthreads();
     }

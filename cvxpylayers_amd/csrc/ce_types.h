@@ -53,6 +53,18 @@ struct NsMany {
     int K;
     long sxk, syk, sAk, sqk, sak;
 };
+// k_backward_ns<..., FWD = true, ..., MANY = true> (plain cones, P or not): K tangents on one factorisation of the instance (cone_engine.hip ce_jvp_many /
+// ce_jvp_qp_many).  Tangent k of instance i: its value row at tA + k * stAk + i * stAb, its q_eval row (n + 1 contiguous entries) at tq + k * stqk + i * stqb; a batch
+// stride of 0 is one row shared by every instance.  Outputs of tangent k lie sxk (dx) / syk (dy, ds) / sak (status -- CeBwdArgs' adj -- and iters) elements further
+struct NsJvpMany {
+    const int *csc_ptr, *csr_ptr, *csr_col, *csr_src, *bpos;          // as NsJvp
+    int K;
+    const double *tA; long stAk, stAb;       // NULL: zero
+    const double *tq; long stqk, stqb;       // NULL: zero
+    double *dx, *dy, *ds;    // [K][B][n], [K][B][m], [K][B][m] (ds may be NULL)
+    long sxk, syk, sak;
+    int *iters;              // [K][B] <- 0 (NULL: not wanted)
+};
 // k_backward_ns<..., FWD = true, REF = true>: one safeguarded Newton step on the KKT residual (cone_engine.hip ce_refine).  The kernel reads the instance's b through
 // bpos and c from q, updates x, y, s IN PLACE when the step is kept, and keeps the per-instance record of the call (one launch = one step)
 struct NsRefine {
@@ -74,6 +86,7 @@ struct NsQp {
 };
 struct NsJvpQp : NsJvp { NsQp Q; };
 struct NsRefineQp : NsRefine { NsQp Q; };
+struct NsJvpQpMany : NsJvpMany { NsQp Q; long stPk, stPb; };          // Q.tP: tangent k of instance i's P row at Q.tP + k * stPk + i * stPb
 // k_backward_ns<..., FWD, REF or not, QP = false, TRI = true>: the same arguments (the triples are described by DevT); types of their own select the launcher
 struct NsJvpTri : NsJvp {};
 struct NsRefineTri : NsRefine {};
@@ -213,6 +226,8 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpTri &w);          // (a third object: exponential / power triples)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefineTri &w);
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsMany &w);               // (a fourth object, ce_tu_ns_many.hip: the adjoint for K cotangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpMany &w);            // (ce_tu_ns_jvp_many.hip, one object per kind: the forward
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQpMany &w);          //  derivative for K tangents, without and with P)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -248,6 +263,8 @@ hipError_t ce_setattr_ns(int bytes);
 hipError_t ce_setattr_ns_qp(int bytes);
 hipError_t ce_setattr_ns_tri(int bytes);
 hipError_t ce_setattr_ns_many(int bytes);
+hipError_t ce_setattr_ns_jvp_many(int bytes);
+hipError_t ce_setattr_ns_jvp_qp_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -313,6 +313,11 @@ int ce_tri_ns_variant(ce_handle h) { return h ? h->plan.tri_ns_variant : -1; }
 // the many-cotangent mode rebuilds every cotangent's vectors in the buffers of the plain adjoint: its row and footprint are ns_variant's, and like the kernel
 // behind ce_vjp it only runs in front of the LSQR re-solve
 int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
+// the many-tangent modes rebuild every tangent's vectors in the buffers of ce_jvp / ce_jvp_qp: their rows and footprints.  Plain kind: the rule of ce_jvp without the
+// triples (TRI keeps K launches: ce_backward_ns.h).  Either kind is kept in-kernel only while its K = 8 bracket lies below K single-tangent calls
+// (profiles/jvp_many/): a kind that fails that is switched off here, and ConeEngine.jvp_many runs its loop.
+int ce_jvp_many_variant(ce_handle h) { return (h && !h->plan.qp_native && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
+int ce_jvp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->plan.qp_ns_variant >= 0) ? h->plan.qp_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -1162,6 +1167,76 @@ int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
               double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     return jvp_ns(h, B, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, tP_vals, dx, dy, ds, jvp_status, lsqr_iters, 0.0, 0.0, 0.0, 0, stream);
+}
+// K tangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., FWD, ..., MANY> factors every instance once and writes all K answers; plain kind:
+// the instances it lists as rank deficient are listed ONCE, and the LSQR kernel walks that list once per tangent with the tangent's pointers (the list parity flips
+// once).  QP kind: no re-solve, the dropped-variable answer stands with status 4 for every k.
+static int jvp_many_ns(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
+                       const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                       const double *tP_vals, long stP_k, long stP_b, double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
+                       double atol, double btol, double conlim, int iter_lim, void *stream) {
+    const bool qp = P_vals != nullptr;
+    const std::string who = qp ? "ce_jvp_qp_many" : "ce_jvp_many";
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (qp) { const int rc = qp_ns_check(h, "ce_jvp_qp_many"); if (rc) return rc; }
+    if ((qp ? ce_jvp_qp_many_variant(h) : ce_jvp_many_variant(h)) < 0) {
+        g_err = who + (qp ? ": this template has no many-tangent elimination with a quadratic objective; call ce_jvp_qp once per tangent"
+                          : ": this template has no many-tangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, CE_BWD_NS=0, "
+                            "or the LSQR vectors of the re-solve exceed LDS); call ce_jvp once per tangent");
+        return CE_E_UNSUPPORTED;
+    }
+    const long nnz = T.nnz_aug, n = T.n, m = T.m;
+    if (B > 1 && sA_b != nnz) { g_err = who + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    if ((tA_vals && stA_b != 0 && stA_b < nnz) || (tq_vals && stq_b != 0 && stq_b < n + 1) || (tP_vals && stP_b != 0 && stP_b < (long)h->nnz_p)) {
+        g_err = who + ": a tangent's batch stride is 0 (one row shared by the batch) or at least the row length"; return CE_E_BADARG;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    FixLists fix{nullptr, nullptr};
+    int rc = CE_OK;
+    if (!qp) { rc = resolve_lists(h, B, st, &fix); if (rc) return rc; }
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
+    const long sxk = (long)((size_t)B * n), syk = (long)((size_t)B * m), sak = B;
+    const NsJvpMany W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), K, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b,
+                      dx, dy, ds, sxk, syk, sak, lsqr_iters};
+    const int lrc = qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
+                       : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
+    if (lrc) { g_err = "internal: no many-tangent kernel for the planned variant"; return CE_E_BADARG; }
+    if (!qp) {
+        const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
+        const int prof_keep = h->prof; h->prof = 0;
+        for (int k = 0; k < K && !rc; k++)
+            rc = jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals ? tA_vals + k * stA_k : nullptr, stA_b, tq_vals ? tq_vals + k * stq_k : nullptr, 1, stq_b,
+                                 dx + k * sxk, dy + k * syk, ds ? ds + k * syk : nullptr, jvp_status + k * sak, lsqr_iters ? lsqr_iters + k * sak : nullptr,
+                                 atol, btol, conlim, iter_lim, stream, fix.cur, 4 | 8, fix.oth);
+        h->fix_par ^= 1;
+        h->prof = prof_keep;
+        if (rc) return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+int ce_jvp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
+        g_err = "ce_jvp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    if (h->plan.qp_native) { g_err = "ce_jvp_many: this template runs a quadratic objective inside the kernels; use ce_jvp_qp_many"; return CE_E_UNSUPPORTED; }
+    return jvp_many_ns(h, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+                       atol, btol, conlim, iter_lim, stream);
+}
+int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                   const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals, long stP_k, long stP_b,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0 || stP_b < 0) {
+        g_err = "ce_jvp_qp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    return jvp_many_ns(h, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
+                       0.0, 0.0, 0.0, 0, stream);
 }
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.

@@ -39,6 +39,7 @@ class ConeEngine:
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
+        self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
@@ -484,6 +485,73 @@ class ConeEngine:
             rc = call(fn, A_c)
         if rc in (-2, -3):
             raise NotImplementedError(_lib.lib().ce_last_error().decode())
+        _lib.check(rc, name)
+        self.last_jvp_kernel = name
+        self.last_lsqr_iters = its
+        return dx, dy, ds, st
+
+    def jvp_many(self, A_bm, x, y, s, tA, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "direct",
+                 P_bm=None, tP=None, force_loop: bool = False):
+        """K tangents at one solution.  tA (K, B, nnz_aug), tq (K, B, n+1), tP (K, B, nnz_p) -- or (K, .) for a tangent every instance shares (batch stride 0: a
+        parameter-space basis vector pushed through the parameter maps); at most two of the three may be None (zero).  Returns dx (K, B, n), dy (K, B, m),
+        ds (K, B, m), status (K, B) and sets last_lsqr_iters (K, B): for every k what jvp(method=method) returns for the k-th tangent.
+        One C call (each instance factored once, last_jvp_many_path == "many") under the rule that sends jvp(method="direct") to ce_jvp / ce_jvp_qp -- ce_jvp_qp_many with
+        P_bm, ce_jvp_many on every path but "const_a" -- when the kind's *_many_variant >= 0.  Every other case (method="lsqr", the shared-A path, PSD cones or
+        triples, templates without the mode, force_loop) is K calls of jvp, stacked ("loop"): the method is total wherever jvp is, and the loop is the comparator."""
+        if method not in ("lsqr", "direct"):
+            raise ValueError(f"ConeEngine.jvp_many: method must be 'lsqr' or 'direct', got {method!r}")
+        given = [t for t in (tA, tq, tP) if t is not None]
+        if not given:
+            raise ValueError("ConeEngine.jvp_many: at least one of tA, tq, tP must be given (K is their leading dimension)")
+        K, B = int(given[0].shape[0]), int(A_bm.shape[0])
+        if any(int(t.shape[0]) != K for t in given):
+            raise ValueError("ConeEngine.jvp_many: the tangents disagree on K")
+        if tP is not None and P_bm is None:
+            raise ValueError("ConeEngine.jvp_many: tP needs P_bm")
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        if path is None:
+            path = self.last_path
+        L = _lib.lib()
+        many = not force_loop and method == "direct" and (L.ce_jvp_qp_many_variant(self._h) >= 0 if P_bm is not None else (path != "const_a" and L.ce_jvp_many_variant(self._h) >= 0))
+        self.last_jvp_many_path = "many" if many else "loop"
+        i32 = dict(dtype=torch.int32, device=dev)
+        if B == 0 or K == 0:
+            self.last_lsqr_iters = torch.empty((K, B), **i32)
+            return torch.empty((K, B, self.n), **f64), torch.empty((K, B, self.m), **f64), torch.empty((K, B, self.m), **f64), torch.empty((K, B), **i32)
+        tA, tq, tP = (None if t is None else t.detach().to(**f64).contiguous() for t in (tA, tq, tP))
+        if not many:
+            def of(t, k):          # tangent k as jvp takes it: one row per instance
+                return None if t is None else (t[k] if t.dim() == 3 else t[k].unsqueeze(0).expand(B, -1))
+            outs, its = [], []
+            for k in range(K):
+                tqk = of(tq, k)
+                outs.append(self.jvp(A_bm, x, y, s, of(tA, k), None if tqk is None else tqk.t(), path=path, lsqr=lsqr, q_eval=q_eval, conlim=conlim, method=method,
+                                     P_bm=P_bm, tP_bm=of(tP, k)))
+                its.append(self.last_lsqr_iters)
+            self.last_lsqr_iters = torch.stack(its)
+            return tuple(torch.stack([o[i] for o in outs]) for i in range(4))
+        def strides(t, row):          # (pointer, tangent stride, batch stride) of a (K, B, row) or (K, row) tangent
+            return (None, 0, 0) if t is None else (t.data_ptr(), t.stride(0), row if t.dim() == 3 else 0)
+        A_c = A_bm.detach().to(**f64)
+        A_c = A_c if (A_c.stride(1) == 1 and (B == 1 or A_c.stride(0) == self.nnz_aug)) else A_c.contiguous()
+        xc, yc, sc_ = (t.detach().to(**f64).contiguous() for t in (x, y, s))
+        dx, dy, ds = torch.empty((K, B, self.n), **f64), torch.empty((K, B, self.m), **f64), torch.empty((K, B, self.m), **f64)
+        st, its = torch.empty((K, B), **i32), torch.empty((K, B), **i32)
+        outp = (dx.data_ptr(), dy.data_ptr(), ds.data_ptr(), st.data_ptr(), its.data_ptr())
+        if P_bm is not None:
+            P_c = P_bm.detach().to(**f64).contiguous()
+            rc, name = L.ce_jvp_qp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                                        *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *strides(tP, self.nnz_p), *outp, self._stream()), "ce_jvp_qp_many"
+        else:
+            atol, btol, lim, system, _ = unpack_rule(lsqr, self.n, self.m)
+            if q_eval is None and system != "reduced":
+                q_eval = self._recent_q(A_bm)
+            if system == "reduced":
+                q_eval = None
+            qd, q_args = self._q_args(q_eval)
+            rc, name = L.ce_jvp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                                     *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream()), "ce_jvp_many"
         _lib.check(rc, name)
         self.last_jvp_kernel = name
         self.last_lsqr_iters = its

@@ -412,6 +412,42 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
     return dA, dq, dP, failed
 
 
+def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=None):
+    """K tangents through the node whose forward returned `backward_data`, with no autograd graph -- the forward twin of adjoint_many.  Tangents batch-major in the
+    engine's conventions: tA (K, B, nnz_aug), tq (K, B, n + 1), tP (K, B, nnz_p), or (K, .) for one every instance shares; at most two may be None.  Applies what
+    _ConeLayer.jvp applies -- device moves, the `failed` mask of a raise_on_error=False call (the derivative at a zero point: the caller turns those instances' rows
+    into NaN like their outputs), the saved path / lsqr rule / q_eval, the symmetrisation of tP that _CvxpyLayer.apply gives the values (sym_perm: the permutation,
+    None for a one-triangle structure), info["jvp"] with (K, B) status and iterations -- and calls ConeEngine.jvp_many.  method: "direct" / "lsqr", None for the
+    call's jvp_mode.  Returns dx (K, B, n), dy (K, B, m) on the engine's device and the `failed` mask or None."""
+    saved, batch_size, _unbatched, _in_device = backward_data
+    if saved is None:
+        raise RuntimeError("tangent_many called on a layer evaluated with needs_grad=False")
+    method = saved.jvp_mode if method is None else method
+    qp = saved.P_bm is not None
+    if qp and method != "direct":
+        raise NotImplementedError("MI355 solver: the LSQR forward-mode derivative is not available with a quadratic objective inside the kernels; "
+                                  "pass solver_args jvp_mode='direct' (the elimination with P inside), or set CE_QP_EPIGRAPH=1 to bring the problem "
+                                  "to cone form, where the default applies")
+    eng, x, y, s, failed = saved.eng, saved.x, saved.y, saved.s, saved.failed
+    with torch.cuda.device(eng.device):
+        f64 = dict(device=eng.device, dtype=torch.float64)
+        tA, tq, tP = (None if t is None else t.detach().to(**f64) for t in (tA, tq, tP if qp else None))
+        if tP is not None and sym_perm is not None:
+            tP = 0.5 * (tP + tP.index_select(tP.dim() - 1, sym_perm.to(eng.device)))
+        if failed is not None:
+            keep = ~failed[:, None]
+            x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
+        # a shared-A call whose A values merely coincide may still carry a tangent in A: the shared kernel reads the b entries only
+        path = saved.path if (saved.path != "const_a" or tA is None or eng.A_is_constant) else "per_instance"
+        if qp:
+            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, method="direct", P_bm=saved.P_bm, tP=tP)
+        else:
+            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method)
+        if isinstance(info, dict):
+            info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many") else "lsqr"}
+    return dx, dy, failed
+
+
 class _CvxpyLayer:
     """What get_torch_cvxpylayer("MI355") returns: `apply(P_eval, q_eval, A_eval, cl_ctx, solver_args, needs_grad, warm_start)
     -> (primal, dual, aux, data)` like every reference plugin (torch/cvxpylayer.py:475-483).  A linear objective goes straight to

@@ -449,7 +449,7 @@ class CvxpyLayer(torch.nn.Module):
             out = out + (self._value(P_eval, q_eval, A_eval, primal, dual, info, solver_args),)
         return out
 
-    def jacobian(self, *params: torch.Tensor, solver_args: dict | None = None, max_bytes: int = 1 << 30):
+    def jacobian(self, *params: torch.Tensor, solver_args: dict | None = None, max_bytes: int = 1 << 30, direction: str = "reverse"):
         """outs, jac = layer.jacobian(*params): `outs` is what forward returns, detached; jac[i][j] = d outs[i] / d params[j] per instance, of shape
         batch + var_i.shape + param_j.shape (both index groups in torch's row-major order), float64, on the parameters' device.  A parameter passed unbatched into a
         batched call is differentiated per instance (its expanded copy), not summed over the batch.
@@ -458,9 +458,19 @@ class CvxpyLayer(torch.nn.Module):
         through interfaces.mi355_if.adjoint_many -- ConeEngine.vjp_many: each instance is factored once per chunk, not once per output element -- and the transposed
         parameter maps on the (K B, .) views.  The cotangents go in chunks whose dA stays within max_bytes (K_chunk B nnz_aug 8 bytes, at least one cotangent); a
         cotangent's result does not depend on the chunk it travels in.  Instances a raise_on_error=False call masks return NaN rows, like their outputs.
-        Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family."""
-        from cvxpylayers_amd.interfaces.mi355_if import adjoint_many
+        Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
+
+        direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q
+        and P, the same for every instance: handed over once, batch stride 0; the constant column is left out) through interfaces.mi355_if.tangent_many --
+        ConeEngine.jvp_many --, in chunks whose dx, dy stay within max_bytes, and the recovery maps on dx / dy.  Same return, same layout.  The route for a layer
+        with few parameter entries and many output elements, and the one by which a quadratic objective inside the kernels gets a one-factorisation Jacobian.
+        It runs the direct elimination unless solver_args (the call's or the layer's) says jvp_mode="lsqr" explicitly: a Jacobian by K LSQR solves is not a
+        default anyone wants.  direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
+        because solver_args["mode"] means something else.)  Any other value: ValueError, before anything touches the device."""
+        from cvxpylayers_amd.interfaces.mi355_if import adjoint_many, tangent_many
         from cvxpylayers_amd.interfaces.solver_args import LPGD_MODES
+        if direction not in ("reverse", "forward", "auto"):
+            raise ValueError(f"CvxpyLayer.jacobian: direction must be 'reverse', 'forward' or 'auto', got {direction!r}")
         solver_args = solver_args or {}
         if self.template.gp:
             raise NotImplementedError("CvxpyLayer.jacobian: gp=True layers are not served (the log / exp maps around the cone program are outside the Jacobian assembled here)")
@@ -494,17 +504,35 @@ class CvxpyLayer(torch.nn.Module):
             eng = saved.eng
             sizes = [int(np.prod(s)) if len(s) else 1 for s in tpl.param_shapes]
             k_chunk = max(1, int(max_bytes) // max(1, B * eng.nnz_aug * 8))
+            n_out = sum(int(self._rec[src][0].mat.shape[0]) for src in self._rec)
+            forward = direction == "forward" or (direction == "auto" and tpl.n_params_total < n_out)
             sym_perm = None
             if saved.P_bm is not None and not self.ctx.solver_ctx.quad.one_triangle:          # (the plugin symmetrises P_eval in front of the kernels: its transpose here)
                 sym_perm = torch.from_numpy(self.ctx.solver_ctx.quad.sym_perm).to(eng.device)
             jac: list = [None] * len(tpl.var_recover)
+            g_fwd = {}
+            if forward:
+                # one tangent per parameter entry: column c of the forward maps, batch-shared; dx, dy (and ds inside the engine) of a chunk stay within max_bytes
+                ptot = tpl.n_params_total
+                method = "lsqr" if merged.get("jvp_mode") == "lsqr" else "direct"
+                c_chunk = max(1, int(max_bytes) // max(1, B * (eng.n + 2 * eng.m) * 8))
+                g_fwd = {src: torch.zeros((int(self._rec[src][0].mat.shape[0]), B, ptot + 1), dtype=torch.float64, device=eng.device) for src in self._rec}
+                for c0 in range(0, ptot, c_chunk):
+                    c1 = min(ptot, c0 + c_chunk)
+                    def cols(dcsr):
+                        return torch.from_numpy(np.ascontiguousarray(dcsr.mat[:, c0:c1].toarray().T)).to(eng.device)
+                    dx, dy, _failed = tangent_many(data, cols(self._P) if saved.P_bm is not None else None, cols(self._q), cols(self._A), info, method=method, sym_perm=sym_perm)
+                    for src, d in (("primal", dx), ("dual", dy)):
+                        if src in self._rec:
+                            rec = _spmm_bm(self._rec[src][0].on(eng.device)[0], d.view((c1 - c0) * B, -1))          # (K B, outputs) = d . recovery^T
+                            g_fwd[src][:, :, c0:c1] = rec.view(c1 - c0, B, -1).permute(2, 1, 0)
             for source in ("primal", "dual"):
                 if source not in self._rec:
                     continue
                 csr, layout = self._rec[source]
                 total = int(csr.mat.shape[0])
-                g_all = torch.empty((total, B, tpl.n_params_total + 1), dtype=torch.float64, device=eng.device)
-                for t0 in range(0, total, k_chunk):
+                g_all = g_fwd[source] if forward else torch.empty((total, B, tpl.n_params_total + 1), dtype=torch.float64, device=eng.device)
+                for t0 in (() if forward else range(0, total, k_chunk)):          # (the reverse direction: rows of the Jacobian, as before)
                     t1 = min(total, t0 + k_chunk)
                     rows = torch.from_numpy(csr.mat[t0:t1].toarray()).to(eng.device)          # one cotangent per output element: a row of the recovery map
                     cot = rows[:, None, :].expand(t1 - t0, B, rows.shape[1]).contiguous()

@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -509,6 +509,35 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
  * adjoint's buffers: same footprint, the launch plan is unchanged).  -1: PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108,
  * CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS. */
 int ce_vjp_many_variant(ce_handle h);
+
+/* MANY TANGENTS AT ONE SOLUTION: for every k < K what ce_jvp (ce_jvp_qp) returns for the k-th tangent, from ONE factorisation per instance -- the forward twin of
+ * ce_vjp_many, and the route by which a layer with few parameters and many outputs, or a native QP layer, gets its Jacobian by columns.  The matrix work is the
+ * adjoint's and depends on (A, x, y, s [, P]) alone; per tangent the kernel rebuilds g = dQ pi from the tangent's rows and the point (read from global memory again),
+ * gamma and the weights of f from the retained classification, d~ from the in-place B_1^-1, the reduced right-hand side, one product with the stored
+ * (Z^T (H [+ P]) Z)^-1, step 5 and the forward epilogue (csrc/ce_backward_ns.h, FWD + MANY).
+ *   A_vals_bm, q_vals, P_vals, x, y, s, atol .. iter_lim as ce_jvp / ce_jvp_qp.
+ *   tangent k of instance i:  its value row at tA_vals + k * stA_k + i * stA_b,  its q_eval row (n + 1 CONTIGUOUS entries, the last ignored) at
+ *   tq_vals + k * stq_k + i * stq_b,  its P row at tP_vals + k * stP_k + i * stP_b.  Each pointer may be NULL (zero).  A batch stride is 0 -- one row shared by
+ *   every instance: a parameter-space basis vector pushed through the parameter maps -- or at least the row length; anything between is CE_E_BADARG.
+ *   dx [K][B][n], dy [K][B][m], ds [K][B][m] (ds may be NULL), jvp_status [K][B], lsqr_iters [K][B] (may be NULL) contiguous.
+ * Rank deficiency is the matrix's: ce_jvp_many flags such an instance for all K, lists it once, and the LSQR kernel walks the list once per tangent (status 4 | 8,
+ * iterations > 0, as ce_jvp); ce_jvp_qp_many has no re-solve, the dropped-variable answer stands with status 4 for every k (as ce_jvp_qp).
+ * K == 1 is legal.  CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0, a bad batch stride.  CE_E_UNSUPPORTED with a
+ * ce_last_error that names the reason when the kind's *_many_variant is -1.  No host synchronisation, no allocation after the first call of a batch size. */
+int ce_jvp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s,
+                const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
+                double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals,
+                   const double *x, const double *y, const double *s,
+                   const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals, long stP_k, long stP_b,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream);
+/* >= 0: the template has the many-tangent mode of its kind; the value is the tile variant (ce_adjoint_ns_variant's / ce_qp_ns_variant's: the mode rebuilds every
+ * tangent's vectors in the buffers of ce_jvp / ce_jvp_qp, the launch plan is unchanged).  -1: no in-kernel mode -- PSD / exponential / power cones (the triples'
+ * forward derivative keeps K launches), n > 108, CE_BWD_NS=0, the LSQR vectors of the re-solve exceed LDS, the other kind's template; a NULL handle. */
+int ce_jvp_many_variant(ce_handle h);
+int ce_jvp_qp_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
