@@ -65,9 +65,12 @@
 // unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  TRI templates keep K launches of the single-tangent kernel:
 // NS_TRI_STIFF below lists an instance for a stiff weighted triple row, a rule of the forward derivative alone that rides on the triples' own footprint and frames --
 // `flagged` is still the matrix's there, but no many-mode is planned on that footprint.  REF never comes with MANY.
+// Without FWD, with QP (cone_engine.hip ce_vjp_qp_many): K cotangents of the adjoint with P.  The system is (H + P) r_x - B^T mu = f, B r_x = d_B; per cotangent the plain
+// many-cotangent rebuild plus the P terms of the many-tangent one (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] in g), and one more output
+// row dP = -sym(r_x x^T) through the structure.  No re-solve list: a flagged instance keeps the dropped-variable answer, status 4 for every k.
 //
 // Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes.  PSD cones keep k_backward_rt, and so does the ADJOINT
-// with triples or with a quadratic objective.
+// with triples, and the single-cotangent adjoint with a quadratic objective.
 #pragma once
 #include "ce_common.h"
 #include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
@@ -107,6 +110,7 @@ template <> struct NsFwdArg<true, true, false, true> { typedef NsRefineTri type;
 template <> struct NsFwdArg<false, false, false, false, true> { typedef NsMany type; };
 template <> struct NsFwdArg<true, false, false, false, true> { typedef NsJvpMany type; };
 template <> struct NsFwdArg<true, false, true, false, true> { typedef NsJvpQpMany type; };
+template <> struct NsFwdArg<false, false, true, false, true> { typedef NsVjpQpMany type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well)
@@ -116,10 +120,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
               int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI, MANY>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
-    static_assert(FWD || !QP, "the adjoint with a quadratic objective lives in k_backward_rt");
+    static_assert(FWD || !QP || MANY, "the single-cotangent adjoint with a quadratic objective lives in k_backward_rt");
     static_assert((FWD && !QP) || !TRI, "exponential / power triples: the forward modes with a linear objective (their adjoint lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !QP && !TRI) || (FWD && !REF && !TRI),
-                  "many right-hand sides on one factorisation: the adjoint with plain cones and a linear objective (K cotangents), or the forward derivative with plain "
+    static_assert(!MANY || (!FWD && !REF && !TRI) || (FWD && !REF && !TRI),
+                  "many right-hand sides on one factorisation: the adjoint with plain cones, P or not (K cotangents), or the forward derivative with plain "
                   "cones, P or not (K tangents); templates with triples keep K launches");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
@@ -549,7 +553,8 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int kc = 0; kc < W.K; kc++) {
                 for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[kc * W.sAk + (size_t)inst * T.nnz_aug + k] = 0.0;
                 for (int j = tid; j <= n; j += NTHR) dqo[kc * W.sqk + j * sdqk + inst * sdqb] = 0.0;
-                if (tid == 0 && adj_status) adj_status[kc * W.sak + inst] = 2;
+                if constexpr (QP) { for (int k = tid; k < W.Q.nnz_p; k += NTHR) W.dP[kc * W.sPk + (size_t)inst * W.Q.nnz_p + k] = 0.0; }
+                if (tid == 0 && adj_status) adj_status[kc * W.sak + inst] = QP ? 4 : 2;
             }
         } else {
             for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[(size_t)inst * T.nnz_aug + k] = 0.0;
@@ -1289,6 +1294,15 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
         };
         list_t();
+        if constexpr (QP) {          // t_j = p_j . x_p for the rows of P (its pivot columns are untouched) -> ptv, as the many-tangent mode rebuilds it
+            for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
+                const int j = j0 + (tid >> 2), part = tid & 3;
+                double a = 0.0;
+                if (j < n) for (int e = part; e < neq; e += 4) { const int pc = pcol[e]; if (pc >= 0) a = fma(Pm[j * n + pc], dB[e], a); }
+                a = group_reduce<4, false>(a);
+                if (j < n && part == 0) ptv[j] = a;
+            }
+        }
         __syncthreads();
         // per boundary cone, with a_0 = sqrt 2 a_y - a_z and a_z = sum z-hat_i a_i (neither row is stored any more):  A_c^T u = sqrt 2 u_0 a_y + sum u'_i a_i,
         // u'_i = u_i - u_0 z-hat_i.  The a_y share is a row of B: it moves the multiplier of the cone's equality by sqrt 2 u_0 (behind step 5) and drops out of
@@ -1305,6 +1319,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         __syncthreads();
         // f' = dx + sum u'_i a_i by column: a pivot column keeps f'[piv] (the multipliers want it), a free column takes  dx + sum (u'_i - theta q'_i) a~_i, which
         // lacks only -R^T dx[piv] of the reduced right-hand side Z^T (f' - H x_p).  4 lanes per column, fixed summation order.
+        // QP: a free column takes -(P x_p)_j = -t_j as well, and -R^T below meets h[piv] = (dx - P x_p)[piv]: Z^T (f' - (H + P) x_p).
         for (int j0 = 0; j0 < n; j0 += NTHR / 4) {
             const int j = j0 + (tid >> 2), part = tid & 3;
             double a = 0.0, b = 0.0;
@@ -1313,14 +1328,21 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 if (ws >= 0) { const double av = sm[wrow[q] + j]; a = fma(av, qv2[ws], a); b = fma(av, tvec[q], b); }
             }
             a = group_reduce<4, false>(a); b = group_reduce<4, false>(b);
-            if (j < n && part == 0) fvec[j] = dxi[j] + a - (cmap[j] >= 0 ? b : 0.0);
+            if (j < n && part == 0) {
+                if constexpr (QP) fvec[j] = cmap[j] >= 0 ? (dxi[j] - ptv[j]) + a - b : dxi[j] + a;
+                else fvec[j] = dxi[j] + a - (cmap[j] >= 0 ? b : 0.0);
+            }
         }
         __syncthreads();
         list_t();          // (tvec holds t again: step 5 adds a~ . x_free to it)
         for (int j = tid; j < n; j += NTHR) {
             if (cmap[j] < 0) continue;
             double a = fvec[j];
-            for (int e = 0; e < neq; e++) { const int pc = pcol[e]; if (pc >= 0) a = fma(-sm[erow[e] + j], dxi[pc], a); }
+            for (int e = 0; e < neq; e++) {
+                const int pc = pcol[e];
+                if constexpr (QP) { if (pc >= 0) a = fma(-sm[erow[e] + j], dxi[pc] - ptv[pc], a); }
+                else if (pc >= 0) a = fma(-sm[erow[e] + j], dxi[pc], a);
+            }
             fvec[j] = a;
         }
         __syncthreads();
@@ -1576,6 +1598,16 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
     }
     for (int j = tid; j <= n; j += NTHR) dqk[j * sdqk + inst * sdqb] = (j < n) ? -rx[j] : 0.0;
+    if constexpr (QP && MANY && !FWD) {
+        // dP = -sym(r_x x^T) through the structure, consecutive lanes on consecutive entries (x and r_x from LDS); a one-triangle entry stands for both matrix
+        // entries and takes both shares, as k_backward_rt writes it
+        double *const dProw = W.dP + kc * W.sPk + (size_t)inst * W.Q.nnz_p;
+        for (int k = tid; k < W.Q.nnz_p; k += NTHR) {
+            const int i = W.prow[k], j = W.pcol[k];
+            const double v = -0.5 * (rx[i] * xs[j] + rx[j] * xs[i]);
+            dProw[k] = (W.p_tri && i != j) ? 2.0 * v : v;
+        }
+    }
     if (tid == 0) {
         const int fl = misc[2];
         if (adjk) adjk[inst] = fl;

@@ -87,6 +87,10 @@ struct NsQp {
 struct NsJvpQp : NsJvp { NsQp Q; };
 struct NsRefineQp : NsRefine { NsQp Q; };
 struct NsJvpQpMany : NsJvpMany { NsQp Q; long stPk, stPb; };          // Q.tP: tangent k of instance i's P row at Q.tP + k * stPk + i * stPb
+// k_backward_ns<..., FWD = false, ..., QP = true, ..., MANY = true>: K cotangents of the adjoint with P on one factorisation (cone_engine.hip ce_vjp_qp_many).  NsMany's
+// strides as ce_vjp_many; entry k of the structure lies at (prow[k], pcol[k]) (p_tri: one triangle is stored and an off-diagonal entry stands for both);
+// dP [K][B][nnz_p], cotangent k sPk elements further.  Q.tP is unused
+struct NsVjpQpMany : NsMany { NsQp Q; const int *prow, *pcol; int p_tri; double *dP; long sPk; };
 // k_backward_ns<..., FWD, REF or not, QP = false, TRI = true>: the same arguments (the triples are described by DevT); types of their own select the launcher
 struct NsJvpTri : NsJvp {};
 struct NsRefineTri : NsRefine {};
@@ -228,6 +232,7 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsMany &w);               // (a fourth object, ce_tu_ns_many.hip: the adjoint for K cotangents)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpMany &w);            // (ce_tu_ns_jvp_many.hip, one object per kind: the forward
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQpMany &w);          //  derivative for K tangents, without and with P)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpQpMany &w);          // (ce_tu_ns_vjp_qp_many.hip: the adjoint with P for K cotangents)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -265,6 +270,7 @@ hipError_t ce_setattr_ns_tri(int bytes);
 hipError_t ce_setattr_ns_many(int bytes);
 hipError_t ce_setattr_ns_jvp_many(int bytes);
 hipError_t ce_setattr_ns_jvp_qp_many(int bytes);
+hipError_t ce_setattr_ns_vjp_qp_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -318,6 +318,7 @@ int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && r
 // (profiles/jvp_many/): a kind that fails that is switched off here, and ConeEngine.jvp_many runs its loop.
 int ce_jvp_many_variant(ce_handle h) { return (h && !h->plan.qp_native && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
 int ce_jvp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->plan.qp_ns_variant >= 0) ? h->plan.qp_ns_variant : -1; }
+int ce_vjp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->plan.qp_ns_variant >= 0) ? h->plan.qp_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -1238,6 +1239,41 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
     return jvp_many_ns(h, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
                        0.0, 0.0, 0.0, 0, stream);
 }
+// K cotangents at one solution of a template with a quadratic objective inside the kernels (include/cone_engine.h).  One launch of k_backward_ns<..., QP, ..., MANY>
+// without FWD factors every instance once and writes all K answers, dP among them.  No re-solve list: no LSQR has a P term, the dropped-variable answer of a
+// rank-deficient instance stands with status 4 for every k (as ce_jvp_qp_many and ce_vjp_qp).
+int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                   const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dA_vals || !dq_vals || !dP_vals) {
+        g_err = "ce_vjp_qp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
+    }
+    { const int rc = qp_ns_check(h, "ce_vjp_qp_many"); if (rc) return rc; }
+    const CePlan &P = h->plan;
+    const DevT &T = h->T;
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_vjp_qp_many: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = T.n, m = T.m, nnz = T.nnz_aug, nnzp = (size_t)h->nnz_p;
+    long syk = (long)((size_t)B * m);
+    if (!dy) {
+        HIPCHK(h->d_dy0.reserve((size_t)B * m));
+        HIPCHK(hipMemsetAsync(h->d_dy0.get(), 0, sizeof(double) * (size_t)B * m, st));
+        dy = h->d_dy0.get(); syk = 0;
+    }
+    NsVjpQpMany W{};
+    W.K = K; W.sxk = (long)((size_t)B * n); W.syk = syk; W.sAk = (long)((size_t)B * nnz); W.sqk = (long)((size_t)B * (n + 1)); W.sak = (long)B;
+    W.Q = NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p};
+    W.prow = h->d_prow.get(); W.pcol = h->d_pcol.get(); W.p_tri = h->p_tri; W.dP = dP_vals; W.sPk = (long)((size_t)B * nnzp);
+    ProfScope ps(h, 1, st);
+    CeBwdArgs ba{};
+    ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
+    ba.adj = adj_status; ba.fix = nullptr;
+    h->last_fast = -1;
+    if (ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no many-cotangent kernel with a quadratic objective for the planned variant"; return CE_E_BADARG; }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
 static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,

@@ -39,6 +39,7 @@ class ConeEngine:
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
+        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
@@ -356,24 +357,42 @@ class ConeEngine:
         _lib.check(rc, "ce_vjp")
         return (dA if batch_minor_out else dA.t()), dq, adj
 
-    def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False):
+    def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False,
+                 qp_many: bool = False):
         """K cotangents at one solution: dx (K, B, n), dy (K, B, m) or None (zero).  Returns dA (K, B, nnz_aug), dq (K, B, n+1), adj (K, B) -- and dP (K, B, nnz_p) when
         P_bm is given -- all batch-major.  For every k the result is what vjp returns for (dx[k], dy[k]).
         One ce_vjp_many call (each instance factored once, last_vjp_many_path == "many") under the rule that sends vjp to the search-free elimination: path
         "per_instance", q_eval given, no P, and a template with the mode (ce_vjp_many_variant >= 0).  Every other case -- the dense / LSQR / shared-A paths, a quadratic
-        objective inside the kernels, templates without the mode, force_loop -- is K calls of vjp, stacked ("loop"): the method is total, and the loop is the comparator."""
+        objective inside the kernels, templates without the mode, force_loop -- is K calls of vjp, stacked ("loop"): the method is total, and the loop is the comparator.
+        qp_many (opt-in, default False): with P_bm, path "per_instance" and ce_vjp_qp_many_variant >= 0, one ce_vjp_qp_many call instead of the K ce_vjp_qp calls
+        (last_vjp_many_path == "many", last_vjp_kernel == "ce_vjp_qp_many"): the search-free elimination with P factors each instance once and returns dP as well.
+        The two routes agree on regular instances; a rank-deficient one keeps the search-free route's dropped-variable answer with status 4 (no re-solve has a P
+        term), where the pivoting kernel of ce_vjp_qp returns its own basic solution -- hence opt-in.  Without P_bm, or on any other path, the flag changes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
         if path is None:
             path = self.last_path
         many = (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
-        self.last_vjp_many_path = "many" if many else "loop"
+        many_qp = (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
+        self.last_vjp_many_path = "many" if (many or many_qp) else "loop"
+        self.last_vjp_kernel = "ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else None)
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
             return out + ((torch.empty((K, B, self.nnz_p), **f64),) if P_bm is not None else ())
         dx = dx.to(**f64).contiguous()
         dy = None if dy is None else dy.to(**f64).contiguous()
+        if many_qp:
+            A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
+            xc, yc, sc_, P_c = (t.detach().to(**f64).contiguous() for t in (x, y, s, P_bm))
+            dA = torch.empty((K, B, self.nnz_aug), **f64)
+            dq = torch.empty((K, B, self.n + 1), **f64)
+            dP = torch.empty((K, B, self.nnz_p), **f64)
+            adj = torch.empty((K, B), dtype=torch.int32, device=dev)
+            rc = _lib.lib().ce_vjp_qp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                           None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), dP.data_ptr(), adj.data_ptr(), self._stream())
+            _lib.check(rc, "ce_vjp_qp_many")
+            return dA, dq, adj, dP
         if not many:
             zero_dy = torch.zeros((B, self.m), **f64) if dy is None else None
             outs = [self.vjp(A_bm, x, y, s, dx[k], zero_dy if dy is None else dy[k], P_bm=P_bm, path=path, lsqr=lsqr, q_eval=q_eval) for k in range(K)]

@@ -458,6 +458,10 @@ class CvxpyLayer(torch.nn.Module):
         through interfaces.mi355_if.adjoint_many -- ConeEngine.vjp_many: each instance is factored once per chunk, not once per output element -- and the transposed
         parameter maps on the (K B, .) views.  The cotangents go in chunks whose dA stays within max_bytes (K_chunk B nnz_aug 8 bytes, at least one cotangent); a
         cotangent's result does not depend on the chunk it travels in.  Instances a raise_on_error=False call masks return NaN rows, like their outputs.
+        A quadratic objective inside the kernels runs the loop of K ce_vjp_qp calls here by default; solver_args {"qp_adjoint": "search_free"} makes one
+        ce_vjp_qp_many call per chunk instead (the search-free elimination with P factors each instance once and returns dP too; a chunk's dP then counts against
+        max_bytes beside its dA; info["adjoint"]["path"] == "ce_vjp_qp_many").  Opt-in: a rank-deficient instance keeps that route's dropped-variable answer with
+        status 4.  The single-cotangent backward of .backward() ignores the key.
         Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
 
         direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q
@@ -504,6 +508,8 @@ class CvxpyLayer(torch.nn.Module):
             eng = saved.eng
             sizes = [int(np.prod(s)) if len(s) else 1 for s in tpl.param_shapes]
             k_chunk = max(1, int(max_bytes) // max(1, B * eng.nnz_aug * 8))
+            if saved.P_bm is not None and saved.qp_adjoint == "search_free":          # (one ce_vjp_qp_many call per chunk: its dP (K_chunk, B, nnz_p) counts beside its dA)
+                k_chunk = max(1, int(max_bytes) // max(1, B * (eng.nnz_aug + eng.nnz_p) * 8))
             n_out = sum(int(self._rec[src][0].mat.shape[0]) for src in self._rec)
             forward = direction == "forward" or (direction == "auto" and tpl.n_params_total < n_out)
             sym_perm = None

@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -538,6 +538,25 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
  * forward derivative keeps K launches), n > 108, CE_BWD_NS=0, the LSQR vectors of the re-solve exceed LDS, the other kind's template; a NULL handle. */
 int ce_jvp_many_variant(ce_handle h);
 int ce_jvp_qp_many_variant(ce_handle h);
+
+/* MANY COTANGENTS AT ONE SOLUTION, QUADRATIC OBJECTIVE INSIDE THE KERNELS: for every k < K what ce_vjp_qp returns for (dx[k], dy[k]) on a QP-native template, dP
+ * included, from ONE factorisation per instance by the search-free elimination -- the reverse twin of ce_jvp_qp_many.  The system is (H + P) r_x - B^T mu = f,
+ * B r_x = d_B; steps 1-4 with P (its rows through the null-space transform, Z^T P Z on the matrix cores) depend on (A, P, x, y, s) alone, and per cotangent the kernel
+ * rebuilds what ce_vjp_many rebuilds plus the P terms (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] for the multipliers), then writes
+ * the dA row, dq and dP = -sym(r_x x^T) through the structure of P, a one-triangle entry doubled (csrc/ce_backward_ns.h, QP + MANY without FWD).
+ *   A_vals_bm  batch-major rows, sA_b = nnz_aug apart;  P_vals [B][nnz_p];  dx [K][B][n], dy [K][B][m] contiguous (dy NULL: zero);
+ *   dA_vals [K][B][nnz_aug], dq_vals [K][B][n + 1] as ce_vjp_many;  dP_vals [K][B][nnz_p];  adj_status [K][B] (or NULL).
+ * Rank deficiency is the matrix's: a vanishing pivot drops the variable, the instance gets status 4 for every k and keeps the finite dropped-variable answer.  There is
+ * no LSQR re-solve (no LSQR has a P term): bit 8 is never set.  ce_vjp_qp's pivoting kernel treats such an instance differently (its own basic solution).
+ * K == 1 is legal.  CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0, non-contiguous A rows.  CE_E_UNSUPPORTED with a
+ * ce_last_error that names the reason when ce_vjp_qp_many_variant(h) < 0.  No host synchronisation, no allocation after the first call of a batch size.
+ * ce_vjp_many keeps refusing QP-native templates. */
+int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals,
+                   const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                   double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream);
+/* >= 0: the template runs a quadratic objective inside the kernels and has the search-free elimination with P; the value is ce_qp_ns_variant's row (same
+ * footprint, the launch plan is unchanged).  -1 otherwise, and for a NULL handle. */
+int ce_vjp_qp_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
