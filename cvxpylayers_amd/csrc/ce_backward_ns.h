@@ -62,15 +62,21 @@
 // and the point, not A, which is transformed by now; a tangent's row lies at k * stride_k + inst * stride_b, stride_b == 0 being one row for the whole batch), gamma and
 // the weights of f from the retained classification, d~ from the in-place inverse, t_q for the list rows (QP: Z^T P x_p from the transformed rows of P, whose pivot
 // columns are untouched), f with the treatment of the two rows that are gone (a_z, and the t-row a_y overwrote), x_free from the tiles, step 5 and the forward EPILOGUE
-// unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  TRI templates keep K launches of the single-tangent kernel:
-// NS_TRI_STIFF below lists an instance for a stiff weighted triple row, a rule of the forward derivative alone that rides on the triples' own footprint and frames --
-// `flagged` is still the matrix's there, but no many-mode is planned on that footprint.  REF never comes with MANY.
+// unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  In the FORWARD direction TRI templates keep K launches of
+// the single-tangent kernel.  REF never comes with MANY.
+// Without FWD, with TRI (cone_engine.hip ce_vjp_tri_many): K cotangents of the adjoint with exponential / power triples, the one adjoint with triples this kernel has.
+// Once per instance the TRI code above runs as it stands (exp_dual_eig / pow_dual_eig once per triple, A_c <- W^T A_c, the weighted rows numbered behind the
+// boundary cones'), W, lambda, rkind and eqrow stay in LDS, and steps 1-4 run on a zero right-hand side on the triples' footprint (tri_ns_variant, tri_ns_lds).  Per
+// cotangent the plain rebuild plus, per triple, h = W^T dy_c: a lambda = 1 row gives its entry of d_B, a lambda = 0 row d = 0, a weighted row d = lambda h and the
+// share u = theta h of f = dx + A^T u on the rotated row (the transpose of the forward's theta gamma a~; k_backward_rt's a~ d / (1 - lambda)); behind step 5
+// r~_y = mu (lambda = 1), 0 (lambda = 0), (d - lambda a~ . r_x) / (1 - lambda) (weighted), rotated back r_y,c = W r~_y,c in front of the output pass.  NS_TRI_STIFF
+// below flags the instance for every k like a vanishing pivot: the threshold is the forward derivative's measured law, carried over, not measured for the adjoint.
 // Without FWD, with QP (cone_engine.hip ce_vjp_qp_many): K cotangents of the adjoint with P.  The system is (H + P) r_x - B^T mu = f, B r_x = d_B; per cotangent the plain
 // many-cotangent rebuild plus the P terms of the many-tangent one (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] in g), and one more output
 // row dP = -sym(r_x x^T) through the structure.  No re-solve list: a flagged instance keeps the dropped-variable answer, status 4 for every k.
 //
-// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes.  PSD cones keep k_backward_rt, and so does the ADJOINT
-// with triples, and the single-cotangent adjoint with a quadratic objective.
+// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes and in the many-cotangent adjoint.  PSD cones keep
+// k_backward_rt, and so do the SINGLE-cotangent adjoint with triples and the single-cotangent adjoint with a quadratic objective.
 #pragma once
 #include "ce_common.h"
 #include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
@@ -97,7 +103,8 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
 }
 
 // TRI: the forward derivative hands an instance with a weighted triple row of 1 - lambda below this to the re-solve (the elimination's error at the threshold, by the
-// measured law: 0.03 eps / NS_TRI_STIFF^2 = 3e-8)
+// measured law: 0.03 eps / NS_TRI_STIFF^2 = 3e-8).  The many-cotangent adjoint with triples carries the rule over as it stands (flagged for every k): the law was
+// measured on the forward derivative, not on the adjoint.
 constexpr double NS_TRI_STIFF = 1e-5;
 
 template <bool FWD, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false> struct NsFwdArg { typedef NsNoJvp type; };
@@ -111,6 +118,7 @@ template <> struct NsFwdArg<false, false, false, false, true> { typedef NsMany t
 template <> struct NsFwdArg<true, false, false, false, true> { typedef NsJvpMany type; };
 template <> struct NsFwdArg<true, false, true, false, true> { typedef NsJvpQpMany type; };
 template <> struct NsFwdArg<false, false, true, false, true> { typedef NsVjpQpMany type; };
+template <> struct NsFwdArg<false, false, false, true, true> { typedef NsVjpTriMany type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well)
@@ -121,10 +129,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
               int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI, MANY>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP || MANY, "the single-cotangent adjoint with a quadratic objective lives in k_backward_rt");
-    static_assert((FWD && !QP) || !TRI, "exponential / power triples: the forward modes with a linear objective (their adjoint lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !REF && !TRI) || (FWD && !REF && !TRI),
-                  "many right-hand sides on one factorisation: the adjoint with plain cones, P or not (K cotangents), or the forward derivative with plain "
-                  "cones, P or not (K tangents); templates with triples keep K launches");
+    static_assert((FWD && !QP) || (!FWD && !REF && !QP && MANY) || !TRI,
+                  "exponential / power triples: the forward modes with a linear objective, and the many-cotangent adjoint with one (their single-cotangent adjoint "
+                  "lives in k_backward_rt)");
+    static_assert(!MANY || (!FWD && !REF && !(TRI && QP)) || (FWD && !REF && !TRI),
+                  "many right-hand sides on one factorisation: the adjoint with plain cones, P or not, or with triples and a linear objective (K cotangents), or "
+                  "the forward derivative with plain cones, P or not (K tangents); the forward derivative with triples keeps K launches");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -1267,6 +1277,22 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 if (l16 == 0) { qv2[r0] = fma(il, d0, k0c); dv[r0] = d0; cinfo[5 * c + 2] = eyd; cinfo[5 * c + 3] = esd; }
             } else if (kind == 1 && l16 == 0) dv[r0] = 0.0;
         }
+        if constexpr (TRI) {
+            // triples, one thread per triple, from the retained W and lambda: h = W^T dy_c, d = lambda h on the rotated rows (a lambda = 1 row: its entry of d_B, taken
+            // by eqrow below; a lambda = 0 row: 0), and for a weighted row its weight u = theta h in f = dx + A^T u BY ROW beside the boundary cones' (k_backward_rt:
+            // a~ d / (1 - lambda))
+            for (int c = tid; c < ntri; c += NTHR) {
+                const int r0 = T.eoff + 3 * c;
+                const double *Wl = Wt + 9 * c;
+                const double h0 = dv[r0], h1 = dv[r0 + 1], h2 = dv[r0 + 2];
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    const double t = Wl[a] * h0 + Wl[3 + a] * h1 + Wl[6 + a] * h2, lam = lamt[3 * c + a];
+                    dv[r0 + a] = lam * t;
+                    qv2[r0 + a] = rkind[r0 + a] == RK_MIX ? lam / (1 - lam) * t : 0.0;
+                }
+            }
+        }
         __syncthreads();
         // d_B by equality (the numbering's source array was the elimination's to overwrite: eqrow and ceq are its inverse) -> mu
         for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
@@ -1315,6 +1341,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int i = r0 + 1; i < r1; i++) zt = fma(vv[i], tvec[qb + i - r0 - 1], zt);
             zt *= inz;
             for (int i = r0 + 1; i < r1; i++) { const double zhi = vv[i] * inz; qv2[i] -= u0 * zhi; tvec[qb + i - r0 - 1] = th * (tvec[qb + i - r0 - 1] - zhi * zt); }
+        }
+        if constexpr (TRI) {          // a triple's weighted row is one list row of its own: theta t (eqrow keeps its list entry)
+            for (int i = T.eoff + tid; i < m; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
         }
         __syncthreads();
         // f' = dx + sum u'_i a_i by column: a pivot column keeps f'[piv] (the multipliers want it), a free column takes  dx + sum (u'_i - theta q'_i) a~_i, which
@@ -1567,6 +1596,23 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             const double k0 = (cy + cs) * M_SQRT1_2, kz = (cy - cs) * M_SQRT1_2;
             for (int i = r0 + 1; i < r1; i++) { const double zh = vv[i] * inz; vv[i] = il * (dv[i] - lam * qv2[i]) + kz * zh; }
             vv[r0] = il * (dv[r0] - lam * q0) + k0;
+        }
+    }
+    if constexpr (TRI) {
+        // triples (as k_backward_rt): r~_y on the three rotated rows -- the multiplier of an equality row, d = 0 of a dropped row, (d - lambda a~ . r_x) / (1 - lambda) of a
+        // weighted row with a~ . r_x from the list (tvec) -- and back to the original basis, r_y,c = W r~_y,c; one thread per triple
+        for (int c = tid; c < ntri; c += NTHR) {
+            const int r0 = T.eoff + 3 * c;
+            const double *Wl = Wt + 9 * c;
+            double rt[3];
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                const int i = r0 + a, rk = rkind[i], e = eqrow[i];
+                const double lam = lamt[3 * c + a];
+                rt[a] = rk == RK_EQ ? dB[e] : (rk == RK_MIX ? (dv[i] - lam * tvec[e]) / (1 - lam) : dv[i]);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; a++) vv[r0 + a] = Wl[3 * a] * rt[0] + Wl[3 * a + 1] * rt[1] + Wl[3 * a + 2] * rt[2];
         }
     }
     __syncthreads();

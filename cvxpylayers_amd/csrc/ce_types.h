@@ -94,6 +94,9 @@ struct NsVjpQpMany : NsMany { NsQp Q; const int *prow, *pcol; int p_tri; double 
 // k_backward_ns<..., FWD, REF or not, QP = false, TRI = true>: the same arguments (the triples are described by DevT); types of their own select the launcher
 struct NsJvpTri : NsJvp {};
 struct NsRefineTri : NsRefine {};
+// k_backward_ns<..., FWD = false, ..., TRI = true, MANY = true>: K cotangents of the adjoint with triples on one factorisation (cone_engine.hip ce_vjp_tri_many).
+// NsMany's fields and strides; a type of its own selects the launcher
+struct NsVjpTriMany : NsMany {};
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -233,6 +236,7 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpMany &w);            // (ce_tu_ns_jvp_many.hip, one object per kind: the forward
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQpMany &w);          //  derivative for K tangents, without and with P)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpQpMany &w);          // (ce_tu_ns_vjp_qp_many.hip: the adjoint with P for K cotangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpTriMany &w);         // (ce_tu_ns_vjp_tri_many.hip: the adjoint with triples for K cotangents)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -271,6 +275,7 @@ hipError_t ce_setattr_ns_many(int bytes);
 hipError_t ce_setattr_ns_jvp_many(int bytes);
 hipError_t ce_setattr_ns_jvp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_qp_many(int bytes);
+hipError_t ce_setattr_ns_vjp_tri_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

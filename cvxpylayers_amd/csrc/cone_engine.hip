@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -319,6 +319,9 @@ int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && r
 int ce_jvp_many_variant(ce_handle h) { return (h && !h->plan.qp_native && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
 int ce_jvp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->plan.qp_ns_variant >= 0) ? h->plan.qp_ns_variant : -1; }
 int ce_vjp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->plan.qp_ns_variant >= 0) ? h->plan.qp_ns_variant : -1; }
+// the many-cotangent mode with exponential / power triples runs on the footprint of the triples' forward modes: tri_ns_variant's row (the tri planner already asks
+// that the LSQR vectors of the re-solve fit LDS)
+int ce_vjp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >= 0) ? h->plan.tri_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -592,18 +595,13 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 // K cotangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., MANY> factors every instance once and writes all K answers; the instances
 // it lists as rank deficient are listed ONCE, and the LSQR kernel walks that list once per cotangent with the cotangent's pointers.  The list parity flips once.
 // Without an armed re-solve (q_vals == NULL, ce_set_adjoint_resolve(h, 0)) ce_vjp itself does not run the elimination: K calls of it then, the same rule.
-int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
-                const double *x, const double *y, const double *s, const double *dx, const double *dy,
-                double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
-    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+// (tri: ce_vjp_tri_many -- the same body on the triples' variant and footprint; `who` names the entry point in the messages)
+static int vjp_many_run(ce_handle h, bool tri, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                        const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                        double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
     const CePlan &P = h->plan;
     const DevT &T = h->T;
-    if (ce_vjp_many_variant(h) < 0) {
-        g_err = "ce_vjp_many: this template has no many-cotangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, "
-                "CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp once per cotangent";
-        return CE_E_UNSUPPORTED;
-    }
-    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_vjp_many: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = std::string(who) + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = T.n, m = T.m, nnz = T.nnz_aug;
@@ -630,7 +628,9 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
     ba.adj = adj_status; ba.fix = fix.cur;
     h->last_fast = -1;
-    if (ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) { g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG; }
+    if (tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsVjpTriMany{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) {
+        g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG;
+    }
     const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
     const int prof_keep = h->prof; h->prof = 0;
     for (int k = 0; k < K && !rc; k++)
@@ -641,6 +641,30 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     return CE_OK;
+}
+int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    if (ce_vjp_many_variant(h) < 0) {
+        g_err = "ce_vjp_many: this template has no many-cotangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, "
+                "CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp once per cotangent";
+        return CE_E_UNSUPPORTED;
+    }
+    return vjp_many_run(h, false, "ce_vjp_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+}
+// K cotangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_vjp_many's body with k_backward_ns<..., TRI, MANY> on the
+// triples' variant and footprint.  Without an armed re-solve K calls of ce_vjp, whose pivoting kernel serves such templates.
+int ce_vjp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                    double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_tri_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    if (ce_vjp_tri_many_variant(h) < 0) {
+        g_err = "ce_vjp_tri_many: this template has no search-free elimination with triples (no exponential / power cone, PSD cones, a quadratic objective inside the "
+                "kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp_many or ce_vjp";
+        return CE_E_UNSUPPORTED;
+    }
+    return vjp_many_run(h, true, "ce_vjp_tri_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
 }
 
 // summary of an int32 vector v[B] (status of a forward call, or adj_status of a backward call): out[0] = min v, out[1] = #{v == 2} ("solved,

@@ -39,7 +39,7 @@ class ConeEngine:
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
-        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" when the last vjp_many made that one call, None when it looped over vjp
+        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
@@ -358,7 +358,7 @@ class ConeEngine:
         return (dA if batch_minor_out else dA.t()), dq, adj
 
     def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False,
-                 qp_many: bool = False):
+                 qp_many: bool = False, tri_many: bool = False):
         """K cotangents at one solution: dx (K, B, n), dy (K, B, m) or None (zero).  Returns dA (K, B, nnz_aug), dq (K, B, n+1), adj (K, B) -- and dP (K, B, nnz_p) when
         P_bm is given -- all batch-major.  For every k the result is what vjp returns for (dx[k], dy[k]).
         One ce_vjp_many call (each instance factored once, last_vjp_many_path == "many") under the rule that sends vjp to the search-free elimination: path
@@ -367,7 +367,11 @@ class ConeEngine:
         qp_many (opt-in, default False): with P_bm, path "per_instance" and ce_vjp_qp_many_variant >= 0, one ce_vjp_qp_many call instead of the K ce_vjp_qp calls
         (last_vjp_many_path == "many", last_vjp_kernel == "ce_vjp_qp_many"): the search-free elimination with P factors each instance once and returns dP as well.
         The two routes agree on regular instances; a rank-deficient one keeps the search-free route's dropped-variable answer with status 4 (no re-solve has a P
-        term), where the pivoting kernel of ce_vjp_qp returns its own basic solution -- hence opt-in.  Without P_bm, or on any other path, the flag changes nothing."""
+        term), where the pivoting kernel of ce_vjp_qp returns its own basic solution -- hence opt-in.  Without P_bm, or on any other path, the flag changes nothing.
+        tri_many (opt-in, default False): on a template with exponential / power triples (ce_vjp_tri_many_variant >= 0), path "per_instance", q_eval given, no P, one
+        ce_vjp_tri_many call instead of the K ce_vjp calls of the pivoting kernel (last_vjp_many_path == "many", last_vjp_kernel == "ce_vjp_tri_many"): the
+        search-free elimination diagonalises and rotates each triple once per instance.  The two kernels agree on regular instances but need not flag the same ones
+        (a pivot search there, the stiff-row rule here; a flagged instance gets LSQR's minimum-norm answer) -- hence opt-in.  In every other case the flag changes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
@@ -375,8 +379,10 @@ class ConeEngine:
             path = self.last_path
         many = (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
         many_qp = (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
-        self.last_vjp_many_path = "many" if (many or many_qp) else "loop"
-        self.last_vjp_kernel = "ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else None)
+        many_tri = (not force_loop and tri_many and not many and path == "per_instance" and q_eval is not None and P_bm is None
+                    and _lib.lib().ce_vjp_tri_many_variant(self._h) >= 0)
+        self.last_vjp_many_path = "many" if (many or many_qp or many_tri) else "loop"
+        self.last_vjp_kernel = "ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else ("ce_vjp_tri_many" if many_tri else None))
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
             return out + ((torch.empty((K, B, self.nnz_p), **f64),) if P_bm is not None else ())
@@ -393,7 +399,7 @@ class ConeEngine:
                                            None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), dP.data_ptr(), adj.data_ptr(), self._stream())
             _lib.check(rc, "ce_vjp_qp_many")
             return dA, dq, adj, dP
-        if not many:
+        if not (many or many_tri):
             zero_dy = torch.zeros((B, self.m), **f64) if dy is None else None
             outs = [self.vjp(A_bm, x, y, s, dx[k], zero_dy if dy is None else dy[k], P_bm=P_bm, path=path, lsqr=lsqr, q_eval=q_eval) for k in range(K)]
             res = (torch.stack([o[0].t() for o in outs]).contiguous(), torch.stack([o[1].t() for o in outs]).contiguous(), torch.stack([o[2] for o in outs]))
@@ -408,9 +414,10 @@ class ConeEngine:
         dA = torch.empty((K, B, self.nnz_aug), **f64)
         dq = torch.empty((K, B, self.n + 1), **f64)
         adj = torch.empty((K, B), dtype=torch.int32, device=dev)
-        rc = _lib.lib().ce_vjp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
-                                    None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
-        _lib.check(rc, "ce_vjp_many")
+        fn, name = (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else (_lib.lib().ce_vjp_many, "ce_vjp_many")
+        rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
+        _lib.check(rc, name)
         return dA, dq, adj
 
     def _q_args(self, q_eval):

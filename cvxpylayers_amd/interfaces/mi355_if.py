@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, qp_adjoint, refine_steps, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, qp_adjoint, refine_steps, tri_adjoint, unpack_rule)
 
 
 class MI355_ctx:
@@ -153,6 +153,7 @@ class _Saved(NamedTuple):
     lpgd: Optional[tuple] = None            # lpgd_rule() of this call: (mode, tau, rho), or None -- the implicit-function adjoint differentiates the node
     fwd_path: str = "per_instance"          # ConeEngine.last_path right after the solve: the path the perturbed solves follow
     qp_adjoint: str = "pivoting"            # qp_adjoint() of this call: "search_free" sends adjoint_many of a native QP node to ce_vjp_qp_many (backward() ignores it)
+    tri_adjoint: str = "pivoting"           # tri_adjoint() of this call: "search_free" sends adjoint_many of a node with exponential / power cones to ce_vjp_tri_many (backward() ignores it)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -184,6 +185,7 @@ class _ConeLayer(torch.autograd.Function):
                           explicit_lookback="acceleration_lookback" in merged_args)
         n_refine = refine_steps(merged_args)
         qp_adj = qp_adjoint(merged_args)          # (validated with the other arguments; read by adjoint_many alone)
+        tri_adj = tri_adjoint(merged_args)        # (likewise)
         n_newton = newton_first(merged_args)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
@@ -247,7 +249,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -401,13 +403,14 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
             keep = ~failed[:, None]
             dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
             x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
-        out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm, qp_many=(saved.qp_adjoint == "search_free"))
+        out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm, qp_many=(saved.qp_adjoint == "search_free"),
+                           tri_many=(saved.tri_adjoint == "search_free"))
         dA, dq, adj = out[:3]
         dP = out[3] if saved.P_bm is not None else None
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
-            if eng.last_vjp_kernel == "ce_vjp_qp_many":
-                info["adjoint"]["path"] = "ce_vjp_qp_many"
+            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many"):
+                info["adjoint"]["path"] = eng.last_vjp_kernel
         if K > 0 and batch_size > 0:
             any_k = adj[0].clone()
             for k in range(1, K):

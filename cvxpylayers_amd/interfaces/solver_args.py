@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -112,6 +112,21 @@ def qp_adjoint(merged_args: dict) -> str:
     mode = str(merged_args.get("qp_adjoint", "pivoting"))
     if mode not in ("pivoting", "search_free"):
         raise ValueError(f"MI355 solver: qp_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
+    return mode
+
+
+def tri_adjoint(merged_args: dict) -> str:
+    """Which elimination serves MANY cotangents at one solution (CvxpyLayer.jacobian in the reverse direction, interfaces.mi355_if.adjoint_many) on a template with
+    exponential / power cones:
+    absent / "pivoting" -> K calls of ce_vjp, the pivoting kernel, one factorisation per cotangent;
+    "search_free" -> one ce_vjp_tri_many call per chunk: the search-free elimination diagonalises and rotates each triple and factors each instance once for every
+    cotangent (templates without it -- PSD cones, n > 108 -- keep the loop; info["adjoint"]["path"] tells which ran).  The two agree on regular instances but need
+    not flag the same ones (a pivot search there; here a weighted triple row with 1 - lambda < 1e-5 flags too); a flagged instance gets LSQR's minimum-norm answer,
+    hence opt-in.
+    The single-cotangent backward of .backward() ignores the key: one cotangent belongs to ce_vjp.  Templates without such cones ignore it too."""
+    mode = str(merged_args.get("tri_adjoint", "pivoting"))
+    if mode not in ("pivoting", "search_free"):
+        raise ValueError(f"MI355 solver: tri_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
     return mode
 
 

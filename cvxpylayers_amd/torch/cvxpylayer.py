@@ -462,6 +462,11 @@ class CvxpyLayer(torch.nn.Module):
         ce_vjp_qp_many call per chunk instead (the search-free elimination with P factors each instance once and returns dP too; a chunk's dP then counts against
         max_bytes beside its dA; info["adjoint"]["path"] == "ce_vjp_qp_many").  Opt-in: a rank-deficient instance keeps that route's dropped-variable answer with
         status 4.  The single-cotangent backward of .backward() ignores the key.
+        A template with exponential / power cones runs the loop of K ce_vjp calls (the pivoting kernel) here by default; solver_args {"tri_adjoint": "search_free"}
+        makes one ce_vjp_tri_many call per chunk instead (the search-free elimination diagonalises and rotates each triple and factors each instance once for the
+        chunk; chunking by max_bytes is unchanged; info["adjoint"]["path"] == "ce_vjp_tri_many").  Opt-in: the two kernels need not flag the same instances (a pivot
+        search there; here a weighted triple row with 1 - lambda < 1e-5 flags too), and a flagged instance gets LSQR's minimum-norm answer.  .backward() ignores
+        the key; direction="forward" and "auto" keep their rules (the forward many-mode does not serve such templates).
         Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
 
         direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q

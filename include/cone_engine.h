@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -557,6 +557,24 @@ int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
 /* >= 0: the template runs a quadratic objective inside the kernels and has the search-free elimination with P; the value is ce_qp_ns_variant's row (same
  * footprint, the launch plan is unchanged).  -1 otherwise, and for a NULL handle. */
 int ce_vjp_qp_many_variant(ce_handle h);
+
+/* MANY COTANGENTS AT ONE SOLUTION, EXPONENTIAL / POWER CONES: for every k < K what ce_vjp returns for (dx[k], dy[k]) on a template with exponential or 3-d power
+ * triples beside plain cones (linear objective, no PSD block), from ONE factorisation per instance by the search-free elimination -- where ce_vjp runs the pivoting
+ * kernel once per cotangent.  Once per instance D Pi of every triple is diagonalised, W diag(lambda) W^T, its three rows of A are rotated (a rotated row is an
+ * equality, a dropped row or one weighted row of the reduced Hessian) and steps 1-4 run on a zero right-hand side; per cotangent the kernel rebuilds what ce_vjp_many
+ * rebuilds plus h = W^T dy_c per triple (d_B entry, 0, or d = lambda h with the share theta h of f), and rotates r_y back, r_y,c = W r~_y,c, in front of the dA row
+ * (csrc/ce_backward_ns.h, TRI + MANY without FWD).
+ *   Arguments, layouts, dy == NULL, K == 1, q_vals == NULL / a switched-off re-solve (K ce_vjp calls inside) and the error rules are exactly ce_vjp_many's.
+ * Flags belong to the matrix: a vanishing pivot, more active rows than variables, or a weighted triple row with 1 - lambda < 1e-5 (the forward derivative's rule
+ * for a stiff row, carried over) flag the instance for every k; it is listed once and the LSQR kernel walks the list once per cotangent (status 4 | 8).  The
+ * pivoting kernel behind ce_vjp need not flag the same instances: a flagged instance gets LSQR's minimum-norm answer.
+ * CE_E_UNSUPPORTED with a ce_last_error that names the reason when ce_vjp_tri_many_variant(h) < 0.  ce_vjp_many keeps refusing such templates. */
+int ce_vjp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                    double *dA_vals, double *dq_vals, int *adj_status, void *stream);
+/* >= 0: the template has the many-cotangent mode with triples; the value is ce_tri_ns_variant's row (same footprint, the launch plan is unchanged).  -1 otherwise,
+ * and for a NULL handle. */
+int ce_vjp_tri_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */

@@ -1,0 +1,232 @@
+"""Time of K cotangents at one solution of a template with exponential cones: ce_vjp_tri_many (the search-free elimination with triples, one factorisation per
+instance, ConeEngine.vjp_many(tri_many=True)) against K sequential ce_vjp calls (the pivoting kernel k_backward_rt, one factorisation per cotangent), one box
+(DESIGN.md section 3.16).
+
+The logistic-regression shape E (problems.CONFIGS["E"]: n = 40, 12 nonnegative rows, one second-order block of 4, 24 exponential cones) at the eps = 1e-8 point:
+B = 4096 with K = 1, 2, 8, and B = 1024 with K = n = 40 (the reverse Jacobian's shape: one cotangent per output); then CvxpyLayer.jacobian whole at B = 1024 for a
+layer on shape E with parameters A, b and c (A is a parameter so that the instances have matrices of their own, as the batch above has) under both values of
+solver_args tri_adjoint.
+
+Per case wall time with the device idle before the clock starts and after it stops, alternating per repetition:
+  (a) K sequential ConeEngine.vjp calls of ANOTHER BUILD of this repository (--parent TREE: a checkout of the parent commit with its library built), run by a
+      child process that is asked for one measurement at a time -- omitted without --parent;
+  (b) the same K sequential calls of this build;
+  (c) this build's vjp_many(tri_many=True).
+All three under the default re-solve rule with q_eval given (flagged instances go through the LSQR kernel in all three); outputs are allocated inside the clock.
+Medians of --reps after --warmup calls, with min and max, and the number of flagged instances of each route; per case also (b) and (c) on the sub-batch of the instances
+ce_vjp_tri_many does not flag (`without_flagged_instances`: no instance to re-solve behind either route, the two eliminations alone).  Prints one JSON line; --out
+also writes it.
+
+    python scripts/vjp_tri_many_timing.py [--reps 30] [--warmup 5] [--parent TREE] [--out profiles/vjp_tri_many/vjp_tri_many_E.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+
+def _args():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--parent", default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-layer", action="store_true", help="skip the CvxpyLayer.jacobian comparison")
+    ap.add_argument("--layer-reps", type=int, default=3)
+    ap.add_argument("--worker", action="store_true")          # (internal: serve single measurements of the tree in --tree over stdin / stdout)
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    return ap.parse_args()
+
+
+a = _args()
+sys.path.insert(0, a.tree)
+
+import torch  # noqa: E402
+
+from cvxpylayers_amd import problems as P  # noqa: E402
+from cvxpylayers_amd.interfaces.mi355_if import ConeEngine, make_settings  # noqa: E402
+
+SEED, EPS = 11, 1e-8
+N = P.CONFIGS["E"]["n"]
+CASES = ((4096, 1), (4096, 2), (4096, 8), (1024, N))          # (B, K)
+
+
+class Bench:
+    """shape E at batch size B, solved by this build at eps 1e-8, and Gaussian cotangents"""
+
+    def __init__(self, B):
+        self.B = B
+        self.dev = torch.device("cuda", 0)
+        self.n, self.cones = N, P.CONFIGS["E"]["cones"]
+        A, b, c = P.generate(self.n, self.cones, B, seed=SEED)
+        self.tpl = P.dense_template(self.n, self.cones)
+        self.eng = ConeEngine(self.tpl.indices, self.tpl.indptr, self.tpl.n, self.tpl.m, self.tpl.cones, self.dev)
+        A_eval, q_eval = self.tpl.values_from_dense(A, b, c)
+        self.A_bm = torch.from_numpy(np.ascontiguousarray(A_eval.T)).to(self.dev); self.q_t = torch.from_numpy(q_eval).to(self.dev)
+        out = self.eng.solve(self.A_bm, self.q_t, make_settings({"eps": EPS, "max_iters": 100000}))
+        self.pt = tuple(out[:3])
+        self.unsolved = int((out[4] != 1).sum())
+        self._cot = {}
+
+    def cotangents(self, K):
+        if K not in self._cot:
+            g = torch.Generator(device="cpu").manual_seed(SEED + K)
+            self._cot[K] = tuple(torch.randn((K, self.B, w), generator=g, dtype=torch.float64).to(self.dev) for w in (self.n, self.tpl.m))
+        return self._cot[K]
+
+    def sequential(self, K):
+        """K ce_vjp calls: (wall ms, flagged instances)"""
+        dx, dy = self.cotangents(K)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = [self.eng.vjp(self.A_bm, *self.pt, dx[k], dy[k], path="per_instance", q_eval=self.q_t) for k in range(K)]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, int((outs[0][2] != 0).sum())
+
+    def many(self, K):
+        dx, dy = self.cotangents(K)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = self.eng.vjp_many(self.A_bm, *self.pt, dx, dy, path="per_instance", q_eval=self.q_t, tri_many=True)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        assert self.eng.last_vjp_many_path == "many" and self.eng.last_vjp_kernel == "ce_vjp_tri_many"
+        return ms, int((out[2][0] != 0).sum())
+
+    def without_flagged(self):
+        """the same point restricted to the instances ce_vjp_tri_many does not flag: no LSQR walk behind either route there, the eliminations alone"""
+        dx, dy = self.cotangents(1)
+        st = self.eng.vjp_many(self.A_bm, *self.pt, dx, dy, path="per_instance", q_eval=self.q_t, tri_many=True)[2][0]
+        keep = torch.nonzero(st == 0).flatten()
+        sub = object.__new__(Bench)
+        sub.__dict__.update(self.__dict__)
+        sub.B, sub.A_bm, sub.q_t, sub.pt, sub._cot = int(keep.numel()), self.A_bm[keep].contiguous(), self.q_t[:, keep].contiguous(), tuple(t[keep].contiguous() for t in self.pt), {}
+        return sub
+
+    def agreement(self, K):
+        """largest relative difference between the two routes on the instances neither flags"""
+        dx, dy = self.cotangents(K)
+        m = self.eng.vjp_many(self.A_bm, *self.pt, dx, dy, path="per_instance", q_eval=self.q_t, tri_many=True)
+        l = self.eng.vjp_many(self.A_bm, *self.pt, dx, dy, path="per_instance", q_eval=self.q_t, force_loop=True)
+        both = (m[2] == 0) & (l[2] == 0)
+        e = ((m[0] - l[0]).abs().amax(dim=2) / (1 + l[0].abs().amax(dim=2)))[both]
+        return float(e.max()), float(both.double().mean())
+
+
+def worker():
+    benches = {}
+    print("ready", flush=True)
+    for line in sys.stdin:
+        req = json.loads(line)
+        if req["B"] not in benches:
+            benches[req["B"]] = Bench(req["B"])
+        ms, fl = benches[req["B"]].sequential(req["K"])
+        print(json.dumps({"ms": ms, "flagged": fl}), flush=True)
+
+
+def stat(v):
+    return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+
+
+ROUTES = (("reverse_search_free", dict(solver_args={"tri_adjoint": "search_free"})), ("reverse_pivoting", dict()))
+
+
+def layer_jacobian(reps, B=1024):
+    """CvxpyLayer.jacobian whole under both values of tri_adjoint, alternating; each includes the forward solve"""
+    from cvxpylayers_amd.torch import CvxpyLayer, VariableRecovery
+    from cvxpylayers_amd.torch.templates import template_from_affine_builder
+    cones = P.CONFIGS["E"]["cones"]
+    m = P.cone_rows(cones)
+    A, b, c = P.generate(N, cones, B, seed=SEED)
+    tpl = template_from_affine_builder(lambda Ap, bp, cp: (Ap, bp, cp), [(m, N), (m,), (N,)], cones, [VariableRecovery(slice(0, N), None, (N,))])
+    layer = CvxpyLayer(template=tpl, solver_args={"eps": EPS, "max_iters": 100000, "raise_on_error": False})
+    params = [torch.from_numpy(t).cuda() for t in (A, b, c)]
+    eng = layer.ctx.solver_ctx.engine(torch.device("cuda", 0))
+    t, paths, flagged, err = {k: [] for k, _ in ROUTES}, {}, {}, {}
+    for it in range(1 + reps):
+        jac = {}
+        for key, kw in ROUTES:
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            _, jac[key] = layer.jacobian(*params, **kw)
+            torch.cuda.synchronize(); ms = (time.perf_counter() - t0) * 1e3
+            paths[key] = [eng.last_vjp_many_path, layer.info["adjoint"]["path"]]
+            st = layer.info["adjoint"]["status"]
+            flagged[key] = int((st[0] != 0).sum())
+            jac[key] = (jac[key], st)
+            if it >= 1:
+                t[key].append(ms)
+        both = ((jac["reverse_search_free"][1] == 0) & (jac["reverse_pivoting"][1] == 0)).all(dim=0)
+        err["search_free_against_pivoting_on_unflagged"] = max(float(torch.nan_to_num(f[both] - r[both]).abs().max() / (1 + torch.nan_to_num(r[both]).abs().max()))
+                                                               for f, r in zip(jac["reverse_search_free"][0][0], jac["reverse_pivoting"][0][0]))
+        err["unflagged_by_both"] = int(both.sum())
+        del jac
+    return {"B": B, "outputs": N, "parameter_entries": tpl.n_params_total, "reps": reps, "layer": "shape E with parameters A (88 x 40), b and c; x is the output",
+            "wall_ms": {k: stat(v) for k, v in t.items()}, "paths": paths, "flagged": flagged, **err}
+
+
+def main():
+    benches = {B: Bench(B) for B in sorted({B for B, _ in CASES})}
+    child = None
+    if a.parent:
+        child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--tree", os.path.abspath(a.parent)],
+                                 stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, cwd=os.path.abspath(a.parent))
+        assert child.stdout.readline().strip() == "ready"
+    rows, subs = [], {}
+    for B, K in CASES:
+        bench = benches[B]
+        t = {"a_parent_sequential": [], "b_sequential": [], "c_many": []}
+        fl = {}
+        for it in range(a.warmup + a.reps):
+            if child is not None:
+                child.stdin.write(json.dumps({"B": B, "K": K}) + "\n"); child.stdin.flush()
+                r = json.loads(child.stdout.readline())
+                fl["a_parent_sequential"] = r["flagged"]
+                if it >= a.warmup:
+                    t["a_parent_sequential"].append(r["ms"])
+            for key, fn in (("b_sequential", bench.sequential), ("c_many", bench.many)):
+                ms, fl[key] = fn(K)
+                if it >= a.warmup:
+                    t[key].append(ms)
+        st = {k_: stat(v) for k_, v in t.items() if v}
+        row = {"B": B, "K": K, "wall_ms": st, "per_cotangent_ms": {k_: v["median"] / K for k_, v in st.items()}, "flagged": fl,
+               "flagged_share": {k_: v / B for k_, v in fl.items()}, "unsolved_instances": bench.unsolved}
+        row["max_rel_difference_on_unflagged"], row["unflagged_by_both"] = bench.agreement(K)
+        sub = subs.setdefault(B, bench.without_flagged())          # (the flagged instances left out: what the two eliminations cost with no instance to re-solve)
+        ts = {"b_sequential": [], "c_many": []}
+        fls = {}
+        for it in range(a.warmup + a.reps):
+            for key, fn in (("b_sequential", sub.sequential), ("c_many", sub.many)):
+                ms, fls[key] = fn(K)
+                if it >= a.warmup:
+                    ts[key].append(ms)
+        row["without_flagged_instances"] = {"B": sub.B, "wall_ms": {k_: stat(v) for k_, v in ts.items()}, "flagged": fls}
+        ref = st.get("a_parent_sequential", st["b_sequential"])
+        row["many_bracket_below_sequential"] = st["c_many"]["max"] < ref["min"]
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    if child is not None:
+        child.stdin.close(); child.wait(timeout=60)
+    b0 = benches[CASES[0][0]]
+    res = {"config": "E", "eps": EPS, "n": b0.n, "m": b0.tpl.m, "nnz_aug": b0.tpl.nnz_aug, "reps": a.reps, "warmup": a.warmup,
+           "device": torch.cuda.get_device_name(0), "parent": bool(a.parent), "rows": rows}
+    del benches
+    if not a.no_layer:
+        try:
+            res["layer_jacobian"] = layer_jacobian(a.layer_reps)
+        except Exception as e:          # (a record of the calls is worth keeping when the layer comparison fails)
+            res["layer_jacobian"] = {"error": f"{type(e).__name__}: {e}"}
+        print(json.dumps({"layer_jacobian": res["layer_jacobian"]}), file=sys.stderr, flush=True)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    worker() if a.worker else main()
