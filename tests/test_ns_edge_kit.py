@@ -82,6 +82,38 @@ def test_every_planted_instance_is_a_regular_kkt_point(group):
             assert pt["nf"].min() > 0, (name, "the reduced Hessian is empty")
 
 
+def test_the_two_dense_references_are_transposes_of_each_other():
+    """the references of tests/test_gpu_ns_many_edges.py against each other, at every served plain and qp case: the oracle's dense adjoint (with P for the QP kind)
+    at that file's first cotangent draw and dense_jvp at tangents(pt) satisfy
+        <xb, dx> + <yb, dy> = <dA, tA> + <db, tb> + <dc, tc> (+ <dP, tP>)
+    within 1e-10 (1 + |lhs| + |rhs|) on every instance -- dense symmetric dP against dense symmetric tP.  Both are backward-stable dense solves of systems with
+    cond <= 1e11 whose right-hand sides are O(1): the identity's two sides differ by eps cond |solution|^2 at the very worst, and by far less in practice."""
+    from oracle import oracle
+    worst = ("", 0.0)
+    for name, (shape, plan, what) in K.all_cases().items():
+        kind = shape[0]
+        if kind == "tri" or not pk.ns_served(kind, plan):
+            continue
+        pt = K.point(name, shape, **K.plant_args(name))
+        rng = np.random.default_rng(pt["seed"] + 31)
+        xb, yb = rng.standard_normal(pt["x"].shape), rng.standard_normal(pt["y"].shape)
+        kw = dict(P=pt["Pm"]) if kind == "qp" else {}
+        g = oracle.adjoint_batch(pt["A"], pt["b"], pt["c"], pt["cones"], pt["x"], pt["y"], pt["s"], xb, yb, mode="dense", **kw)
+        tA, tb, tc, tP = t = K.tangents(pt)
+        dx, dy, ds, ok = K.dense_jvp(pt, t)
+        assert ok.all(), (name, ok)
+        lhs = (xb * dx).sum(axis=1) + (yb * dy).sum(axis=1)
+        rhs = (g["dA"] * tA).sum(axis=(1, 2)) + (g["db"] * tb).sum(axis=1) + (g["dc"] * tc).sum(axis=1)
+        if kind == "qp":
+            assert np.abs(g["dP"] - g["dP"].transpose(0, 2, 1)).max() <= 1e-12 * (1 + np.abs(g["dP"]).max()), name          # the dense dP is symmetric
+            rhs = rhs + (g["dP"] * tP).sum(axis=(1, 2))
+        e = np.abs(lhs - rhs) / (1 + np.abs(lhs) + np.abs(rhs))
+        print(f"{name}: transpose identity of the two references max {e.max():.2e}, max |lhs| {np.abs(lhs).max():.2e}")
+        assert (e <= 1e-10).all() and np.abs(lhs).max() > 1e-3, (name, e)
+        worst = max(worst, (name, float(e.max())), key=lambda w: w[1])
+    print("worst:", worst)
+
+
 def test_the_three_states_of_a_triple_occur():
     seen = np.zeros(3, int)
     for name, (shape, plan, what) in K.all_cases().items():
