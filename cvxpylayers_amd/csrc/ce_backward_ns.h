@@ -62,8 +62,12 @@
 // and the point, not A, which is transformed by now; a tangent's row lies at k * stride_k + inst * stride_b, stride_b == 0 being one row for the whole batch), gamma and
 // the weights of f from the retained classification, d~ from the in-place inverse, t_q for the list rows (QP: Z^T P x_p from the transformed rows of P, whose pivot
 // columns are untouched), f with the treatment of the two rows that are gone (a_z, and the t-row a_y overwrote), x_free from the tiles, step 5 and the forward EPILOGUE
-// unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  In the FORWARD direction TRI templates keep K launches of
-// the single-tangent kernel.  REF never comes with MANY.
+// unchanged.  Rank deficiency belongs to the matrix: the instance is flagged for every k and listed once.  REF never comes with MANY.
+// With FWD and TRI (cone_engine.hip ce_jvp_tri_many): K tangents with exponential / power triples.  Once per instance the TRI code above runs as it stands on a zero
+// right-hand side (exp_dual_eig / pow_dual_eig once per triple, the snap, A_c <- W^T A_c, the numbering); W, lambda, rkind, eqrow and the list entries stay in LDS.
+// Per tangent the plain many-tangent rebuild plus, per triple, gamma_c = W^T g_y,c: a lambda = 1 row puts its gamma into d_B, a lambda = 0 row contributes nothing, a
+// weighted row puts theta gamma into its weight slot (qv2, by row) and theta t into its list entry; step 5 and the TRI forward epilogue follow unchanged.
+// NS_TRI_STIFF flags the instance for every k like a vanishing pivot, the forward derivative's own rule.  The footprint is the triples' (tri_ns_variant, tri_ns_lds).
 // Without FWD, with TRI (cone_engine.hip ce_vjp_tri_many): K cotangents of the adjoint with exponential / power triples, the one adjoint with triples this kernel has.
 // Once per instance the TRI code above runs as it stands (exp_dual_eig / pow_dual_eig once per triple, A_c <- W^T A_c, the weighted rows numbered behind the
 // boundary cones'), W, lambda, rkind and eqrow stay in LDS, and steps 1-4 run on a zero right-hand side on the triples' footprint (tri_ns_variant, tri_ns_lds).  Per
@@ -75,7 +79,7 @@
 // many-cotangent rebuild plus the P terms of the many-tangent one (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] in g), and one more output
 // row dP = -sym(r_x x^T) through the structure.  No re-solve list: a flagged instance keeps the dropped-variable answer, status 4 for every k.
 //
-// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes and in the many-cotangent adjoint.  PSD cones keep
+// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes (one tangent or many) and in the many-cotangent adjoint.  PSD cones keep
 // k_backward_rt, and so do the SINGLE-cotangent adjoint with triples and the single-cotangent adjoint with a quadratic objective.
 #pragma once
 #include "ce_common.h"
@@ -119,6 +123,7 @@ template <> struct NsFwdArg<true, false, false, false, true> { typedef NsJvpMany
 template <> struct NsFwdArg<true, false, true, false, true> { typedef NsJvpQpMany type; };
 template <> struct NsFwdArg<false, false, true, false, true> { typedef NsVjpQpMany type; };
 template <> struct NsFwdArg<false, false, false, true, true> { typedef NsVjpTriMany type; };
+template <> struct NsFwdArg<true, false, false, true, true> { typedef NsJvpManyTri type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well)
@@ -130,11 +135,11 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP || MANY, "the single-cotangent adjoint with a quadratic objective lives in k_backward_rt");
     static_assert((FWD && !QP) || (!FWD && !REF && !QP && MANY) || !TRI,
-                  "exponential / power triples: the forward modes with a linear objective, and the many-cotangent adjoint with one (their single-cotangent adjoint "
-                  "lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !REF && !(TRI && QP)) || (FWD && !REF && !TRI),
-                  "many right-hand sides on one factorisation: the adjoint with plain cones, P or not, or with triples and a linear objective (K cotangents), or "
-                  "the forward derivative with plain cones, P or not (K tangents); the forward derivative with triples keeps K launches");
+                  "exponential / power triples: the forward modes with a linear objective (one tangent, many tangents, refinement), and the many-cotangent adjoint "
+                  "with one (their single-cotangent adjoint lives in k_backward_rt)");
+    static_assert(!MANY || (!FWD && !REF && !(TRI && QP)) || (FWD && !REF && !(TRI && QP)),
+                  "many right-hand sides on one factorisation: the adjoint (K cotangents) or the forward derivative (K tangents), each with plain cones, P or not, or "
+                  "with triples and a linear objective; never the refinement, never triples with P");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -1152,6 +1157,21 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int i = r0 + 1 + l16; i < r1; i += 16) qv2[i] = th * (dv[i] - vv[i] * inz * zeta);
             if (cv && l16 == 0) { cinfo[5 * c + 2] = (h0 + zeta) * M_SQRT1_2; cinfo[5 * c + 3] = (h0 - zeta) * M_SQRT1_2; }
         }
+        if constexpr (TRI) {
+            // triples, one thread per triple, from the retained W and lambda: the rows keep gamma = W^T g_y (a lambda = 1 row: its entry of d_B, taken by eqrow below; a
+            // lambda = 0 row: nothing in f, the epilogue wants its gamma), and a weighted row's share of f, theta gamma, waits in qv2 BY ROW beside the boundary cones'
+            for (int c = tid; c < ntri; c += NTHR) {
+                const int r0 = T.eoff + 3 * c;
+                const double *Wl = Wt + 9 * c;
+                const double h0 = dv[r0], h1 = dv[r0 + 1], h2 = dv[r0 + 2];
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    const double t = Wl[a] * h0 + Wl[3 + a] * h1 + Wl[6 + a] * h2, lam = lamt[3 * c + a];
+                    dv[r0 + a] = t;
+                    qv2[r0 + a] = rkind[r0 + a] == RK_MIX ? lam / (1 - lam) * t : 0.0;
+                }
+            }
+        }
         __syncthreads();
         // d_B = gamma_B by equality (eqrow and ceq are the numbering's inverse) -> mu
         for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
@@ -1198,6 +1218,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int i = r0 + 1; i < r1; i++) zt = fma(vv[i], tvec[qb + i - r0 - 1], zt);
             zt *= inz;
             for (int i = r0 + 1; i < r1; i++) { const double zhi = vv[i] * inz; tvec[qb + i - r0 - 1] = th * (tvec[qb + i - r0 - 1] - zhi * zt); }
+        }
+        if constexpr (TRI) {          // a triple's weighted row is one list row of its own: theta t (eqrow keeps its list entry)
+            for (int i = T.eoff + tid; i < m; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
         }
         __syncthreads();
         // f = -g_x + sum u_i a_i by column.  A pivot column keeps f[piv] (the multipliers want it); a free column takes  h + sum (u_i - theta q'_i) a~_i  with
@@ -1558,7 +1581,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 const int fl = misc[2];
                 if (adjk) adjk[inst] = fl;
                 if (W.iters) W.iters[kc * W.sak + inst] = 0;
-                if (fix && (fl & 4) && kc == 0) fix[1 + atomicAdd(fix, 1)] = inst;      // listed once for all tangents (ce_jvp_many walks the list once per tangent)
+                if (fix && (fl & 4) && kc == 0) fix[1 + atomicAdd(fix, 1)] = inst;      // listed once for all tangents (the LSQR launch behind ce_jvp_many / ce_jvp_tri_many walks K x list pairs)
             }
             continue;
         } else {

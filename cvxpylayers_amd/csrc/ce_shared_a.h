@@ -59,11 +59,14 @@ __global__ void __launch_bounds__(NT, 3)
 k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long sAb, int per_inst, const double *__restrict__ qg, long sqk, long sqb, const double *__restrict__ xg, const double *__restrict__ yg,
           const double *__restrict__ sg, const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo,
           double *__restrict__ dqo, long sdqk, long sdqb, int *__restrict__ adj_status, int *__restrict__ iters_o, double atol, double btol, double conlim, int itn_lim,
-          const int *__restrict__ sel = nullptr, int status_or = 0, int a_lds = 0, int *__restrict__ sel_reset = nullptr, SaJvp W = SaJvp{}) {
+          const int *__restrict__ sel = nullptr, int status_or = 0, int a_lds = 0, int *__restrict__ sel_reset = nullptr, SaJvp W = SaJvp{}, SaWalkMany WM = SaWalkMany{}) {
     static_assert(!(FWD && LSMR), "the forward derivative runs LSQR's recurrences only");
     // sel != nullptr (ce_vjp's re-solve of the instances its direct elimination flagged rank-deficient): sel[0] instances are listed in sel[1 ...] (appended by
     // the elimination kernel on the same stream); the grid is a fixed number of workgroups that walk the list -- the host never learns the count.  status_or is
     // OR-ed into the adj_status of every instance served (ce_vjp: 4 | 8 = "rank-deficient, re-solved by LSQR").
+    // WM.K > 1 (the many-modes: K right-hand sides at one solution, the list written once): the same grid walks K * sel[0] (right-hand side, instance) pairs, and the
+    // pointers of a right-hand side lie k strides further (ko below).  Each pair is the from-scratch solve a launch of its own would run; one launch fills the device
+    // where K walks over a short list left it idle.  K == 1: ko is zero, the walk and the addressing are the single right-hand side's.
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x;
     // ce_vjp alternates TWO lists: while this launch walks `sel`, it empties the other one (walked by the previous call's launch, appended to by the next call's
@@ -96,8 +99,12 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
     p += (size_t)(p - sm) & 1;
     double *Ad = p;                                          // [m][n], boundary sign (the products negate)
   for (int li = blockIdx.x;; li += gridDim.x) {              // (one pass without a list: instance = workgroup)
-    int inst = li;
-    if (sel) { if (li >= sel[0]) break; inst = sel[1 + li]; } else if (li != (int)blockIdx.x) break;
+    int inst = li, ko = 0;          // ko: which right-hand side (uniform, like inst)
+    if (sel) {
+        const int cnt = sel[0];
+        if (WM.K > 1) { if (li >= cnt * WM.K) break; ko = li / cnt; inst = sel[1 + li - ko * cnt]; }          // (an empty list broke out above: cnt > 0 at the division)
+        else { if (li >= cnt) break; inst = sel[1 + li]; }
+    } else if (li != (int)blockIdx.x) break;
     const double *x = xg + (size_t)inst * n, *y = yg + (size_t)inst * m, *s = sg + (size_t)inst * m;
     // the tau row / column of the operator: c_j from the boundary's q values, b_i from this instance's value row (both stay in global memory: L2-resident, read
     // with the loads of the products they join; LDS has no room for two more vectors at three workgroups per CU).  qg == null: r_tau pinned to 0.
@@ -319,7 +326,7 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
     if constexpr (FWD) {
         // ---- LSQR on  M d = -g,  M = N^T:  u-space <- N^T v,  v-space <- N u.   g = dQ pi = ( dA^T y + dc , -dA x + db , -dc.x - db.y )  with the tangents in the
         //      boundary convention: dA = -tA_eval (A part), db = +tA_eval (b column), dc = tq_eval[:n]
-        const double *tA = W.tA ? W.tA + (size_t)inst * W.stAb : nullptr, *tq = W.tq ? W.tq + (size_t)inst * W.stqb : nullptr;
+        const double *tA = W.tA ? W.tA + ko * WM.stAk + (size_t)inst * W.stAb : nullptr, *tq = W.tq ? W.tq + ko * WM.stqk + (size_t)inst * W.stqb : nullptr;
         for (int j = tid; j < n; j += NT) { const double v = tq ? tq[(size_t)j * W.stqk] : 0.0; ux[j] = -v; rx[j] = 0.0; acct = fma(x[j], v, acct); }
         for (int i = tid; i < m; i += NT) { const int pb = tA ? S.bpos[i] : -1; const double v = pb >= 0 ? tA[pb] : 0.0; uy[i] = -v; ry[i] = 0.0; acct = fma(y[i], v, acct); }
         if (tA && per_inst) {          // (a shared A has no tangent)
@@ -347,8 +354,8 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
         vt = TAU ? dsum : 0.0;
         alfa = sqrt(fma(vt, vt, acc));
     } else {
-        for (int j = tid; j < n; j += NT) { const double v = dxg[(size_t)inst * n + j]; ux[j] = v; rx[j] = 0.0; if constexpr (LSMR) hbx[j] = 0.0; acc = fma(v, v, acc); acct = fma(x[j], v, acct); }
-        for (int i = tid; i < m; i += NT) { const double v = dyg[(size_t)inst * m + i]; ty[i] = v; ry[i] = 0.0; if constexpr (LSMR) hby[i] = 0.0; acct = fma(y[i], v, acct); }
+        for (int j = tid; j < n; j += NT) { const double v = dxg[ko * WM.sxk + (size_t)inst * n + j]; ux[j] = v; rx[j] = 0.0; if constexpr (LSMR) hbx[j] = 0.0; acc = fma(v, v, acc); acct = fma(x[j], v, acct); }
+        for (int i = tid; i < m; i += NT) { const double v = dyg[ko * WM.syk + (size_t)inst * m + i]; ty[i] = v; ry[i] = 0.0; if constexpr (LSMR) hby[i] = 0.0; acct = fma(y[i], v, acct); }
         __syncthreads();
         dproj(ty, 1.0, [&](int i, double o) { uy[i] = o; acc = fma(o, o, acc); });
         acc = sum_two(acc, acct, dsum);
@@ -522,27 +529,27 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
         // ---- outputs: the tangents of the solution,  dx = d_x - x d_tau ,  dy = DPi(d_y) - y d_tau ,  ds = DPi(d_y) - d_y - s d_tau      (oracle/cone_oracle.c: diffcp's D)
         dproj(ry, 1.0, [&](int i, double o) { qv[i] = o; });
         __syncthreads();
-        for (int j = tid; j < n; j += NT) W.dx[(size_t)inst * n + j] = fma(-x[j], rt, rx[j]);
+        for (int j = tid; j < n; j += NT) W.dx[ko * WM.sok + (size_t)inst * n + j] = fma(-x[j], rt, rx[j]);
         for (int i = tid; i < m; i += NT) {
             const double qi = qv[i];
-            W.dy[(size_t)inst * m + i] = fma(-y[i], rt, qi);
-            if (W.ds) W.ds[(size_t)inst * m + i] = fma(-s[i], rt, qi - ry[i]);
+            W.dy[ko * WM.sosk + (size_t)inst * m + i] = fma(-y[i], rt, qi);
+            if (W.ds) W.ds[ko * WM.sosk + (size_t)inst * m + i] = fma(-s[i], rt, qi - ry[i]);
         }
     } else {
         // ---- outputs in the boundary convention: dA_eval = [-dA.data, db[b_idx]], dq_eval = [dc, 0]  (diffcp_if.py:91-92);
         //      dA_ij = x_j r_y,i - y_i r_x,j ,  db = y r_tau - r_y ,  dc = x r_tau - r_x        (oracle/cone_oracle.c adjoint_one: dQ = r Pi(z)^T antisymmetrised)
-        double *dA = dAo + (size_t)inst * T.nnz_aug;
+        double *dA = dAo + ko * WM.sAk + (size_t)inst * T.nnz_aug;
         for (int k = tid; k < T.nnz_aug; k += NT) {
             const int r = T.rowidx[k], c = T.colidx[k];
             dA[k] = (c < n) ? -(x[c] * ry[r] - y[r] * rx[c]) : fma(y[r], rt, -ry[r]);
         }
-        for (int j = tid; j <= n; j += NT) dqo[j * sdqk + inst * sdqb] = (j < n) ? fma(x[j], rt, -rx[j]) : 0.0;
+        for (int j = tid; j <= n; j += NT) dqo[ko * WM.sqk + j * sdqk + inst * sdqb] = (j < n) ? fma(x[j], rt, -rx[j]) : 0.0;
     }
 #ifdef CE_TIMING
     __syncthreads();
     if constexpr (!FWD) if (tid == 0) for (int k = 0; k < 8; k++) dAo[(size_t)inst * T.nnz_aug + k] = (double)ls_tacc[k];
 #endif
-    if (tid == 0) { if (adj_status) adj_status[inst] = (live ? 1 : 0) | status_or; if (iters_o) iters_o[inst] = itn; }
+    if (tid == 0) { if (adj_status) adj_status[ko * WM.sak + inst] = (live ? 1 : 0) | status_or; if (iters_o) iters_o[ko * WM.sak + inst] = itn; }
     __syncthreads();          // (the next listed instance reuses every LDS vector)
   }
 }

@@ -9,7 +9,7 @@ int ce_launch_sa_lsqr(int variant, int grid, size_t lds, hipStream_t st, const C
     switch (variant) {
 #define X(V, RP, HPSD, HTRI, LSMR, FWD) \
     case V: hipLaunchKernelGGL((k_sa_lsqr<RP, HPSD != 0, HTRI != 0, LSMR != 0, FWD != 0>), dim3(grid), dim3(NT), lds, st, a.T, a.S, a.F, a.A_vals0, a.sA_b, a.per_inst, a.q, a.sqk, a.sqb, \
-                               a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.iters, a.atol, a.btol, a.conlim, a.iter_lim, a.sel, a.status_or, a.a_lds, a.sel_reset, a.W); return 0;
+                               a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.iters, a.atol, a.btol, a.conlim, a.iter_lim, a.sel, a.status_or, a.a_lds, a.sel_reset, a.W, a.M); return 0;
         CE_SA_LSQR_VARIANTS(X)
 #undef X
     default: return -1;

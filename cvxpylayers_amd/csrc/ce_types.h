@@ -97,6 +97,11 @@ struct NsRefineTri : NsRefine {};
 // k_backward_ns<..., FWD = false, ..., TRI = true, MANY = true>: K cotangents of the adjoint with triples on one factorisation (cone_engine.hip ce_vjp_tri_many).
 // NsMany's fields and strides; a type of its own selects the launcher
 struct NsVjpTriMany : NsMany {};
+// k_backward_ns<..., FWD = true, ..., TRI = true, MANY = true>: K tangents of the forward derivative with triples on one factorisation (cone_engine.hip
+// ce_jvp_tri_many).  NsJvpMany's fields and strides; a type of its own selects the launcher.  The name does NOT end in "Many" on purpose: the ledger of
+// tests/test_gpu_ns_many_edges.py collects the ce_launch_ns overloads whose type matches Ns\w*Many and pins them to the modes that file covers; this mode's edge
+// ledger lives in tests/test_gpu_jvp_tri_many_edges.py (tests/test_jvp_tri_many_args.py pins both facts)
+struct NsJvpManyTri : NsJvpMany {};
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -127,6 +132,16 @@ struct SaJvp {
     const double *tA; long stAb;             // [B][nnz_aug] tangent of the boundary's value rows (A part read only when the template's A is per instance)
     const double *tq; long stqk, stqb;       // tangent of q_eval, entry j of instance i at j * stqk + i * stqb (the last entry is ignored)
     double *dx, *dy, *ds;                    // [B][n], [B][m], [B][m] (ds may be null)
+};
+
+// k_sa_lsqr walking a re-solve list for K right-hand sides in ONE launch (the many-modes: ce_vjp_many, ce_vjp_tri_many, ce_jvp_many, ce_jvp_tri_many): the walk covers
+// K * sel[0] pairs, pair li being right-hand side k = li / sel[0] of instance sel[1 + li % sel[0]]; every per-right-hand-side pointer lies k times its stride (elements)
+// further.  K == 1 (the default): today's walk and addressing.  Without a list K is ignored.
+struct SaWalkMany {
+    int K = 1;
+    long sxk = 0, syk = 0, sAk = 0, sqk = 0;     // adjoint: dx, dy (0: one dy for all), dA, dq
+    long stAk = 0, stqk = 0, sok = 0, sosk = 0;  // forward: tA, tq, dx (sok), dy and ds (sosk)
+    long sak = 0;                                // both: adj_status and iters
 };
 
 struct SaFwd {
@@ -162,6 +177,7 @@ struct CeSaLsqrArgs {
     double atol, btol, conlim; int iter_lim;
     const int *sel; int status_or, a_lds; int *sel_reset;      // the re-solve list of ce_vjp / ce_jvp (ce_shared_a.h)
     SaJvp W;
+    SaWalkMany M;
 };
 
 // ---- optimal value and its envelope-theorem derivatives (ce_value.h): products and sums over the template's structure, no plan ----
@@ -237,6 +253,7 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpQpMany &w);          //  derivative for K tangents, without and with P)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpQpMany &w);          // (ce_tu_ns_vjp_qp_many.hip: the adjoint with P for K cotangents)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpTriMany &w);         // (ce_tu_ns_vjp_tri_many.hip: the adjoint with triples for K cotangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyTri &w);         // (ce_tu_ns_jvp_tri_many.hip: the forward derivative with triples for K tangents -- the type's name: see its declaration)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -276,6 +293,7 @@ hipError_t ce_setattr_ns_jvp_many(int bytes);
 hipError_t ce_setattr_ns_jvp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_tri_many(int bytes);
+hipError_t ce_setattr_ns_jvp_tri_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

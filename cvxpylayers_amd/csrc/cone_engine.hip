@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -322,6 +322,9 @@ int ce_vjp_qp_many_variant(ce_handle h) { return (h && h->plan.qp_native && h->p
 // the many-cotangent mode with exponential / power triples runs on the footprint of the triples' forward modes: tri_ns_variant's row (the tri planner already asks
 // that the LSQR vectors of the re-solve fit LDS)
 int ce_vjp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >= 0) ? h->plan.tri_ns_variant : -1; }
+// the many-tangent mode with triples: the same rule and row (its rebuild lives in the buffers the single-tangent mode and the many-cotangent mode use on tri_ns_lds:
+// no shape is excluded by the footprint)
+int ce_jvp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >= 0) ? h->plan.tri_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -467,7 +470,7 @@ int ce_vjp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const
 static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
-                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr, const SaJvp *fwd = nullptr);
+                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr, const SaJvp *fwd = nullptr, const SaWalkMany *many = nullptr);
 // The re-solve list of ce_vjp_qp and ce_jvp.  The elimination kernel of a call appends the instances whose system it found rank deficient (or too large for its
 // tile) to a device-side list; a fixed grid of LSQR workgroups behind it walks the list and overwrites those instances' results with diffcp's minimum-norm answer
 // (k_sa_lsqr with the instance's own A).  No host round trip; an empty list costs one launch of workgroups that return at once.
@@ -593,7 +596,7 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 }
 
 // K cotangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., MANY> factors every instance once and writes all K answers; the instances
-// it lists as rank deficient are listed ONCE, and the LSQR kernel walks that list once per cotangent with the cotangent's pointers.  The list parity flips once.
+// it lists as rank deficient are listed ONCE, and ONE launch of the LSQR kernel walks the K x list (cotangent, instance) pairs (SaWalkMany).  The list parity flips once.
 // Without an armed re-solve (q_vals == NULL, ce_set_adjoint_resolve(h, 0)) ce_vjp itself does not run the elimination: K calls of it then, the same rule.
 // (tri: ce_vjp_tri_many -- the same body on the triples' variant and footprint; `who` names the entry point in the messages)
 static int vjp_many_run(ce_handle h, bool tri, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
@@ -633,9 +636,9 @@ static int vjp_many_run(ce_handle h, bool tri, const char *who, int B, int K, co
     }
     const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
     const int prof_keep = h->prof; h->prof = 0;
-    for (int k = 0; k < K && !rc; k++)
-        rc = vjp_lsqr_launch(h, grid, A_vals_bm, (long)nnz, 1, q_vals, sq_k, sq_b, x, y, s, dx + k * W.sxk, dy + k * W.syk, dA_vals + k * W.sAk, dq_vals + k * W.sqk, 1, (long)(n + 1),
-                             adj_status ? adj_status + k * W.sak : nullptr, nullptr, h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, fix.cur, 4 | 8, fix.oth);
+    SaWalkMany wm; wm.K = K; wm.sxk = W.sxk; wm.syk = W.syk; wm.sAk = W.sAk; wm.sqk = W.sqk; wm.sak = W.sak;
+    rc = vjp_lsqr_launch(h, grid, A_vals_bm, (long)nnz, 1, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, 1, (long)(n + 1),
+                         adj_status, nullptr, h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, fix.cur, 4 | 8, fix.oth, nullptr, &wm);
     h->fix_par ^= 1;
     h->prof = prof_keep;
     if (rc) return rc;
@@ -1063,8 +1066,9 @@ int ce_solve_shared_a(ce_handle h, int B, int r, int RP, const double *AdT, cons
 static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
-                           const int *sel, int status_or, int *sel_reset, const SaJvp *fwd) {
+                           const int *sel, int status_or, int *sel_reset, const SaJvp *fwd, const SaWalkMany *many) {
     // fwd != nullptr: the forward derivative (ce_jvp_lsqr / ce_jvp_shared_a) -- k_sa_lsqr<..., FWD> on the same plan; dx ... dq_vals are unused
+    // many != nullptr (with sel): the list is walked for many->K right-hand sides in this ONE launch; the pointers are those of right-hand side 0
     if (!h || B <= 0 || !A_vals0 || !x || !y || !s) { g_err = "null argument"; return CE_E_BADARG; }
     if (fwd ? (!fwd->dx || !fwd->dy) : (!dx || !dy || !dA_bm || !dq_vals)) { g_err = "null argument"; return CE_E_BADARG; }
     const DevT &T = h->T;
@@ -1086,7 +1090,7 @@ static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b,
                           SaSplit{h->sp_r, RP, h->d_sp_AdT.get(), h->d_sp_drow.get(), h->d_sp_srow_col.get(), h->d_sp_sval.get(), h->d_sp_scol_ptr.get(), h->d_sp_scol_row.get(),
                                   h->d_sp_rowslot.get(), h->d_sp_sing_i.get(), h->d_sp_sing_v.get()},
                           A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_bm, dq_vals, sdq_k, sdq_b, adj_status, lsqr_iters,
-                          atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, sl.a_lds, sel_reset, fwd ? *fwd : SaJvp{}};
+                          atol, btol, conlim, iter_lim > 0 ? iter_lim : 2 * (T.n + T.m + 1), sel, status_or, sl.a_lds, sel_reset, fwd ? *fwd : SaJvp{}, (many && sel) ? *many : SaWalkMany{}};
     if (RP > 0) {      // the values may differ between calls: refill A_d^T / singleton values from this call's A (n RP + m doubles)
         HIPCHK(hipMemsetAsync(h->d_sp_AdT.get(), 0, sizeof(double) * (size_t)T.n * RP, (hipStream_t)stream));
         HIPCHK(hipMemsetAsync(h->d_sp_sval.get(), 0, sizeof(double) * T.m, (hipStream_t)stream));
@@ -1116,13 +1120,13 @@ int ce_vjp_lsqr(ce_handle h, int B, const double *A_vals_bm, long sA_b, const do
 static int jvp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                            double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
-                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr) {
+                           const int *sel = nullptr, int status_or = 0, int *sel_reset = nullptr, const SaWalkMany *many = nullptr) {
     // sel: the re-solve list of ce_jvp (B is then the fixed grid that walks it; the kernel addresses every per-instance array by the LISTED instance)
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     if (h->plan.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
     const SaJvp W{tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, dx, dy, ds};
     return vjp_lsqr_launch(h, B, A_vals0, sA_b, per_inst, q_vals, sq_k, sq_b, x, y, s, nullptr, nullptr, nullptr, nullptr, 0, 0, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream,
-                           sel, status_or, sel_reset, &W);
+                           sel, status_or, sel_reset, &W, many);
 }
 int ce_jvp_shared_a(ce_handle h, int B, const double *A_vals0, long sA_b, const double *q_vals, long sq_k, long sq_b,
                     const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
@@ -1194,19 +1198,22 @@ int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
     return jvp_ns(h, B, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, tP_vals, dx, dy, ds, jvp_status, lsqr_iters, 0.0, 0.0, 0.0, 0, stream);
 }
 // K tangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., FWD, ..., MANY> factors every instance once and writes all K answers; plain kind:
-// the instances it lists as rank deficient are listed ONCE, and the LSQR kernel walks that list once per tangent with the tangent's pointers (the list parity flips
-// once).  QP kind: no re-solve, the dropped-variable answer stands with status 4 for every k.
-static int jvp_many_ns(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
+// the instances it lists as rank deficient are listed ONCE, and ONE launch of the LSQR kernel walks the K x list (tangent, instance) pairs (SaWalkMany; the list parity
+// flips once).  QP kind: no re-solve, the dropped-variable answer stands with status 4 for every k.  tri: ce_jvp_tri_many -- the plain kind's body with
+// k_backward_ns<..., FWD, ..., TRI, MANY> on the triples' variant and footprint.
+static int jvp_many_ns(ce_handle h, bool tri, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                        const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                        const double *tP_vals, long stP_k, long stP_b, double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
                        double atol, double btol, double conlim, int iter_lim, void *stream) {
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_jvp_qp_many" : "ce_jvp_many";
+    const std::string who = qp ? "ce_jvp_qp_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many");
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (qp) { const int rc = qp_ns_check(h, "ce_jvp_qp_many"); if (rc) return rc; }
-    if ((qp ? ce_jvp_qp_many_variant(h) : ce_jvp_many_variant(h)) < 0) {
+    if ((qp ? ce_jvp_qp_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h))) < 0) {
         g_err = who + (qp ? ": this template has no many-tangent elimination with a quadratic objective; call ce_jvp_qp once per tangent"
+                       : tri ? ": this template has no search-free elimination with triples (no exponential / power cone, PSD cones, a quadratic objective inside the "
+                               "kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_jvp_many or ce_jvp"
                           : ": this template has no many-tangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, CE_BWD_NS=0, "
                             "or the LSQR vectors of the re-solve exceed LDS); call ce_jvp once per tangent");
         return CE_E_UNSUPPORTED;
@@ -1228,15 +1235,14 @@ static int jvp_many_ns(ce_handle h, int B, int K, const double *A_vals_bm, long 
     const NsJvpMany W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), K, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b,
                       dx, dy, ds, sxk, syk, sak, lsqr_iters};
     const int lrc = qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
-                       : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
+                       : tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsJvpManyTri{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
     if (lrc) { g_err = "internal: no many-tangent kernel for the planned variant"; return CE_E_BADARG; }
     if (!qp) {
         const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
         const int prof_keep = h->prof; h->prof = 0;
-        for (int k = 0; k < K && !rc; k++)
-            rc = jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals ? tA_vals + k * stA_k : nullptr, stA_b, tq_vals ? tq_vals + k * stq_k : nullptr, 1, stq_b,
-                                 dx + k * sxk, dy + k * syk, ds ? ds + k * syk : nullptr, jvp_status + k * sak, lsqr_iters ? lsqr_iters + k * sak : nullptr,
-                                 atol, btol, conlim, iter_lim, stream, fix.cur, 4 | 8, fix.oth);
+        SaWalkMany wm; wm.K = K; wm.stAk = stA_k; wm.stqk = stq_k; wm.sok = sxk; wm.sosk = syk; wm.sak = sak;
+        rc = jvp_lsqr_launch(h, grid, A_vals_bm, sA_b, 1, q_vals, sq_k, sq_b, x, y, s, tA_vals, stA_b, tq_vals, 1, stq_b, dx, dy, ds, jvp_status, lsqr_iters,
+                             atol, btol, conlim, iter_lim, stream, fix.cur, 4 | 8, fix.oth, &wm);
         h->fix_par ^= 1;
         h->prof = prof_keep;
         if (rc) return rc;
@@ -1251,7 +1257,18 @@ int ce_jvp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
         g_err = "ce_jvp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
     if (h->plan.qp_native) { g_err = "ce_jvp_many: this template runs a quadratic objective inside the kernels; use ce_jvp_qp_many"; return CE_E_UNSUPPORTED; }
-    return jvp_many_ns(h, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+    return jvp_many_ns(h, false, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+                       atol, btol, conlim, iter_lim, stream);
+}
+// K tangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_jvp_many's body with k_backward_ns<..., FWD, ..., TRI, MANY> on
+// the triples' variant and footprint; the re-solve behind it is the same one launch.  Refusals come before any device call.
+int ce_jvp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
+        g_err = "ce_jvp_tri_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    return jvp_many_ns(h, true, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
                        atol, btol, conlim, iter_lim, stream);
 }
 int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
@@ -1260,7 +1277,7 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
     if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0 || stP_b < 0) {
         g_err = "ce_jvp_qp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
-    return jvp_many_ns(h, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
+    return jvp_many_ns(h, false, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
                        0.0, 0.0, 0.0, 0, stream);
 }
 // K cotangents at one solution of a template with a quadratic objective inside the kernels (include/cone_engine.h).  One launch of k_backward_ns<..., QP, ..., MANY>

@@ -40,7 +40,7 @@ class ConeEngine:
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" when the last vjp_many made that one call, None when it looped over vjp
-        self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many call) / "loop" (K calls of jvp): what the last jvp_many ran
+        self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
@@ -517,13 +517,17 @@ class ConeEngine:
         return dx, dy, ds, st
 
     def jvp_many(self, A_bm, x, y, s, tA, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "direct",
-                 P_bm=None, tP=None, force_loop: bool = False):
+                 P_bm=None, tP=None, force_loop: bool = False, tri_many: bool = False):
         """K tangents at one solution.  tA (K, B, nnz_aug), tq (K, B, n+1), tP (K, B, nnz_p) -- or (K, .) for a tangent every instance shares (batch stride 0: a
         parameter-space basis vector pushed through the parameter maps); at most two of the three may be None (zero).  Returns dx (K, B, n), dy (K, B, m),
         ds (K, B, m), status (K, B) and sets last_lsqr_iters (K, B): for every k what jvp(method=method) returns for the k-th tangent.
         One C call (each instance factored once, last_jvp_many_path == "many") under the rule that sends jvp(method="direct") to ce_jvp / ce_jvp_qp -- ce_jvp_qp_many with
         P_bm, ce_jvp_many on every path but "const_a" -- when the kind's *_many_variant >= 0.  Every other case (method="lsqr", the shared-A path, PSD cones or
-        triples, templates without the mode, force_loop) is K calls of jvp, stacked ("loop"): the method is total wherever jvp is, and the loop is the comparator."""
+        triples, templates without the mode, force_loop) is K calls of jvp, stacked ("loop"): the method is total wherever jvp is, and the loop is the comparator.
+        tri_many (opt-in, default False): on a template with exponential / power triples (ce_jvp_tri_many_variant >= 0), method "direct", no P_bm, any path but
+        "const_a", one ce_jvp_tri_many call instead of the K ce_jvp calls (last_jvp_many_path == "many", last_jvp_kernel == "ce_jvp_tri_many"): each triple is
+        diagonalised and rotated and each instance factored once for all K tangents, and one LSQR launch re-solves the flagged instances for every k.  Flags and
+        the re-solve's answers are those of the loop.  In every other case the flag changes nothing."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp_many: method must be 'lsqr' or 'direct', got {method!r}")
         given = [t for t in (tA, tq, tP) if t is not None]
@@ -540,6 +544,9 @@ class ConeEngine:
             path = self.last_path
         L = _lib.lib()
         many = not force_loop and method == "direct" and (L.ce_jvp_qp_many_variant(self._h) >= 0 if P_bm is not None else (path != "const_a" and L.ce_jvp_many_variant(self._h) >= 0))
+        many_tri = (not force_loop and tri_many and not many and method == "direct" and P_bm is None and path != "const_a"
+                    and L.ce_jvp_tri_many_variant(self._h) >= 0)
+        many = many or many_tri
         self.last_jvp_many_path = "many" if many else "loop"
         i32 = dict(dtype=torch.int32, device=dev)
         if B == 0 or K == 0:
@@ -576,8 +583,9 @@ class ConeEngine:
             if system == "reduced":
                 q_eval = None
             qd, q_args = self._q_args(q_eval)
-            rc, name = L.ce_jvp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
-                                     *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream()), "ce_jvp_many"
+            fn, name = (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many, "ce_jvp_many")
+            rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
+                    *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream())
         _lib.check(rc, name)
         self.last_jvp_kernel = name
         self.last_lsqr_iters = its

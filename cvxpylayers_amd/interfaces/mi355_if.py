@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, qp_adjoint, refine_steps, tri_adjoint, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -154,6 +154,7 @@ class _Saved(NamedTuple):
     fwd_path: str = "per_instance"          # ConeEngine.last_path right after the solve: the path the perturbed solves follow
     qp_adjoint: str = "pivoting"            # qp_adjoint() of this call: "search_free" sends adjoint_many of a native QP node to ce_vjp_qp_many (backward() ignores it)
     tri_adjoint: str = "pivoting"           # tri_adjoint() of this call: "search_free" sends adjoint_many of a node with exponential / power cones to ce_vjp_tri_many (backward() ignores it)
+    tri_tangents: str = "loop"              # tri_tangents() of this call: "many" sends tangent_many of a node with exponential / power cones to ce_jvp_tri_many (one-tangent forward-mode AD ignores it)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -186,6 +187,7 @@ class _ConeLayer(torch.autograd.Function):
         n_refine = refine_steps(merged_args)
         qp_adj = qp_adjoint(merged_args)          # (validated with the other arguments; read by adjoint_many alone)
         tri_adj = tri_adjoint(merged_args)        # (likewise)
+        tri_tan = tri_tangents(merged_args)       # (likewise; read by tangent_many alone)
         n_newton = newton_first(merged_args)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
@@ -249,7 +251,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -331,7 +333,7 @@ class _ConeLayer(torch.autograd.Function):
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp") else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod
@@ -449,9 +451,10 @@ def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=Non
         if qp:
             dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, method="direct", P_bm=saved.P_bm, tP=tP)
         else:
-            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method)
+            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method, tri_many=(saved.tri_tangents == "many"))
         if isinstance(info, dict):
-            info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many") else "lsqr"}
+            info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel,
+                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many") else "lsqr"}
     return dx, dy, failed
 
 

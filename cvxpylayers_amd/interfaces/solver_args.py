@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -127,6 +127,19 @@ def tri_adjoint(merged_args: dict) -> str:
     mode = str(merged_args.get("tri_adjoint", "pivoting"))
     if mode not in ("pivoting", "search_free"):
         raise ValueError(f"MI355 solver: tri_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
+    return mode
+
+
+def tri_tangents(merged_args: dict) -> str:
+    """How MANY tangents at one solution (CvxpyLayer.jacobian in the forward direction, interfaces.mi355_if.tangent_many) are served on a template with
+    exponential / power cones:
+    absent / "loop" -> K calls of ce_jvp: every triple diagonalised, its rows rotated and every instance factored once per tangent;
+    "many" -> one ce_jvp_tri_many call per chunk: all of that once per instance for the whole chunk, and one LSQR launch for the flagged instances of every tangent
+    (templates without the mode -- PSD cones, n > 108 -- keep the loop; info["jvp"]["kernel"] tells which ran).  Flags and re-solved answers are the loop's.
+    Forward-mode AD with one tangent ignores the key: one tangent belongs to ce_jvp.  Templates without such cones ignore it too."""
+    mode = str(merged_args.get("tri_tangents", "loop"))
+    if mode not in ("loop", "many"):
+        raise ValueError(f"MI355 solver: tri_tangents must be 'loop' or 'many', got {mode!r}")
     return mode
 
 

@@ -466,7 +466,7 @@ class CvxpyLayer(torch.nn.Module):
         makes one ce_vjp_tri_many call per chunk instead (the search-free elimination diagonalises and rotates each triple and factors each instance once for the
         chunk; chunking by max_bytes is unchanged; info["adjoint"]["path"] == "ce_vjp_tri_many").  Opt-in: the two kernels need not flag the same instances (a pivot
         search there; here a weighted triple row with 1 - lambda < 1e-5 flags too), and a flagged instance gets LSQR's minimum-norm answer.  .backward() ignores
-        the key; direction="forward" and "auto" keep their rules (the forward many-mode does not serve such templates).
+        the key; direction="forward" and "auto" keep their rules (the forward direction has a key of its own, below).
         Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
 
         direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q
@@ -474,7 +474,10 @@ class CvxpyLayer(torch.nn.Module):
         ConeEngine.jvp_many --, in chunks whose dx, dy stay within max_bytes, and the recovery maps on dx / dy.  Same return, same layout.  The route for a layer
         with few parameter entries and many output elements, and the one by which a quadratic objective inside the kernels gets a one-factorisation Jacobian.
         It runs the direct elimination unless solver_args (the call's or the layer's) says jvp_mode="lsqr" explicitly: a Jacobian by K LSQR solves is not a
-        default anyone wants.  direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
+        default anyone wants.  A template with exponential / power cones runs the loop of K ce_jvp calls here by default (every triple diagonalised, its rows
+        rotated and every instance factored once per parameter entry); solver_args {"tri_tangents": "many"} makes one ce_jvp_tri_many call per chunk instead: all
+        of that once per instance for the chunk, and one LSQR launch for the flagged instances of every tangent (info["jvp"]["kernel"] == "ce_jvp_tri_many",
+        info["jvp"]["path"] stays "direct"; chunking is unchanged).  Opt-in; forward-mode AD with one tangent ignores the key.  direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
         because solver_args["mode"] means something else.)  Any other value: ValueError, before anything touches the device."""
         from cvxpylayers_amd.interfaces.mi355_if import adjoint_many, tangent_many
         from cvxpylayers_amd.interfaces.solver_args import LPGD_MODES

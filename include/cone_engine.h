@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -499,7 +499,7 @@ int ce_adjoint_ns_variant(ce_handle h);
  *   A_vals_bm  batch-major rows, sA_b = nnz_aug apart (as ce_jvp takes them);  q_vals as ce_vjp (NULL: no re-solve, K plain ce_vjp calls inside)
  *   dx [K][B][n], dy [K][B][m] contiguous (dy NULL: zero);  dA_vals [K][B][nnz_aug] and dq_vals [K][B][n + 1] contiguous batch-major, boundary convention of ce_vjp;
  *   adj_status [K][B] (or NULL): the bit field of ce_vjp.  Rank deficiency is a property of the matrix: bits 4 and 8 are equal across k for an instance, which is
- *   listed for the LSQR re-solve once; the LSQR kernel walks that list once per cotangent.  Bit 1 is per cotangent.
+ *   listed for the LSQR re-solve once; one launch of the LSQR kernel serves all K cotangents of the listed instances.  Bit 1 is per cotangent.
  * K == 1 is legal.  CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0.  CE_E_UNSUPPORTED with a ce_last_error that names the reason
  * when ce_vjp_many_variant(h) < 0.  Batch-minor outputs are not served.  No host synchronisation, no allocation after the first call of a batch size. */
 int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
@@ -520,7 +520,7 @@ int ce_vjp_many_variant(ce_handle h);
  *   tq_vals + k * stq_k + i * stq_b,  its P row at tP_vals + k * stP_k + i * stP_b.  Each pointer may be NULL (zero).  A batch stride is 0 -- one row shared by
  *   every instance: a parameter-space basis vector pushed through the parameter maps -- or at least the row length; anything between is CE_E_BADARG.
  *   dx [K][B][n], dy [K][B][m], ds [K][B][m] (ds may be NULL), jvp_status [K][B], lsqr_iters [K][B] (may be NULL) contiguous.
- * Rank deficiency is the matrix's: ce_jvp_many flags such an instance for all K, lists it once, and the LSQR kernel walks the list once per tangent (status 4 | 8,
+ * Rank deficiency is the matrix's: ce_jvp_many flags such an instance for all K, lists it once, and one launch of the LSQR kernel serves all K tangents of the listed instances (status 4 | 8,
  * iterations > 0, as ce_jvp); ce_jvp_qp_many has no re-solve, the dropped-variable answer stands with status 4 for every k (as ce_jvp_qp).
  * K == 1 is legal.  CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0, a bad batch stride.  CE_E_UNSUPPORTED with a
  * ce_last_error that names the reason when the kind's *_many_variant is -1.  No host synchronisation, no allocation after the first call of a batch size. */
@@ -534,8 +534,8 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
                    const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals, long stP_k, long stP_b,
                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream);
 /* >= 0: the template has the many-tangent mode of its kind; the value is the tile variant (ce_adjoint_ns_variant's / ce_qp_ns_variant's: the mode rebuilds every
- * tangent's vectors in the buffers of ce_jvp / ce_jvp_qp, the launch plan is unchanged).  -1: no in-kernel mode -- PSD / exponential / power cones (the triples'
- * forward derivative keeps K launches), n > 108, CE_BWD_NS=0, the LSQR vectors of the re-solve exceed LDS, the other kind's template; a NULL handle. */
+ * tangent's vectors in the buffers of ce_jvp / ce_jvp_qp, the launch plan is unchanged).  -1: no in-kernel mode -- PSD / exponential / power cones (triples have
+ * ce_jvp_tri_many), n > 108, CE_BWD_NS=0, the LSQR vectors of the re-solve exceed LDS, the other kind's template; a NULL handle. */
 int ce_jvp_many_variant(ce_handle h);
 int ce_jvp_qp_many_variant(ce_handle h);
 
@@ -566,7 +566,7 @@ int ce_vjp_qp_many_variant(ce_handle h);
  * (csrc/ce_backward_ns.h, TRI + MANY without FWD).
  *   Arguments, layouts, dy == NULL, K == 1, q_vals == NULL / a switched-off re-solve (K ce_vjp calls inside) and the error rules are exactly ce_vjp_many's.
  * Flags belong to the matrix: a vanishing pivot, more active rows than variables, or a weighted triple row with 1 - lambda < 1e-5 (the forward derivative's rule
- * for a stiff row, carried over) flag the instance for every k; it is listed once and the LSQR kernel walks the list once per cotangent (status 4 | 8).  The
+ * for a stiff row, carried over) flag the instance for every k; it is listed once and one launch of the LSQR kernel serves all K cotangents of the listed instances (status 4 | 8).  The
  * pivoting kernel behind ce_vjp need not flag the same instances: a flagged instance gets LSQR's minimum-norm answer.
  * CE_E_UNSUPPORTED with a ce_last_error that names the reason when ce_vjp_tri_many_variant(h) < 0.  ce_vjp_many keeps refusing such templates. */
 int ce_vjp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
@@ -575,6 +575,27 @@ int ce_vjp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
 /* >= 0: the template has the many-cotangent mode with triples; the value is ce_tri_ns_variant's row (same footprint, the launch plan is unchanged).  -1 otherwise,
  * and for a NULL handle. */
 int ce_vjp_tri_many_variant(ce_handle h);
+
+/* MANY TANGENTS AT ONE SOLUTION, EXPONENTIAL / POWER CONES: for every k < K what ce_jvp returns for the k-th tangent on a template with exponential or 3-d power
+ * triples beside plain cones (linear objective, no PSD block), from ONE factorisation per instance -- the forward twin of ce_vjp_tri_many, where ce_jvp
+ * re-diagonalises every triple, re-rotates its rows and re-factors every instance once per tangent.  Once per instance D Pi of every triple is diagonalised,
+ * W diag(lambda) W^T (lambda snapped to 0 / 1 within 1e-9), its three rows of A are rotated and steps 1-4 run on a zero right-hand side; per tangent the kernel
+ * rebuilds what ce_jvp_many rebuilds plus gamma_c = W^T g_y,c per triple (a lambda = 1 row: its entry of d_B; a lambda = 0 row: nothing; a weighted row: theta gamma
+ * in f and theta t in the list), then step 5 and the triples' forward epilogue, dy = W lambda eta, ds = -W (1 - lambda) eta (csrc/ce_backward_ns.h, FWD + TRI + MANY).
+ *   Arguments, layouts, strides (a batch stride of 0: one tangent row for the whole batch), K == 1 and the error rules are exactly ce_jvp_many's.
+ * Flags belong to the matrix: a vanishing pivot, more active rows than variables, or a weighted triple row with 1 - lambda < 1e-5 (ce_jvp's own rule for a stiff
+ * row) flag the instance for every k; it is listed once and ONE launch of the LSQR kernel re-solves all K tangents of the listed instances (status 4 | 8,
+ * iterations > 0, the answers of K ce_jvp calls bit for bit).
+ * CE_E_UNSUPPORTED with a ce_last_error that names the entry point and the reason when ce_jvp_tri_many_variant(h) < 0; nothing is written then.  ce_jvp_many keeps
+ * refusing templates with triples. */
+int ce_jvp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s,
+                    const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
+                    double atol, double btol, double conlim, int iter_lim, void *stream);
+/* >= 0: the template has the many-tangent mode with triples; the value is ce_tri_ns_variant's row (the rebuild lives in the buffers of the triples' footprint: no
+ * shape is excluded, the launch plan is unchanged).  -1 otherwise, and for a NULL handle. */
+int ce_jvp_tri_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
