@@ -55,6 +55,15 @@
 // REF: y-hat of a triple is exp_project_dual / pow_project_dual_of_entry from the cold start exp_dual_eig / pow_dual_eig evaluate at -- the same decision, the
 // rule of ns_soc_kind.  W and lambda live behind the index arrays in LDS (ns_layout's TRI mode).
 //
+// PSD = true (with FWD, REF or not; never QP, TRI or MANY): PSD blocks beside the plain cones (cone_engine.hip ce_jvp_psd, ce_refine_psd: entry points of their own, ce_jvp
+// and ce_refine keep refusing such templates).  smat(v_c) = U Lambda U^T by the workgroup's Jacobi sweeps (ce_psd_jacobi.h); in the basis E_ab = svec(sym(u_a u_b^T))
+// D Pi is diagonal with eigenvalue B_ab (1 / 0 / l+ / (l+ - l-), k_backward_rt's comparisons, no snap).  The block's rows of A are rotated in place,
+// a~ = svec(U^T smat(a) U) per column, gamma = Q^T g_y with them; afterwards a rotated row is an equality, a dropped row or ONE weighted row of the list, exactly a
+// triple's rows, and steps 1-5 run unchanged.  The epilogue computes eta of the rotated rows and rotates back,  dy_c = Q (B o eta),  ds_c = -Q ((1 - B) o eta),
+// Q r = svec(U smat(r) U^T).  REF: y-hat_c = svec(U max(Lambda, 0) U^T) from the decomposition that gives B; a full step that fails the safeguard is tried again at
+// 1/2, 1/4, 1/8 of its length (the REF epilogue: this mode alone).  NS_TRI_STIFF flags the forward derivative's instance
+// with a weighted PSD row of 1 - B below it: carried over, not measured on PSD rows.  U, Lambda, B and the scratch live behind the index arrays (ns_layout's PSD mode).
+//
 // MANY = true: K right-hand sides on ONE factorisation of the instance.  Steps 1-4 depend on (A, x, y, s [, P]) alone and run once, on a zero right-hand side; the sweep is an
 // in-place inversion, so -(Z^T (H [+ P]) Z)^-1 stays in the accumulator tiles and B_1^-1 in the pivot columns, and each right-hand side is rebuilt behind the sweep, then
 // step 5 and the mode's epilogue run on the same buffers.  Without FWD (cone_engine.hip ce_vjp_many): K cotangents of the plain adjoint.  With FWD, QP or not
@@ -79,11 +88,13 @@
 // many-cotangent rebuild plus the P terms of the many-tangent one (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] in g), and one more output
 // row dP = -sym(r_x x^T) through the structure.  No re-solve list: a flagged instance keeps the dropped-variable answer, status 4 for every k.
 //
-// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes (one tangent or many) and in the many-cotangent adjoint.  PSD cones keep
-// k_backward_rt, and so do the SINGLE-cotangent adjoint with triples and the single-cotangent adjoint with a quadratic objective.
+// Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes (one tangent or many) and in the many-cotangent adjoint.  PSD blocks in the forward
+// derivative and the refinement with PSD.  The adjoint of PSD templates keeps k_backward_rt, and so do the SINGLE-cotangent adjoint with triples and the single-cotangent
+// adjoint with a quadratic objective.
 #pragma once
 #include "ce_common.h"
 #include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
+#include "ce_psd_jacobi.h"         // PSD: psd_jacobi
 
 #include "ce_ns_layout.h"          // ns_layout: the LDS segments of this kernel and its footprint (what the launch plan and tests/test_ns_layout_host.py use); bwd_ns_ldp, bwd_ns_nsl,
                                    // bwd_ns_kwmax, bwd_ns_union_doubles.  The carve below is still the kernel's own statement of the same layout.
@@ -111,7 +122,7 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
 // measured on the forward derivative, not on the adjoint.
 constexpr double NS_TRI_STIFF = 1e-5;
 
-template <bool FWD, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false> struct NsFwdArg { typedef NsNoJvp type; };
+template <bool FWD, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false, bool PSD = false> struct NsFwdArg { typedef NsNoJvp type; };
 template <> struct NsFwdArg<true, false> { typedef NsJvp type; };
 template <> struct NsFwdArg<true, true> { typedef NsRefine type; };
 template <> struct NsFwdArg<true, false, true> { typedef NsJvpQp type; };
@@ -124,14 +135,16 @@ template <> struct NsFwdArg<true, false, true, false, true> { typedef NsJvpQpMan
 template <> struct NsFwdArg<false, false, true, false, true> { typedef NsVjpQpMany type; };
 template <> struct NsFwdArg<false, false, false, true, true> { typedef NsVjpTriMany type; };
 template <> struct NsFwdArg<true, false, false, true, true> { typedef NsJvpManyTri type; };
+template <> struct NsFwdArg<true, false, false, false, false, true> { typedef NsJvpPsd type; };
+template <> struct NsFwdArg<true, true, false, false, false, true> { typedef NsRefinePsd type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
-// frames of their own, planned for two as well)
-template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false>
-__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? ((QP || TRI) ? 2 : 3) : 1))
+// frames of their own, planned for two as well; PSD: the block's segments on top of A leave room for two at the shapes it serves)
+template <int NTILE, int NTHR, bool FWD = false, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false, bool PSD = false>
+__global__ void __launch_bounds__(NTHR, (NTHR == 256 ? ((QP || TRI || PSD) ? 2 : 3) : 1))
 k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict__ xg, const double *__restrict__ yg, const double *__restrict__ sg,
               const double *__restrict__ dxg, const double *__restrict__ dyg, double *__restrict__ dAo, double *__restrict__ dqo, long sdqk, long sdqb,
-              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI, MANY>::type W) {
+              int *__restrict__ adj_status, int *__restrict__ fix, typename NsFwdArg<FWD, REF, QP, TRI, MANY, PSD>::type W) {
     static_assert(FWD || !REF, "the refinement step is the forward derivative's elimination with its own prologue and epilogue");
     static_assert(FWD || !QP || MANY, "the single-cotangent adjoint with a quadratic objective lives in k_backward_rt");
     static_assert((FWD && !QP) || (!FWD && !REF && !QP && MANY) || !TRI,
@@ -140,6 +153,7 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     static_assert(!MANY || (!FWD && !REF && !(TRI && QP)) || (FWD && !REF && !(TRI && QP)),
                   "many right-hand sides on one factorisation: the adjoint (K cotangents) or the forward derivative (K tangents), each with plain cones, P or not, or "
                   "with triples and a linear objective; never the refinement, never triples with P");
+    static_assert(!PSD || (FWD && !QP && !TRI && !MANY), "PSD blocks: the forward derivative and the refinement, linear objective, one right-hand side, no triple beside them");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -199,6 +213,18 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         Wt = (double *)ip;           // per triple: W (row-major 3 x 3, eigenvectors in the columns) of D Pi_K*(v)
         lamt = Wt + 9 * ntri;        // per rotated triple row: its eigenvalue after the snap
     }
+    // PSD: per block U and Lambda of smat(v_c), per rotated row its eigenvalue B of D Pi, the Jacobi scratch and one (X, W) pair per wave for the rotations (ns_layout's
+    // PSD mode: nothing here aliases the union region).  The blocks' rows are psd0 .. T.eoff - 1 (no triple follows them in this mode).
+    const int psd0 = PSD ? T.soff[0] : 0, msq = PSD ? T.maxs * T.maxs : 0;
+    double *psdU = nullptr, *psdEv = nullptr, *lamp = nullptr, *psdScr = nullptr, *psdXW = nullptr;
+    if constexpr (PSD) {
+        ip += (ip - (int *)sm) & 1;
+        psdU = (double *)ip;
+        psdEv = psdU + T.ns * msq;
+        lamp = psdEv + T.ns * T.maxs;
+        psdScr = lamp + (T.eoff - psd0);
+        psdXW = psdScr + 2 * msq + 2 * T.maxs + 8;
+    }
     // QP: the instance's P row through the template's dense entry map (-1: structural zero; a one-triangle entry stands for both matrix entries)
     auto load_P = [&]() {
         if constexpr (QP) {
@@ -223,6 +249,18 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         if (rst0 & (2 | 4 | 16)) return;
     }
+    // PSD: smat(v_c) = U Lambda U^T of every block by the workgroup's Jacobi sweeps (U -> psdU, vectors in the columns; Lambda -> psdEv).  ONE decomposition gives the
+    // eigenvalues B of D Pi in the classification pass and, REF, y-hat of the block.  All threads; ends behind a barrier.
+    auto psd_decompose = [&](const double *vs) {
+        if constexpr (PSD) {
+            for (int c = 0; c < T.ns; c++) {
+                const int k = T.sord[c];
+                psd_jacobi<NTHR>(vs + T.soff[c], k, psdScr, psdU + c * msq, psdScr + 2 * msq, red);
+                for (int i = tid; i < k; i += NTHR) psdEv[c * T.maxs + i] = psdScr[i * k + i];
+                __syncthreads();
+            }
+        }
+    };
     // REF: y-hat = the projection of v onto the dual cone (zero -> free, nonnegative, second-order) by ns_soc_kind, the decision of the classification pass below
     // (16 lanes per cone); s-hat = y-hat - v
     auto project_dual = [&](const double *vs, double *yh) {
@@ -250,6 +288,19 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 double w[3] = {vs[r0], vs[r0 + 1], vs[r0 + 2]};
                 if (c < T.nep) { double rs = 0.0; exp_project_dual(w, &rs); } else { double rs = -1.0; pow_project_dual_of_entry(w, T.pw[c - T.nep], &rs); }
                 yh[r0] = w[0]; yh[r0 + 1] = w[1]; yh[r0 + 2] = w[2];
+            }
+        }
+        if constexpr (PSD) {          // y-hat_c = svec(U max(Lambda, 0) U^T) from the decomposition the classification pass reads its B from (psdU, psdEv): one decision
+            psd_decompose(vs);
+            for (int c = 0; c < T.ns; c++) {
+                const int k = T.sord[c], r0 = T.soff[c];
+                const double *Um = psdU + c * msq, *ev = psdEv + c * T.maxs;
+                for (int pos = tid; pos < k * (k + 1) / 2; pos += NTHR) {
+                    int b = 0, rem = pos; while (rem >= k - b) { rem -= k - b; b++; }
+                    const int a = b + rem;
+                    double acc = 0; for (int e = 0; e < k; e++) acc = fma(Um[a * k + e] * fmax(ev[e], 0.0), Um[b * k + e], acc);
+                    yh[r0 + pos] = (a == b) ? acc : acc * M_SQRT2;
+                }
             }
         }
         }
@@ -485,6 +536,59 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             for (int k = 0; k < 9; k++) Wt[9 * c + k] = Wl[k];
         }
     }
+    if constexpr (PSD) {
+        // PSD blocks (as k_backward_rt<PSD>): in the orthonormal basis E_ab = svec(sym(u_a u_b^T)) D Pi(v_c) is diagonal with eigenvalue B_ab -- 1 when both
+        // eigenvalues of smat(v_c) are positive, 0 when both are non-positive, l+ / (l+ - l-) otherwise (k_backward_rt's comparisons, no snap: both kernels decide
+        // alike).  The block's rows of A are ROTATED into that basis in place, a~ = svec(U^T smat(a) U) per column, and gamma = Q^T g_y with them as column n (dv);
+        // afterwards a rotated row is an ordinary equality (B = 1), a dropped row (B = 0) or ONE weighted row of the list (theta = B / (1 - B), theta gamma a~ in f:
+        // tvec), exactly a triple's rows.  One column per wave at a time, on the wave's (X, W) pair.  REF: the decomposition is the prologue's (project_dual).
+        if constexpr (!REF) psd_decompose(vv);
+        for (int c = 0; c < T.ns; c++) {
+            const int k = T.sord[c], r0 = T.soff[c], d = k * (k + 1) / 2;
+            const double *Um = psdU + c * msq, *ev = psdEv + c * T.maxs;
+            double *X = psdXW + wave * 2 * msq, *Wm = X + msq;
+            for (int g0 = 0; g0 <= n; g0 += NWB) {
+                const int col = g0 + wave;
+                if (col <= n) {
+                    for (int idx = lane; idx < k * k; idx += 64) {
+                        const int i = idx / k, j = idx - i * k, a = i >= j ? i : j, b = i >= j ? j : i;
+                        const int pos = b * k - (b * (b - 1)) / 2 + (a - b);
+                        const double v = (col < n) ? A[(r0 + pos) * lda + col] : dv[r0 + pos];
+                        X[idx] = (a == b) ? v : v * M_SQRT1_2;
+                    }
+                }
+                __syncthreads();
+                if (col <= n) {
+                    for (int idx = lane; idx < k * k; idx += 64) {       // W = X U
+                        const int i = idx / k, j = idx - i * k;
+                        double acc = 0; for (int a = 0; a < k; a++) acc = fma(X[i * k + a], Um[a * k + j], acc);
+                        Wm[idx] = acc;
+                    }
+                }
+                __syncthreads();
+                if (col <= n) {
+                    for (int pos = lane; pos < d; pos += 64) {           // U^T W, packed back as svec
+                        int b = 0, rem = pos; while (rem >= k - b) { rem -= k - b; b++; }
+                        const int a = b + rem;
+                        double acc = 0; for (int i = 0; i < k; i++) acc = fma(Um[i * k + a], Wm[i * k + b], acc);
+                        const double t = (a == b) ? acc : acc * M_SQRT2;
+                        if (col < n) A[(r0 + pos) * lda + col] = t;
+                        else {
+                            const double la = ev[a], lb = ev[b];
+                            const double Bv = (la > 0 && lb > 0) ? 1.0 : ((la <= 0 && lb <= 0) ? 0.0 : fmax(la, lb) / (fmax(la, lb) - fmin(la, lb)));
+                            const bool mix = Bv != 1.0 && Bv != 0.0;
+                            // a weighted row that is all but an equality: the triples' rule and constant (NS_TRI_STIFF), carried over -- the law behind it is a property
+                            // of the sweep, not of the cone, but it was not measured on PSD rows.  The forward derivative flags the instance, the refinement takes it.
+                            if constexpr (!REF) { if (mix && 1 - Bv < NS_TRI_STIFF) atomicOr(&misc[2], 4); }
+                            lamp[r0 - psd0 + pos] = Bv; dv[r0 + pos] = t; tvec[r0 + pos] = mix ? Bv / (1 - Bv) * t : 0.0;
+                            rkind[r0 + pos] = (Bv == 1.0) ? RK_EQ : (Bv == 0.0 ? RK_FREE : RK_MIX);
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
     __syncthreads();
     if constexpr (TRI) {          // A_c <- W^T A_c in place (read again behind the barriers of the numbering below)
         for (int idx = tid; idx < ntri * n; idx += NTHR) {
@@ -549,6 +653,23 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
             __syncthreads();
         }
+        if constexpr (PSD) {
+            // the weighted rows of the PSD blocks follow the boundary cones' in the list in row order, one lane per rotated row: entry, source row and weight theta (the
+            // rotated row is in place already); eqrow of such a row keeps its list entry for the epilogue
+            const int kw0 = misc[3];
+            __syncthreads();
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) {
+                int kw = kw0;
+                for (int r = psd0; r < i; r++) kw += rkind[r] == RK_MIX ? 1 : 0;
+                if (rkind[i] == RK_MIX) {
+                    const double lam = lamp[i - psd0];
+                    wrow[kw] = (int)(A - sm) + i * lda; wsrc[kw] = i; wgt[kw] = lam / (1 - lam); eqrow[i] = kw;
+                    kw++;
+                }
+                if (i == T.eoff - 1) misc[3] = kw;
+            }
+            __syncthreads();
+        }
     }
     const int neq = misc[0], KW = misc[3], KW4 = (KW + 4) & ~3;          // (at least one pad entry: entry KW stands for f in the null-space transform)
     if (neq > n) {   // more active rows than variables: rank deficient by counting (flagged, zero gradient / zero tangents; the LSQR launch behind this kernel serves it)
@@ -603,6 +724,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             }
             if constexpr (TRI) {          // + theta gamma a~ of the triples' weighted rows
                 for (int i = T.eoff + part; i < m; i += 4) if (rkind[i] == RK_MIX) acc = fma(A[i * lda + j], tvec[i], acc);
+            }
+            if constexpr (PSD) {          // + theta gamma a~ of the PSD blocks' weighted rows
+                for (int i = psd0 + part; i < T.eoff; i += 4) if (rkind[i] == RK_MIX) acc = fma(A[i * lda + j], tvec[i], acc);
             }
         }
         acc = group_reduce<4, false>(acc);
@@ -1535,6 +1659,43 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 }
             }
         }
+        if constexpr (PSD) {
+            // a block's weighted row: eta = (a~ . d_x - gamma) / (1 - B) with a~ . d_x from the list (tvec), so dy~ = B eta, ds~ = gamma - a~ . d_x; its equality and
+            // dropped rows went with the others above.  Then back per block, both vectors at once on the pairs of waves 0 and 1:  dy_c = Q dy~,  ds_c = Q ds~  with
+            // Q r = svec(U smat(r) U^T)  (k_backward_rt's rotation back).
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) {
+                if (rkind[i] != RK_MIX) continue;
+                const double lam = lamp[i - psd0], qd = tvec[eqrow[i]] - dv[i];
+                vv[i] = lam * qd / (1 - lam); dv[i] = -qd;
+            }
+            __syncthreads();
+            for (int c = 0; c < T.ns; c++) {
+                const int k = T.sord[c], r0 = T.soff[c], d = k * (k + 1) / 2;
+                const double *Um = psdU + c * msq;
+                for (int idx = tid; idx < 2 * k * k; idx += NTHR) {
+                    const int w = idx / (k * k), e = idx - w * k * k, i = e / k, j = e - i * k, a = i >= j ? i : j, b = i >= j ? j : i;
+                    const double v = (w ? dv : vv)[r0 + b * k - (b * (b - 1)) / 2 + (a - b)];
+                    psdXW[w * 2 * msq + e] = (a == b) ? v : v * M_SQRT1_2;
+                }
+                __syncthreads();
+                for (int idx = tid; idx < 2 * k * k; idx += NTHR) {          // W = U X
+                    const int w = idx / (k * k), e = idx - w * k * k, i = e / k, j = e - i * k;
+                    const double *X = psdXW + w * 2 * msq;
+                    double acc = 0; for (int a = 0; a < k; a++) acc = fma(Um[i * k + a], X[a * k + j], acc);
+                    psdXW[w * 2 * msq + msq + e] = acc;
+                }
+                __syncthreads();
+                for (int idx = tid; idx < 2 * d; idx += NTHR) {              // W U^T, packed back as svec
+                    const int w = idx / d, pos = idx - w * d;
+                    const double *Wm = psdXW + w * 2 * msq + msq;
+                    int b = 0, rem = pos; while (rem >= k - b) { rem -= k - b; b++; }
+                    const int a = b + rem;
+                    double acc = 0; for (int e = 0; e < k; e++) acc = fma(Wm[a * k + e], Um[b * k + e], acc);
+                    (w ? dv : vv)[r0 + pos] = (a == b) ? acc : acc * M_SQRT2;
+                }
+                __syncthreads();
+            }
+        }
         __syncthreads();
         if constexpr (REF) {
             // ---- REF epilogue: x+ = x + dx -> rx,  v+ = v + (dy - ds) -> vv,  y+ = Pi(v+) -> tvec,  s+ = y+ - v+.  The elimination overwrote A: the instance's
@@ -1543,6 +1704,42 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             const bool flagged = (misc[2] & 4) != 0;
             bool ok = false;
             double rho1 = rho_cur;
+            if constexpr (PSD) {
+            // PSD: the same test on a SHORTENED step when the full one fails it.  The projection onto a PSD block changes its active set (the signs of the eigenvalues)
+            // continuously along the step, and from a loose point the full Newton step can cross such a change and RAISE rho, where the step of a plain cone rarely
+            // does (measured: one instance of 48 at eps 1e-4, the dense numpy step raising rho 8.6e-5 -> 2.2e-4 alike).  The step (dx in rx, dv = dy - ds in dv) is kept
+            // and tried at alpha = 1, 1/2, 1/4, 1/8: x+ = x + alpha dx -> fvec, v+ = v + alpha dv -> vv, y+ = Pi(v+) -> tvec; the first trial that passes ce_refine's
+            // acceptance rule (rho below rho of the point that came in, as evaluated now and as recorded) is written, else nothing is.  alpha = 1 first: where the
+            // full step passes, this is ce_refine's step bit for bit in its arithmetic order (fma(1, d, x) = x + d).  A is scattered once for all trials.
+            if (!flagged) {          // (uniform)
+                const double *vals = Avals + (size_t)inst * T.nnz_aug;
+                for (int i = tid; i < m; i += NTHR) dv[i] = vv[i] - dv[i];
+                for (int i = tid; i < m * lda; i += NTHR) A[i] = 0.0;
+                __syncthreads();
+                for (int k0 = tid; k0 < T.nnzA; k0 += 4 * NTHR) {
+                    double v0[4]; int r0[4], c0[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) { const int k = k0 + u * NTHR, kc = k < T.nnzA ? k : 0; v0[u] = vals[kc]; r0[u] = T.rowidx[kc]; c0[u] = k < T.nnzA ? T.colidx[kc] : -1; }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (c0[u] >= 0) A[r0[u] * lda + c0[u]] = -v0[u];
+                }
+                double alpha = 1.0;
+                for (int trial = 0; trial < 4 && !ok; trial++, alpha *= 0.5) {          // (uniform: rho1 is the same LDS reduction in every thread)
+                    __syncthreads();
+                    for (int j = tid; j < n; j += NTHR) fvec[j] = fma(alpha, rx[j], W.x[(size_t)inst * n + j]);
+                    for (int i = tid; i < m; i += NTHR) vv[i] = fma(alpha, dv[i], W.y[(size_t)inst * m + i] - W.s[(size_t)inst * m + i]);
+                    __syncthreads();
+                    project_dual(vv, tvec);
+                    __syncthreads();
+                    rho1 = kkt_residual(fvec, tvec, vv, false);
+                    ok = rho1 < fmin(rho0, rho_cur);
+                }
+                if (ok) {
+                    for (int j = tid; j < n; j += NTHR) W.x[(size_t)inst * n + j] = fvec[j];
+                    for (int i = tid; i < m; i += NTHR) { const double yi = tvec[i]; W.y[(size_t)inst * m + i] = yi; W.s[(size_t)inst * m + i] = yi - vv[i]; }
+                }
+            }
+            } else
             if (!flagged) {          // (uniform)
                 const double *vals = Avals + (size_t)inst * T.nnz_aug;
                 for (int j = tid; j < n; j += NTHR) rx[j] += W.x[(size_t)inst * n + j];

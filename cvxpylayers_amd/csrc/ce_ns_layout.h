@@ -58,14 +58,23 @@ struct NsLayout {
     // ---- exponential / power triples only (TRI mode; len 0 otherwise), behind the ints rounded to 8 bytes
     NsSeg Wt;        // doubles: per triple the eigenvectors W (row-major 3 x 3, columns) of D Pi_K*(v): the triple's rows of A are rotated by W^T in place
     NsSeg lamt;      // doubles: per rotated triple row its eigenvalue lambda after the snap (1: equality, 0: dropped, else a weighted row)
+    // ---- PSD blocks only (PSD mode; len 0 otherwise), behind the ints rounded to 8 bytes.  NONE of them aliases the union region or any other segment: U, Lambda
+    //      and B live from the decomposition to the rotation back in the epilogue, across every phase of the union's members; the two scratch segments are used in
+    //      the classification pass, in the epilogue and in the refinement's projections, and cost 5.2 KB at order 8 with four waves -- kept apart, no phase proof needed
+    NsSeg psdU;      // doubles: per block the eigenvectors U of smat(v_c) (row-major, pitch maxs x maxs per block, order k x k inside, vectors in the columns)
+    NsSeg psdEv;     // doubles: per block its eigenvalues Lambda (pitch maxs)
+    NsSeg lamp;      // doubles: per rotated PSD row (a, b) the eigenvalue B_ab of D Pi (1: equality, 0: dropped, else a weighted row)
+    NsSeg psdScr;    // doubles: the Jacobi scratch, 2 maxs^2 + 2 maxs + 8 (ce_psd_jacobi.h: S, a spare matrix, the rotations of a round)
+    NsSeg psdXW;     // doubles: the rotation's (X, W) pair of maxs x maxs matrices per wave
     // ---- ints: the footprint has always counted the two alignment doubles (behind A, in front of U) whether or not the carve takes them, and the launch plan
     //      is decided on the footprint: the ones not taken stay reserved here, at the end (two ints each), and nothing uses them
     NsSeg slack;
     size_t bytes;    // the footprint: the end of the last segment
 };
 
-// the modes of the layout: the plain one, the one with the dense P behind the ints (qp), and the one with the triples' segments there (ntri > 0 triples; never with qp)
-__host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE, int NTHR, bool qp, int ntri = 0) {
+// the modes of the layout: the plain one, the one with the dense P behind the ints (qp), the one with the triples' segments there (ntri > 0 triples; never with qp),
+// and the one with the PSD blocks' segments there (ns > 0 blocks of order <= maxs that own psdrows rows together; never with qp or triples)
+__host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE, int NTHR, bool qp, int ntri = 0, int ns = 0, int maxs = 0, int psdrows = 0) {
     const int nqs = nq > 0 ? nq : 1, npad = n + (n & 1), kw = bwd_ns_kwmax(m), nwb = NTHR / 64;
     NsLayout L{};
     int p = 0, taken = 0;          // doubles
@@ -119,6 +128,17 @@ __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE
         L.lamt = {p, 3 * ntri}; p += 3 * ntri;
         ip = 2 * p;
     }
+    L.psdU = {0, 0}; L.psdEv = {0, 0}; L.lamp = {0, 0}; L.psdScr = {0, 0}; L.psdXW = {0, 0};
+    if (ns > 0) {
+        ip += ip & 1;
+        p = ip / 2;
+        L.psdU = {p, ns * maxs * maxs}; p += ns * maxs * maxs;
+        L.psdEv = {p, ns * maxs}; p += ns * maxs;
+        L.lamp = {p, psdrows}; p += psdrows;
+        L.psdScr = {p, 2 * maxs * maxs + 2 * maxs + 8}; p += 2 * maxs * maxs + 2 * maxs + 8;
+        L.psdXW = {p, 2 * nwb * maxs * maxs}; p += 2 * nwb * maxs * maxs;
+        ip = 2 * p;
+    }
     L.slack = {ip, 2 * (2 - taken)}; ip += 2 * (2 - taken);
     L.bytes = (size_t)ip * 4;
     return L;
@@ -127,3 +147,4 @@ __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE
 __host__ __device__ constexpr size_t bwd_ns_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, true).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_tri_lds_bytes_of(int n, int m, int nq, int ntri, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, ntri).bytes; }
+__host__ __device__ constexpr size_t bwd_ns_psd_lds_bytes_of(int n, int m, int nq, int ns, int maxs, int psdrows, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, 0, ns, maxs, psdrows).bytes; }

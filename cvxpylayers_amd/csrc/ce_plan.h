@@ -48,6 +48,7 @@ struct CePlan {
     int ns_variant = -1; size_t ns_lds = 0;        // row of CE_NS_VARIANTS: search-free null-space adjoint (-1: not applicable)
     int qp_ns_variant = -1; size_t qp_ns_lds = 0;  // row of CE_NS_VARIANTS with the QP footprint: forward derivative and refinement of a qp_native template (-1: none)
     int tri_ns_variant = -1; size_t tri_ns_lds = 0;      // row of CE_NS_VARIANTS with the TRI footprint: forward derivative and refinement of a template with exponential / power triples (-1: none)
+    int psd_ns_variant = -1; size_t psd_ns_lds = 0;      // row of CE_NS_VARIANTS with the PSD footprint: the opt-in forward derivative and refinement of a template with PSD blocks (ce_jvp_psd, ce_refine_psd; -1: none)
 };
 
 #ifdef CE_TIMING
@@ -102,9 +103,10 @@ static bool resolve_lds_fits(const DevT &T, int psd_first) {
 }
 // k_backward_ns: the first row of CE_NS_VARIANTS whose tiles hold the reduced system (4 ceil(n / 4) + 1 columns) and whose layout (with P: the dense P on top) fits LDS;
 // -1: none.  *lds: its footprint
-static int ns_first_fit(const DevT &T, bool qp, size_t *lds, int ntri = 0) {      // (ntri > 0: the layout's TRI mode, the triples' W and lambda on top)
-    for (int v = 0; v < (int)std::size(NS_ROWS); v++) {
-        const size_t by = ntri > 0 ? bwd_ns_tri_lds_bytes_of(T.n, T.m, T.nq, ntri, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
+static int ns_first_fit(const DevT &T, bool qp, size_t *lds, int ntri = 0, int psdrows = 0) {      // (ntri > 0: the layout's TRI mode, the triples' W and lambda on top;
+    for (int v = 0; v < (int)std::size(NS_ROWS); v++) {                                               //  psdrows > 0: its PSD mode, the rows the T.ns blocks own together)
+        const size_t by = psdrows > 0 ? bwd_ns_psd_lds_bytes_of(T.n, T.m, T.nq, T.ns, T.maxs, psdrows, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
+                        : ntri > 0 ? bwd_ns_tri_lds_bytes_of(T.n, T.m, T.nq, ntri, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
                         : qp ? bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR) : bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
         if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { *lds = by; return v; }
     }
@@ -260,6 +262,14 @@ static int plan_engine(const ce_template *tpl, const DevT &T, int nnz_p, const P
     // front of the triples).  ns_variant stays -1: the adjoint of such a template keeps k_backward_rt.
     if (T.ns == 0 && T.nep + T.np > 0 && nnz_p == 0 && !E.ns_off && !E.force_generic && resolve_lds_fits(T, T.eoff))
         P.tri_ns_variant = ns_first_fit(T, false, &P.tri_ns_lds, T.nep + T.np);
+    // And with PSD blocks beside the plain cones (k_backward_ns<..., PSD>): the forward derivative and the refinement behind entry points of their own (ce_jvp_psd,
+    // ce_refine_psd), linear objective, no triple, planned on the PSD footprint -- when the LSQR vectors of the re-solve fit LDS too.  psd_first: the blocks' first
+    // row, qoff[nq] (plan_sizes: the PSD rows end at T.eoff, and nothing follows them here).  Every other field keeps its value: ce_jvp / ce_refine still refuse.
+    if (T.ns > 0 && T.nep + T.np == 0 && nnz_p == 0 && !E.ns_off && !E.force_generic) {
+        int psdrows = 0;
+        for (int c = 0; c < tpl->ns; c++) psdrows += tpl->s[c] * (tpl->s[c] + 1) / 2;
+        if (resolve_lds_fits(T, T.eoff - psdrows)) P.psd_ns_variant = ns_first_fit(T, false, &P.psd_ns_lds, 0, psdrows);
+    }
     return CE_OK;
 }
 

@@ -94,6 +94,10 @@ struct NsVjpQpMany : NsMany { NsQp Q; const int *prow, *pcol; int p_tri; double 
 // k_backward_ns<..., FWD, REF or not, QP = false, TRI = true>: the same arguments (the triples are described by DevT); types of their own select the launcher
 struct NsJvpTri : NsJvp {};
 struct NsRefineTri : NsRefine {};
+// k_backward_ns<..., FWD, REF or not, ..., PSD = true>: the same arguments again (the PSD blocks are described by DevT: ns, maxs, soff, sord); types of their own
+// select the launcher (cone_engine.hip ce_jvp_psd, ce_refine_psd)
+struct NsJvpPsd : NsJvp {};
+struct NsRefinePsd : NsRefine {};
 // k_backward_ns<..., FWD = false, ..., TRI = true, MANY = true>: K cotangents of the adjoint with triples on one factorisation (cone_engine.hip ce_vjp_tri_many).
 // NsMany's fields and strides; a type of its own selects the launcher
 struct NsVjpTriMany : NsMany {};
@@ -254,6 +258,8 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpQpMany &w);          // (ce_tu_ns_vjp_qp_many.hip: the adjoint with P for K cotangents)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpTriMany &w);         // (ce_tu_ns_vjp_tri_many.hip: the adjoint with triples for K cotangents)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyTri &w);         // (ce_tu_ns_jvp_tri_many.hip: the forward derivative with triples for K tangents -- the type's name: see its declaration)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpPsd &w);             // (ce_tu_ns_psd.hip: the forward derivative and the refinement
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefinePsd &w);          //  with PSD blocks)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -294,6 +300,7 @@ hipError_t ce_setattr_ns_jvp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_tri_many(int bytes);
 hipError_t ce_setattr_ns_jvp_tri_many(int bytes);
+hipError_t ce_setattr_ns_psd(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

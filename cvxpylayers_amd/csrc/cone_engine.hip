@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -310,6 +310,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
 int ce_adjoint_ns_variant(ce_handle h) { return h ? h->plan.ns_variant : -1; }
 int ce_qp_ns_variant(ce_handle h) { return h ? h->plan.qp_ns_variant : -1; }
 int ce_tri_ns_variant(ce_handle h) { return h ? h->plan.tri_ns_variant : -1; }
+int ce_psd_ns_variant(ce_handle h) { return h ? h->plan.psd_ns_variant : -1; }
+long ce_psd_ns_lds(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? (long)h->plan.psd_ns_lds : 0; }
 // the many-cotangent mode rebuilds every cotangent's vectors in the buffers of the plain adjoint: its row and footprint are ns_variant's, and like the kernel
 // behind ce_vjp it only runs in front of the LSQR re-solve
 int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
@@ -1149,20 +1151,23 @@ static int qp_ns_check(ce_handle h, const char *who) {
 // re-solves the instances it listed as rank deficient -- the same re-solve list.  With P_vals (ce_jvp_qp: k_backward_ns<..., FWD, QP>) one launch and no re-solve list: no LSQR has a P term.
 static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
-                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false) {
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_jvp_qp" : "ce_jvp";
+    const std::string who = qp ? "ce_jvp_qp" : (psd ? "ce_jvp_psd" : "ce_jvp");
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     int rc = CE_OK;
     if (qp) { rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc; }
-    else {
+    else if (psd) {      // (the opt-in entry point of PSD templates: ce_jvp itself keeps refusing them)
+        if (P.psd_ns_variant < 0) { g_err = "ce_jvp_psd: this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    } else {
         if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
         if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
         if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
     }
-    const bool tri = !qp && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, TRI> on its own footprint, the same re-solve list behind it
-    const int variant = qp ? P.qp_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant); const size_t lds = qp ? P.qp_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds);
+    const bool tri = !qp && !psd && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, TRI> on its own footprint, the same re-solve list behind it
+    const int variant = qp ? P.qp_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant));
+    const size_t lds = qp ? P.qp_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds));
     if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = who + ": A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1173,6 +1178,7 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
     const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
+                  : psd ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsd{W})
                   : tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
     if (lrc) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
     if (!qp) {
@@ -1190,6 +1196,12 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
            double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+int ce_jvp_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+               const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+               double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream, true);
 }
 int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
               const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
@@ -1318,18 +1330,21 @@ int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
 static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
-                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false) {
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_refine_qp" : "ce_refine";
+    const std::string who = qp ? "ce_refine_qp" : (psd ? "ce_refine_psd" : "ce_refine");
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (qp) { const int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc; }
-    else {
+    else if (psd) {      // (the opt-in entry point of PSD templates: ce_refine itself keeps refusing them)
+        if (P.psd_ns_variant < 0) { g_err = "ce_refine_psd: this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
+    } else {
         if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
         if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
     }
-    const bool tri = !qp && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, REF, TRI>
-    const int variant = qp ? P.qp_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant); const size_t lds = qp ? P.qp_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds);
+    const bool tri = !qp && !psd && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, REF, TRI>
+    const int variant = qp ? P.qp_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant));
+    const size_t lds = qp ? P.qp_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds));
     if (B > 1 && sA_b != T.nnz_aug) { g_err = who + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1339,6 +1354,7 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
         const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
+                      : psd ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsd{W})
                       : tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefineTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
         if (lrc) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
     }
@@ -1349,6 +1365,11 @@ int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
               const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine: null argument or negative step count"; return CE_E_BADARG; }
     return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream);
+}
+int ce_refine_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+                  const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_psd: null argument or negative step count"; return CE_E_BADARG; }
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream, true);
 }
 int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
                  const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {

@@ -44,7 +44,7 @@ class ConeEngine:
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
-        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
+        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_psd" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -85,6 +85,7 @@ class ConeEngine:
         _lib.check(rc, "ce_create")
         self._h = h
         self.qp_native = bool(self.nnz_p) and bool(L.ce_qp_native(h))     # P runs inside the kernels (else: epigraph form upstream)
+        self.psd_ns_variant = int(L.ce_psd_ns_variant(h))                 # >= 0: ce_jvp_psd / ce_refine_psd serve this template (solver_args psd_elimination)
         a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()          # fixed by ce_create (plan_engine)
         L.ce_get_launch_info(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         self._launch_info = dict(fwd_lds_bytes=a.value, bwd_lds_bytes=b.value, fwd_mode=c.value, bwd_mode=d.value)
@@ -464,7 +465,7 @@ class ConeEngine:
         return out
 
     def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "lsqr",
-            P_bm=None, tP_bm=None):
+            P_bm=None, tP_bm=None, psd_ns: bool = False):
         """Forward-mode derivative of the solution map (diffcp's `derivative`): tangents tA_bm (B, nnz_aug) of the value rows and tq (n+1, B) of q_eval, either may be
         None (zero).  Returns dx (B, n), dy (B, m), ds (B, m), status (B,) -- 1: LSQR hit its iteration limit -- and sets last_lsqr_iters.
         One kernel per call, ce_jvp_lsqr, or ce_jvp_shared_a when `path` is "const_a" (only the b entries of tA_bm are read there: a shared A has no tangent).
@@ -473,7 +474,9 @@ class ConeEngine:
         (status 4 | 8 and iterations > 0 there, status 0 and 0 iterations elsewhere).  Where the library has no elimination for the template, and on the const_a
         path, the LSQR call runs instead; last_jvp_kernel names the entry point that ran.
         P_bm (B, nnz_p): the quadratic objective of a qp_native engine, with its tangent tP_bm (or None: zero) -- method="direct" only: ce_jvp_qp, the same elimination
-        with P inside and NO LSQR behind it (a flagged instance keeps the elimination's answer, status 4, 0 iterations); NotImplementedError under method="lsqr"."""
+        with P inside and NO LSQR behind it (a flagged instance keeps the elimination's answer, status 4, 0 iterations); NotImplementedError under method="lsqr".
+        psd_ns=True (with method="direct"): ce_jvp_psd in the place of ce_jvp -- the elimination with PSD blocks (psd_ns_plan()["psd_ns_variant"] >= 0), which
+        ce_jvp refuses; the same fall to the LSQR call where the library has none for the template.  Without it a PSD template runs the LSQR call, as ever."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
@@ -504,9 +507,10 @@ class ConeEngine:
                       float(atol), float(btol), float(conlim), int(lim), self._stream())
         rc = -2
         if method == "direct" and not shared:
-            rc = call(_lib.lib().ce_jvp, A_c if A_c.stride(0) == self.nnz_aug else A_c.contiguous())
+            direct, dname = (_lib.lib().ce_jvp_psd, "ce_jvp_psd") if psd_ns else (_lib.lib().ce_jvp, "ce_jvp")
+            rc = call(direct, A_c if A_c.stride(0) == self.nnz_aug else A_c.contiguous())
             if rc != -2:          # (CE_E_UNSUPPORTED: no elimination for this template -- the LSQR call below serves it)
-                name = "ce_jvp"
+                name = dname
         if rc == -2:
             rc = call(fn, A_c)
         if rc in (-2, -3):
@@ -621,13 +625,14 @@ class ConeEngine:
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
-    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None, P_bm=None):
+    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None, P_bm=None, psd_ns: bool = False):
         """`steps` safeguarded Newton steps on the KKT residual of (x, y, s) (include/cone_engine.h ce_refine): A_bm (B, nnz_aug), q_eval (n+1, B), x (B, n), y, s
         (B, m); status (B,) int32 or None: instances with a negative forward status are skipped.  Returns x, y, s, info -- contiguous fp64 tensors on this
         engine's device are refined IN PLACE and handed back, others are copied first.  info: "status" (bits 1 a step kept, 2 a step rejected, 4 flagged by the
         elimination, 16 skipped), "steps" (kept per instance), "resid_before" / "resid_after" (rho of the point that came in and of the one returned), "path"
         "ns" -- or "none", with the other entries None and the point untouched, where the library has no elimination for the template.  No host synchronisation.
-        P_bm (B, nnz_p): the quadratic objective of a qp_native engine (ce_refine_qp: F_x = P x + A^T y^ + c)."""
+        P_bm (B, nnz_p): the quadratic objective of a qp_native engine (ce_refine_qp: F_x = P x + A^T y^ + c).
+        psd_ns=True: ce_refine_psd in the place of ce_refine -- the elimination with PSD blocks, which ce_refine refuses (path "none" without the flag)."""
         B = A_bm.shape[0]
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -644,6 +649,8 @@ class ConeEngine:
         if P_bm is not None:
             P_c = P_bm.detach().to(**f64).contiguous()
             rc, name = _lib.lib().ce_refine_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp"
+        elif psd_ns:
+            rc, name = _lib.lib().ce_refine_psd(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine_psd"
         else:
             rc, name = _lib.lib().ce_refine(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine"
         if rc == -2:
@@ -772,3 +779,9 @@ class ConeEngine:
         buf = (C.c_int * cnt)()
         L.ce_get_plan(self._h, buf, cnt)
         return dict(zip(self.PLAN_FIELDS, list(buf)))
+
+    def psd_ns_plan(self):
+        """The plan of the opt-in search-free elimination with PSD blocks (ce_jvp_psd / ce_refine_psd), which ce_get_plan and PLAN_FIELDS do not carry:
+        "psd_ns_variant" (row of CE_NS_VARIANTS, -1: the template is not served) and "psd_ns_lds" (its LDS footprint in bytes, 0: none)."""
+        L = _lib.lib()
+        return {"psd_ns_variant": int(L.ce_psd_ns_variant(self._h)), "psd_ns_lds": int(L.ce_psd_ns_lds(self._h))}

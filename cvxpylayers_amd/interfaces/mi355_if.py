@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, psd_elimination, psd_elimination_active, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -155,6 +155,7 @@ class _Saved(NamedTuple):
     qp_adjoint: str = "pivoting"            # qp_adjoint() of this call: "search_free" sends adjoint_many of a native QP node to ce_vjp_qp_many (backward() ignores it)
     tri_adjoint: str = "pivoting"           # tri_adjoint() of this call: "search_free" sends adjoint_many of a node with exponential / power cones to ce_vjp_tri_many (backward() ignores it)
     tri_tangents: str = "loop"              # tri_tangents() of this call: "many" sends tangent_many of a node with exponential / power cones to ce_jvp_tri_many (one-tangent forward-mode AD ignores it)
+    psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -189,6 +190,7 @@ class _ConeLayer(torch.autograd.Function):
         tri_adj = tri_adjoint(merged_args)        # (likewise)
         tri_tan = tri_tangents(merged_args)       # (likewise; read by tangent_many alone)
         n_newton = newton_first(merged_args)
+        psd_ns = psd_elimination_active(psd_elimination(merged_args), eng.psd_ns_variant, bool(len(eng.cone_dict.get("s", []) or [])))
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
         with torch.cuda.device(dev):
@@ -205,7 +207,7 @@ class _ConeLayer(torch.autograd.Function):
             # (newton_first.py: one 4-byte host read, also under raise_on_error=False); everything below sees the final full-batch result
             nf_info = None
             if n_newton > 0 and warm is not None and batch_size > 0:
-                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm)
+                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns)
                 if nf_info["path"] == "none":
                     _warn_once("newton_first_none", "MI355 solver: solver_args newton_first needs the search-free elimination, which this template or path does not have "
                                                     "(PSD cones, n > 108, a shared A); the ordinary warm-started solve ran (info['newton_first']['path'] == 'none')")
@@ -220,7 +222,7 @@ class _ConeLayer(torch.autograd.Function):
             if n_refine > 0:
                 refine_info = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
                 if eng.last_path == "per_instance" and status.numel():
-                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm)
+                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm, psd_ns=psd_ns)
                 if refine_info["path"] == "none" and status.numel():
                     _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD "
                                               "cones, n > 108, a shared A); the solver's point is returned "
@@ -251,7 +253,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -328,12 +330,12 @@ class _ConeLayer(torch.autograd.Function):
                     tP_bm = (tP.unsqueeze(1) if originally_unbatched else tP).detach().to(device=eng.device, dtype=torch.float64).t().contiguous()
                 dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, method="direct", P_bm=saved.P_bm, tP_bm=tP_bm)
             else:
-                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode)
+                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode, psd_ns=saved.psd_ns)
             if failed is not None:
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp") else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod

@@ -36,9 +36,9 @@ def _read_int(eng: ConeEngine, dev_int: torch.Tensor) -> int:
     return int(slot[0])
 
 
-def newton_first_solve(eng: ConeEngine, A_bm, q_eval, settings, warm, steps: int, P_bm=None):
+def newton_first_solve(eng: ConeEngine, A_bm, q_eval, settings, warm, steps: int, P_bm=None, psd_ns: bool = False):
     """The forward solve of a warm-started call with newton_first = steps > 0.  A_bm (B, nnz_aug) contiguous, q_eval (n+1, B), warm = (x, y, s), P_bm (B, nnz_p)
-    or None, settings the call's ce_settings.  Returns (x, y, s, iters, status, resid), info -- what ConeEngine.solve returns for the whole batch, and
+    or None, settings the call's ce_settings, psd_ns: the steps run ce_refine_psd (a template with PSD blocks under solver_args psd_elimination).  Returns (x, y, s, iters, status, resid), info -- what ConeEngine.solve returns for the whole batch, and
     info["newton_first"].  Where the feature is not served (a shared A, no elimination for the template) the ordinary warm-started solve runs and info's path is
     "none".  Leaves on the engine what a full-batch per-instance solve() leaves (last_path, last_acceleration, the remembered objective)."""
     B = A_bm.shape[0]
@@ -50,7 +50,7 @@ def newton_first_solve(eng: ConeEngine, A_bm, q_eval, settings, warm, steps: int
     refine_info = {"path": "none"}
     if not const_a:
         x, y, s = (t.detach().to(device=dev, dtype=torch.float64).clone().contiguous() for t in warm)          # (refine works in place: never on the caller's tensors)
-        x, y, s, refine_info = eng.refine(A_bm, q_eval, x, y, s, steps, status=None, P_bm=P_bm)
+        x, y, s, refine_info = eng.refine(A_bm, q_eval, x, y, s, steps, status=None, P_bm=P_bm, psd_ns=psd_ns)
     if refine_info["path"] != "ns":
         return eng.solve(A_bm, q_eval, settings, warm=warm, P_bm=P_bm, path="const_a" if const_a else "per_instance"), not_served(steps, B)
     # (status, iters, resid: every entry is written below -- by the test for an accepted instance, by the scatter for the others -- so they start uninitialised)

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -92,7 +92,8 @@ def jvp_mode(merged_args: dict) -> str:
     """How the forward-mode derivative (torch.autograd.forward_ad) solves diffcp's M d = -dQ pi on PER-INSTANCE-A templates:
     absent / "lsqr" -> diffcp's LSQR for every instance (ce_jvp_lsqr);
     "direct" -> the search-free elimination the default adjoint runs, and behind it on the device LSQR for exactly the instances it finds rank deficient
-    (ce_jvp; exponential / power triples included).  Templates without that elimination (PSD cones, n > 108) and shared-A templates run LSQR whatever this says;
+    (ce_jvp; exponential / power triples included; PSD blocks under psd_elimination="search_free": ce_jvp_psd).  Templates without that elimination (PSD cones
+    by default, n > 108) and shared-A templates run LSQR whatever this says;
     info["jvp"]["path"] tells which one ran.  A quadratic objective inside the kernels has "direct" alone (ce_jvp_qp: the elimination with P inside, no LSQR
     behind it); the default raises NotImplementedError there."""
     mode = str(merged_args.get("jvp_mode", "lsqr"))
@@ -143,10 +144,36 @@ def tri_tangents(merged_args: dict) -> str:
     return mode
 
 
+def psd_elimination(merged_args: dict) -> str:
+    """Whether a per-instance-A template with PSD blocks uses the search-free elimination (ce_jvp_psd, ce_refine_psd: the blocks' rows rotated into the eigenbasis
+    of D Pi, then the elimination of the plain cones):
+    absent / "off" -> today's routes: forward-mode AD by LSQR whatever jvp_mode says, no refine_steps, no newton_first;
+    "search_free" -> jvp_mode="direct" runs ce_jvp_psd (LSQR behind it for the instances it flags), refine_steps and newton_first are served by ce_refine_psd.
+    Opt-in: the flagging rule for stiff rows is the triples', not measured on PSD rows.  Templates the mode does not serve (no PSD block, triples or a quadratic
+    objective beside them, n > 108) ignore the key; psd_elimination_active says so once where the template has a PSD block."""
+    mode = str(merged_args.get("psd_elimination", "off"))
+    if mode not in ("off", "search_free"):
+        raise ValueError(f"MI355 solver: psd_elimination must be 'off' or 'search_free', got {mode!r}")
+    return mode
+
+
+def psd_elimination_active(mode: str, psd_ns_variant: int, has_psd: bool) -> bool:
+    """True when this call runs the PSD elimination: the key asks for it and the engine serves the template (ConeEngine.psd_ns_variant >= 0).  A template with a
+    PSD block that is not served gets one notice; a template without one is silent (the key is inert there)."""
+    if mode != "search_free":
+        return False
+    if psd_ns_variant >= 0:
+        return True
+    if has_psd:
+        _warn_once("psd_elimination_none", "MI355 solver: solver_args psd_elimination='search_free' is ignored on this template: the search-free elimination does not "
+                                           "serve it (exponential / power cones or a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
+    return False
+
+
 def refine_steps(merged_args: dict) -> int:
     """Newton refinement steps behind the forward solve (ce_refine, ce_refine_qp with a quadratic objective inside the kernels: the search-free elimination on the
     KKT residual, every step safeguarded so that the residual never grows): an integer >= 0, default 0 = none.  Templates without that elimination (PSD
-    cones, n > 108, shared-A paths) keep the solver's point and say so once; info["refine"]["path"] tells which."""
+    cones unless psd_elimination="search_free" asks for ce_refine_psd, n > 108, shared-A paths) keep the solver's point and say so once; info["refine"]["path"] tells which."""
     v = merged_args.get("refine_steps", 0)
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0:
         raise ValueError(f"MI355 solver: refine_steps must be an integer >= 0, got {v!r}")

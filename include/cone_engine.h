@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -377,6 +377,34 @@ int ce_qp_ns_variant(ce_handle h);
  * them, no PSD block, linear objective, n <= 108; planned on the footprint with the triples' eigenvectors and eigenvalues on top, and only when the LSQR vectors
  * of ce_jvp's re-solve fit LDS); -1: none.  ce_adjoint_ns_variant stays -1 for such a template: its adjoint keeps the pivoting kernel. */
 int ce_tri_ns_variant(ce_handle h);
+
+/*
+ * ce_jvp and ce_refine for a template with PSD BLOCKS beside zero / nonnegative / second-order cones (linear objective, no exponential / power triple, n <= 108):
+ * the same search-free elimination with the blocks' code, behind entry points of their own -- ce_jvp and ce_refine keep refusing such a handle, so nothing changes
+ * for a caller that does not ask.  Per block smat(v_c) = U Lambda U^T (the workgroup's Jacobi sweeps); in the basis E_ab = svec(sym(u_a u_b^T)) D Pi(v_c) is diagonal
+ * with eigenvalue B_ab = 1 (both eigenvalues positive), 0 (both non-positive) or l+ / (l+ - l-), the comparisons of ce_vjp's pivoting kernel without a snap.  The
+ * block's rows of A are rotated into that basis and join the equalities (B = 1), drop out (B = 0) or enter the reduced Hessian as one weighted row each
+ * (theta = B / (1 - B)); the answers are rotated back.  ce_refine_psd: y^ of a block is svec(U max(Lambda, 0) U^T) from the same decomposition.
+ * ce_refine_psd keeps ce_refine's acceptance rule and adds a shortened step: when the full Newton step fails the rule (a block's active set can change inside the
+ * step) the same step is tried at 1/2, 1/4 and 1/8 of its length and the first trial that passes is kept; bit 2 is set only when all four fail.
+ * Arguments, outputs, status bits, the re-solve list behind ce_jvp_psd and the safeguard of ce_refine_psd otherwise as ce_jvp / ce_refine.  4 | 8 of ce_jvp_psd has the second
+ * meaning it has with triples: an instance with a weighted PSD row of 1 - B < 1e-5 (a small negative eigenvalue beside a large positive one) is handed to LSQR.
+ * That threshold is the triples' (csrc/ce_backward_ns.h NS_TRI_STIFF), carried over: the law behind it belongs to the sweep, but it was NOT measured on PSD rows.
+ * ce_refine_psd does not apply it.
+ * CE_E_UNSUPPORTED when ce_psd_ns_variant(h) < 0.
+ */
+int ce_jvp_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+               const double *x, const double *y, const double *s,
+               const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+               double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_refine_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                  double *x, double *y, double *s /* in/out */, const int *status /* may be NULL */, int steps,
+                  int *refine_status, int *steps_taken, double *resid, void *stream);
+/* >= 0: the row of CE_NS_VARIANTS that serves ce_jvp_psd / ce_refine_psd (at least one PSD block, no triple, linear objective, n <= 108; planned on the footprint
+ * with the blocks' U, Lambda, B and scratch on top, and only when the LSQR vectors of the re-solve fit LDS); -1: none, or h == NULL.  ce_psd_ns_lds: that
+ * footprint in bytes, 0 when there is none.  ce_adjoint_ns_variant and ce_tri_ns_variant stay -1 for such a template, and ce_get_plan does not report these two. */
+int ce_psd_ns_variant(ce_handle h);
+long ce_psd_ns_lds(ce_handle h);
 
 /*
  * THE OPTIMAL VALUE and its derivatives by the envelope theorem.  No reference call site: the reference's layers return the minimiser and the duals, and users
