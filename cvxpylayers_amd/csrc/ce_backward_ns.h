@@ -55,7 +55,7 @@
 // REF: y-hat of a triple is exp_project_dual / pow_project_dual_of_entry from the cold start exp_dual_eig / pow_dual_eig evaluate at -- the same decision, the
 // rule of ns_soc_kind.  W and lambda live behind the index arrays in LDS (ns_layout's TRI mode).
 //
-// PSD = true (with FWD, REF or not; never QP, TRI or MANY): PSD blocks beside the plain cones (cone_engine.hip ce_jvp_psd, ce_refine_psd: entry points of their own, ce_jvp
+// PSD = true (with FWD, REF or not, or with MANY, FWD or not -- below; never QP or TRI): PSD blocks beside the plain cones (cone_engine.hip ce_jvp_psd, ce_refine_psd: entry points of their own, ce_jvp
 // and ce_refine keep refusing such templates).  smat(v_c) = U Lambda U^T by the workgroup's Jacobi sweeps (ce_psd_jacobi.h); in the basis E_ab = svec(sym(u_a u_b^T))
 // D Pi is diagonal with eigenvalue B_ab (1 / 0 / l+ / (l+ - l-), k_backward_rt's comparisons, no snap).  The block's rows of A are rotated in place,
 // a~ = svec(U^T smat(a) U) per column, gamma = Q^T g_y with them; afterwards a rotated row is an equality, a dropped row or ONE weighted row of the list, exactly a
@@ -87,10 +87,22 @@
 // Without FWD, with QP (cone_engine.hip ce_vjp_qp_many): K cotangents of the adjoint with P.  The system is (H + P) r_x - B^T mu = f, B r_x = d_B; per cotangent the plain
 // many-cotangent rebuild plus the P terms of the many-tangent one (t_j = p_j . x_p and Z^T P x_p in the reduced right-hand side, (P r_x)[piv] in g), and one more output
 // row dP = -sym(r_x x^T) through the structure.  No re-solve list: a flagged instance keeps the dropped-variable answer, status 4 for every k.
+// With PSD, FWD or not (cone_engine.hip ce_jvp_psd_many, ce_vjp_psd_many; never REF, QP or TRI beside them): K tangents / K cotangents with PSD blocks, the two modes
+// that make seventeen.  Once per instance the PSD code above runs as it stands on a zero right-hand side (psd_decompose, A_c rotated in place column by column, B -> lamp,
+// the weighted rows numbered behind the boundary cones', NS_TRI_STIFF); psdU, psdEv, lamp, rkind and eqrow stay in LDS behind the sweep on the blocks' footprint
+// (psd_ns_variant, psd_ns_lds: no segment is added -- psdScr idles behind the decomposition, the first (X, W) pair of psdXW is the rotation workspace of a right-hand
+// side: psd_rotate_vec, all threads, three phases per block behind workgroup-uniform barriers).  Per tangent the plain many-tangent rebuild plus gamma_c = Q^T g_y,c per
+// block: a B = 1 row puts its gamma into d_B, a B = 0 row contributes nothing, a weighted row puts theta gamma into its weight slot (qv2, by row) and theta t into its
+// list entry, as a triple's; step 5 and the PSD forward epilogue follow unchanged.  Per cotangent the plain many-cotangent rebuild plus h = Q^T dy_c per block: a B = 1
+// row gives its entry of d_B, a B = 0 row d = 0, a weighted row d = B h and the share u = theta h of f = dx + A^T u on the rotated row; behind step 5
+// r~_y = mu (B = 1), 0 (B = 0), (d - B a~ . r_x) / (1 - B) (weighted), rotated back r_y,c = Q r~_y,c in front of the unchanged output pass (original basis, ce_vjp's
+// boundary convention).  It is the one adjoint with PSD blocks this kernel has.  Flags belong to the matrix: a vanishing pivot, neq > n or a weighted PSD row with
+// 1 - B < NS_TRI_STIFF flag the instance for every k and it is listed once -- the threshold is carried over AGAIN (the triples' forward law -> the triples' adjoint ->
+// PSD rows, in both directions): not measured on PSD rows, not measured for an adjoint.  A flagged instance runs to the same barriers as any other.
 //
 // Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes (one tangent or many) and in the many-cotangent adjoint.  PSD blocks in the forward
-// derivative and the refinement with PSD.  The adjoint of PSD templates keeps k_backward_rt, and so do the SINGLE-cotangent adjoint with triples and the single-cotangent
-// adjoint with a quadratic objective.
+// derivative, the refinement, and the two many-modes with PSD.  The SINGLE-cotangent adjoint of PSD templates keeps k_backward_rt, and so do the single-cotangent adjoint
+// with triples and the single-cotangent adjoint with a quadratic objective.
 #pragma once
 #include "ce_common.h"
 #include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
@@ -119,7 +131,7 @@ __device__ __forceinline__ int ns_soc_kind(int d, double t0, double nz, double &
 
 // TRI: the forward derivative hands an instance with a weighted triple row of 1 - lambda below this to the re-solve (the elimination's error at the threshold, by the
 // measured law: 0.03 eps / NS_TRI_STIFF^2 = 3e-8).  The many-cotangent adjoint with triples carries the rule over as it stands (flagged for every k): the law was
-// measured on the forward derivative, not on the adjoint.
+// measured on the forward derivative, not on the adjoint.  PSD rows carry it over again, in the forward modes and in the many-cotangent adjoint: not measured there.
 constexpr double NS_TRI_STIFF = 1e-5;
 
 template <bool FWD, bool REF = false, bool QP = false, bool TRI = false, bool MANY = false, bool PSD = false> struct NsFwdArg { typedef NsNoJvp type; };
@@ -137,6 +149,8 @@ template <> struct NsFwdArg<false, false, false, true, true> { typedef NsVjpTriM
 template <> struct NsFwdArg<true, false, false, true, true> { typedef NsJvpManyTri type; };
 template <> struct NsFwdArg<true, false, false, false, false, true> { typedef NsJvpPsd type; };
 template <> struct NsFwdArg<true, true, false, false, false, true> { typedef NsRefinePsd type; };
+template <> struct NsFwdArg<false, false, false, false, true, true> { typedef NsVjpManyPsd type; };
+template <> struct NsFwdArg<true, false, false, false, true, true> { typedef NsJvpManyPsd type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well; PSD: the block's segments on top of A leave room for two at the shapes it serves)
@@ -150,10 +164,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     static_assert((FWD && !QP) || (!FWD && !REF && !QP && MANY) || !TRI,
                   "exponential / power triples: the forward modes with a linear objective (one tangent, many tangents, refinement), and the many-cotangent adjoint "
                   "with one (their single-cotangent adjoint lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !REF && !(TRI && QP)) || (FWD && !REF && !(TRI && QP)),
+    static_assert(!MANY || (!FWD && !REF && !(TRI && QP) && !(PSD && (QP || TRI))) || (FWD && !REF && !(TRI && QP) && !(PSD && (QP || TRI))),
                   "many right-hand sides on one factorisation: the adjoint (K cotangents) or the forward derivative (K tangents), each with plain cones, P or not, or "
-                  "with triples and a linear objective; never the refinement, never triples with P");
-    static_assert(!PSD || (FWD && !QP && !TRI && !MANY), "PSD blocks: the forward derivative and the refinement, linear objective, one right-hand side, no triple beside them");
+                  "with triples and a linear objective, or with PSD blocks and a linear objective; never the refinement, never triples or PSD blocks with P, never both");
+    static_assert(!PSD || (!QP && !TRI && ((FWD && !MANY) || (MANY && !REF))),
+                  "PSD blocks: the forward derivative and the refinement on one right-hand side, K tangents and K cotangents on one factorisation; linear objective, no "
+                  "triple beside them (their single-cotangent adjoint lives in k_backward_rt)");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -257,6 +273,38 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 const int k = T.sord[c];
                 psd_jacobi<NTHR>(vs + T.soff[c], k, psdScr, psdU + c * msq, psdScr + 2 * msq, red);
                 for (int i = tid; i < k; i += NTHR) psdEv[c * T.maxs + i] = psdScr[i * k + i];
+                __syncthreads();
+            }
+        }
+    };
+    // PSD with MANY: one block vector per right-hand side through the retained U, in place, every block in turn on the first (X, W) pair of psdXW (the rotation
+    // workspace per right-hand side; psdScr idles behind the decomposition).  back == false:  r_c <- Q^T r_c = svec(U^T smat(r_c) U)  (gamma of a tangent, h of a
+    // cotangent);  back == true:  r_c <- Q r_c = svec(U smat(r_c) U^T)  (r_y of a cotangent).  All threads; three phases per block behind barriers, the block loop
+    // and the phases workgroup-uniform (T.ns, T.sord are the template's); the caller has a barrier in front, the last phase ends behind one.
+    auto psd_rotate_vec = [&](double *vec, bool back) {
+        if constexpr (PSD && MANY) {
+            double *X = psdXW, *Wm = psdXW + msq;
+            for (int c = 0; c < T.ns; c++) {
+                const int k = T.sord[c], r0 = T.soff[c], d = k * (k + 1) / 2;
+                const double *Um = psdU + c * msq;
+                for (int idx = tid; idx < k * k; idx += NTHR) {
+                    const int i = idx / k, j = idx - i * k, a = i >= j ? i : j, b = i >= j ? j : i;
+                    const double v = vec[r0 + b * k - (b * (b - 1)) / 2 + (a - b)];
+                    X[idx] = (a == b) ? v : v * M_SQRT1_2;
+                }
+                __syncthreads();
+                for (int idx = tid; idx < k * k; idx += NTHR) {          // W = X U  (back: X U^T)
+                    const int i = idx / k, j = idx - i * k;
+                    double acc = 0; for (int a = 0; a < k; a++) acc = fma(X[i * k + a], back ? Um[j * k + a] : Um[a * k + j], acc);
+                    Wm[idx] = acc;
+                }
+                __syncthreads();
+                for (int pos = tid; pos < d; pos += NTHR) {              // U^T W  (back: U W), packed back as svec
+                    int b = 0, rem = pos; while (rem >= k - b) { rem -= k - b; b++; }
+                    const int a = b + rem;
+                    double acc = 0; for (int i = 0; i < k; i++) acc = fma(back ? Um[a * k + i] : Um[i * k + a], Wm[i * k + b], acc);
+                    vec[r0 + pos] = (a == b) ? acc : acc * M_SQRT2;
+                }
                 __syncthreads();
             }
         }
@@ -1296,6 +1344,13 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 }
             }
         }
+        if constexpr (PSD && MANY) {
+            // PSD blocks, from the retained U and B: the rows keep gamma_c = Q^T g_y,c (a B = 1 row: its entry of d_B, taken by eqrow below; a B = 0 row: nothing in f, the
+            // epilogue wants its gamma), and a weighted row's share of f, theta gamma, waits in qv2 BY ROW beside the boundary cones'
+            __syncthreads();
+            psd_rotate_vec(dv, false);
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) { const double lam = lamp[i - psd0]; qv2[i] = rkind[i] == RK_MIX ? lam / (1 - lam) * dv[i] : 0.0; }
+        }
         __syncthreads();
         // d_B = gamma_B by equality (eqrow and ceq are the numbering's inverse) -> mu
         for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
@@ -1345,6 +1400,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         if constexpr (TRI) {          // a triple's weighted row is one list row of its own: theta t (eqrow keeps its list entry)
             for (int i = T.eoff + tid; i < m; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
+        }
+        if constexpr (PSD && MANY) {          // so is a block's weighted row
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
         }
         __syncthreads();
         // f = -g_x + sum u_i a_i by column.  A pivot column keeps f[piv] (the multipliers want it); a free column takes  h + sum (u_i - theta q'_i) a~_i  with
@@ -1440,6 +1498,17 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
                 }
             }
         }
+        if constexpr (PSD && MANY) {
+            // PSD blocks, from the retained U and B: h = Q^T dy_c, d = B h on the rotated rows (a B = 1 row: its entry of d_B, taken by eqrow below; a B = 0 row: 0), and
+            // for a weighted row its weight u = theta h in f = dx + A^T u BY ROW beside the boundary cones' (k_backward_rt: a~ d / (1 - B))
+            __syncthreads();
+            psd_rotate_vec(dv, false);
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) {
+                const double lam = lamp[i - psd0], t = dv[i];
+                dv[i] = lam * t;
+                qv2[i] = rkind[i] == RK_MIX ? lam / (1 - lam) * t : 0.0;
+            }
+        }
         __syncthreads();
         // d_B by equality (the numbering's source array was the elimination's to overwrite: eqrow and ceq are its inverse) -> mu
         for (int i = tid; i < m; i += NTHR) if (rkind[i] == RK_EQ) mu[eqrow[i]] = dv[i];
@@ -1491,6 +1560,9 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         }
         if constexpr (TRI) {          // a triple's weighted row is one list row of its own: theta t (eqrow keeps its list entry)
             for (int i = T.eoff + tid; i < m; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
+        }
+        if constexpr (PSD && MANY) {          // so is a block's weighted row
+            for (int i = psd0 + tid; i < T.eoff; i += NTHR) if (rkind[i] == RK_MIX) { const int q = eqrow[i]; tvec[q] *= wgt[q]; }
         }
         __syncthreads();
         // f' = dx + sum u'_i a_i by column: a pivot column keeps f'[piv] (the multipliers want it), a free column takes  dx + sum (u'_i - theta q'_i) a~_i, which
@@ -1834,6 +1906,17 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
 #pragma unroll
             for (int a = 0; a < 3; a++) vv[r0 + a] = Wl[3 * a] * rt[0] + Wl[3 * a + 1] * rt[1] + Wl[3 * a + 2] * rt[2];
         }
+    }
+    if constexpr (PSD && MANY) {
+        // PSD blocks (as k_backward_rt): r~_y on the rotated rows -- the multiplier of an equality row, d = 0 of a dropped row, (d - B a~ . r_x) / (1 - B) of a weighted
+        // row with a~ . r_x from the list (tvec) -- and back to the original basis per block, r_y,c = Q r~_y,c
+        for (int i = psd0 + tid; i < T.eoff; i += NTHR) {
+            const int rk = rkind[i], e = eqrow[i];
+            const double lam = lamp[i - psd0];
+            vv[i] = rk == RK_EQ ? dB[e] : (rk == RK_MIX ? (dv[i] - lam * tvec[e]) / (1 - lam) : dv[i]);
+        }
+        __syncthreads();
+        psd_rotate_vec(vv, true);
     }
     __syncthreads();
     NS_STAMP(9);

@@ -106,6 +106,12 @@ struct NsVjpTriMany : NsMany {};
 // tests/test_gpu_ns_many_edges.py collects the ce_launch_ns overloads whose type matches Ns\w*Many and pins them to the modes that file covers; this mode's edge
 // ledger lives in tests/test_gpu_jvp_tri_many_edges.py (tests/test_jvp_tri_many_args.py pins both facts)
 struct NsJvpManyTri : NsJvpMany {};
+// k_backward_ns<..., MANY = true, PSD = true>, without and with FWD: K cotangents of the adjoint / K tangents of the forward derivative with PSD blocks on one
+// factorisation (cone_engine.hip ce_vjp_psd_many, ce_jvp_psd_many).  NsMany's / NsJvpMany's fields and strides (the blocks are described by DevT); types of their own
+// select the launchers.  Neither name ends in "Many", for NsJvpManyTri's reason: their edge ledger lives in tests/test_gpu_psd_many_edges.py
+// (tests/test_psd_many_args.py pins the names)
+struct NsVjpManyPsd : NsMany {};
+struct NsJvpManyPsd : NsJvpMany {};
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -260,6 +266,8 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyTri &w);         // (ce_tu_ns_jvp_tri_many.hip: the forward derivative with triples for K tangents -- the type's name: see its declaration)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpPsd &w);             // (ce_tu_ns_psd.hip: the forward derivative and the refinement
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefinePsd &w);          //  with PSD blocks)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpManyPsd &w);         // (ce_tu_ns_vjp_psd_many.hip: the adjoint with PSD blocks for K cotangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyPsd &w);         // (ce_tu_ns_jvp_psd_many.hip: the forward derivative with PSD blocks for K tangents)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -301,6 +309,8 @@ hipError_t ce_setattr_ns_vjp_qp_many(int bytes);
 hipError_t ce_setattr_ns_vjp_tri_many(int bytes);
 hipError_t ce_setattr_ns_jvp_tri_many(int bytes);
 hipError_t ce_setattr_ns_psd(int bytes);
+hipError_t ce_setattr_ns_vjp_psd_many(int bytes);
+hipError_t ce_setattr_ns_jvp_psd_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -327,6 +327,10 @@ int ce_vjp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >
 // the many-tangent mode with triples: the same rule and row (its rebuild lives in the buffers the single-tangent mode and the many-cotangent mode use on tri_ns_lds:
 // no shape is excluded by the footprint)
 int ce_jvp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >= 0) ? h->plan.tri_ns_variant : -1; }
+// the many-cotangent and many-tangent modes with PSD blocks run on the footprint of the blocks' forward modes: psd_ns_variant's row (the psd planner already asks
+// that the LSQR vectors of the re-solve fit LDS; the rotation of a right-hand side lives in the (X, W) pairs the single-tangent mode rotates A on)
+int ce_vjp_psd_many_variant(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? h->plan.psd_ns_variant : -1; }
+int ce_jvp_psd_many_variant(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? h->plan.psd_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -600,8 +604,10 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 // K cotangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., MANY> factors every instance once and writes all K answers; the instances
 // it lists as rank deficient are listed ONCE, and ONE launch of the LSQR kernel walks the K x list (cotangent, instance) pairs (SaWalkMany).  The list parity flips once.
 // Without an armed re-solve (q_vals == NULL, ce_set_adjoint_resolve(h, 0)) ce_vjp itself does not run the elimination: K calls of it then, the same rule.
-// (tri: ce_vjp_tri_many -- the same body on the triples' variant and footprint; `who` names the entry point in the messages)
-static int vjp_many_run(ce_handle h, bool tri, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+// (kind NS_MANY_TRI: ce_vjp_tri_many -- the same body on the triples' variant and footprint; NS_MANY_PSD: ce_vjp_psd_many -- on the PSD blocks'; `who` names the
+// entry point in the messages)
+enum NsManyKind { NS_MANY_PLAIN = 0, NS_MANY_TRI = 1, NS_MANY_PSD = 2 };
+static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                         const double *x, const double *y, const double *s, const double *dx, const double *dy,
                         double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
     const CePlan &P = h->plan;
@@ -633,7 +639,8 @@ static int vjp_many_run(ce_handle h, bool tri, const char *who, int B, int K, co
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
     ba.adj = adj_status; ba.fix = fix.cur;
     h->last_fast = -1;
-    if (tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsVjpTriMany{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) {
+    if (kind == NS_MANY_PSD ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsVjpManyPsd{W})
+        : kind == NS_MANY_TRI ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsVjpTriMany{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) {
         g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG;
     }
     const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
@@ -656,7 +663,7 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
                 "CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp once per cotangent";
         return CE_E_UNSUPPORTED;
     }
-    return vjp_many_run(h, false, "ce_vjp_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+    return vjp_many_run(h, NS_MANY_PLAIN, "ce_vjp_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
 }
 // K cotangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_vjp_many's body with k_backward_ns<..., TRI, MANY> on the
 // triples' variant and footprint.  Without an armed re-solve K calls of ce_vjp, whose pivoting kernel serves such templates.
@@ -669,7 +676,20 @@ int ce_vjp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
                 "kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_vjp_many or ce_vjp";
         return CE_E_UNSUPPORTED;
     }
-    return vjp_many_run(h, true, "ce_vjp_tri_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+    return vjp_many_run(h, NS_MANY_TRI, "ce_vjp_tri_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+}
+// K cotangents at one solution of a template with PSD blocks (include/cone_engine.h): ce_vjp_many's body with k_backward_ns<..., MANY, PSD> on the blocks' variant and
+// footprint.  Without an armed re-solve K calls of ce_vjp, whose pivoting kernel serves such templates.
+int ce_vjp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                    double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_psd_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    if (ce_vjp_psd_many_variant(h) < 0) {
+        g_err = "ce_vjp_psd_many: this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, "
+                "its footprint exceeds LDS, or CE_BWD_NS=0); call ce_vjp once per cotangent";
+        return CE_E_UNSUPPORTED;
+    }
+    return vjp_many_run(h, NS_MANY_PSD, "ce_vjp_psd_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
 }
 
 // summary of an int32 vector v[B] (status of a forward call, or adj_status of a backward call): out[0] = min v, out[1] = #{v == 2} ("solved,
@@ -1212,18 +1232,20 @@ int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
 // K tangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., FWD, ..., MANY> factors every instance once and writes all K answers; plain kind:
 // the instances it lists as rank deficient are listed ONCE, and ONE launch of the LSQR kernel walks the K x list (tangent, instance) pairs (SaWalkMany; the list parity
 // flips once).  QP kind: no re-solve, the dropped-variable answer stands with status 4 for every k.  tri: ce_jvp_tri_many -- the plain kind's body with
-// k_backward_ns<..., FWD, ..., TRI, MANY> on the triples' variant and footprint.
-static int jvp_many_ns(ce_handle h, bool tri, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
+// k_backward_ns<..., FWD, ..., TRI, MANY> on the triples' variant and footprint; psd: ce_jvp_psd_many -- with k_backward_ns<..., FWD, ..., MANY, PSD> on the blocks'.
+static int jvp_many_ns(ce_handle h, NsManyKind kind, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                        const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                        const double *tP_vals, long stP_k, long stP_b, double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
                        double atol, double btol, double conlim, int iter_lim, void *stream) {
-    const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_jvp_qp_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many");
+    const bool qp = P_vals != nullptr, tri = kind == NS_MANY_TRI, psd = kind == NS_MANY_PSD;
+    const std::string who = qp ? "ce_jvp_qp_many" : (psd ? "ce_jvp_psd_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (qp) { const int rc = qp_ns_check(h, "ce_jvp_qp_many"); if (rc) return rc; }
-    if ((qp ? ce_jvp_qp_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h))) < 0) {
+    if ((qp ? ce_jvp_qp_many_variant(h) : (psd ? ce_jvp_psd_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h)))) < 0) {
         g_err = who + (qp ? ": this template has no many-tangent elimination with a quadratic objective; call ce_jvp_qp once per tangent"
+                       : psd ? ": this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its "
+                               "footprint exceeds LDS, or CE_BWD_NS=0); call ce_jvp_lsqr once per tangent"
                        : tri ? ": this template has no search-free elimination with triples (no exponential / power cone, PSD cones, a quadratic objective inside the "
                                "kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); call ce_jvp_many or ce_jvp"
                           : ": this template has no many-tangent elimination (PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108, CE_BWD_NS=0, "
@@ -1247,6 +1269,7 @@ static int jvp_many_ns(ce_handle h, bool tri, int B, int K, const double *A_vals
     const NsJvpMany W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), K, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b,
                       dx, dy, ds, sxk, syk, sak, lsqr_iters};
     const int lrc = qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
+                       : psd ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsJvpManyPsd{W})
                        : tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsJvpManyTri{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
     if (lrc) { g_err = "internal: no many-tangent kernel for the planned variant"; return CE_E_BADARG; }
     if (!qp) {
@@ -1269,7 +1292,7 @@ int ce_jvp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
         g_err = "ce_jvp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
     if (h->plan.qp_native) { g_err = "ce_jvp_many: this template runs a quadratic objective inside the kernels; use ce_jvp_qp_many"; return CE_E_UNSUPPORTED; }
-    return jvp_many_ns(h, false, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+    return jvp_many_ns(h, NS_MANY_PLAIN, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
                        atol, btol, conlim, iter_lim, stream);
 }
 // K tangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_jvp_many's body with k_backward_ns<..., FWD, ..., TRI, MANY> on
@@ -1280,7 +1303,18 @@ int ce_jvp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
     if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
         g_err = "ce_jvp_tri_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
-    return jvp_many_ns(h, true, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+    return jvp_many_ns(h, NS_MANY_TRI, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+                       atol, btol, conlim, iter_lim, stream);
+}
+// K tangents at one solution of a template with PSD blocks (include/cone_engine.h): ce_jvp_many's body with k_backward_ns<..., FWD, ..., MANY, PSD> on the blocks'
+// variant and footprint; the re-solve behind it is the same one launch.  Refusals come before any device call.
+int ce_jvp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
+        g_err = "ce_jvp_psd_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    return jvp_many_ns(h, NS_MANY_PSD, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
                        atol, btol, conlim, iter_lim, stream);
 }
 int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
@@ -1289,7 +1323,7 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
     if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0 || stP_b < 0) {
         g_err = "ce_jvp_qp_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
-    return jvp_many_ns(h, false, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
+    return jvp_many_ns(h, NS_MANY_PLAIN, B, K, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, tP_vals, stP_k, stP_b, dx, dy, ds, jvp_status, lsqr_iters,
                        0.0, 0.0, 0.0, 0, stream);
 }
 // K cotangents at one solution of a template with a quadratic objective inside the kernels (include/cone_engine.h).  One launch of k_backward_ns<..., QP, ..., MANY>

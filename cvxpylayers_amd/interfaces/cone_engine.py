@@ -39,8 +39,8 @@ class ConeEngine:
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
-        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" when the last vjp_many made that one call, None when it looped over vjp
-        self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many call) / "loop" (K calls of jvp): what the last jvp_many ran
+        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
+        self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
@@ -359,7 +359,7 @@ class ConeEngine:
         return (dA if batch_minor_out else dA.t()), dq, adj
 
     def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False,
-                 qp_many: bool = False, tri_many: bool = False):
+                 qp_many: bool = False, tri_many: bool = False, psd_many: bool = False):
         """K cotangents at one solution: dx (K, B, n), dy (K, B, m) or None (zero).  Returns dA (K, B, nnz_aug), dq (K, B, n+1), adj (K, B) -- and dP (K, B, nnz_p) when
         P_bm is given -- all batch-major.  For every k the result is what vjp returns for (dx[k], dy[k]).
         One ce_vjp_many call (each instance factored once, last_vjp_many_path == "many") under the rule that sends vjp to the search-free elimination: path
@@ -372,7 +372,10 @@ class ConeEngine:
         tri_many (opt-in, default False): on a template with exponential / power triples (ce_vjp_tri_many_variant >= 0), path "per_instance", q_eval given, no P, one
         ce_vjp_tri_many call instead of the K ce_vjp calls of the pivoting kernel (last_vjp_many_path == "many", last_vjp_kernel == "ce_vjp_tri_many"): the
         search-free elimination diagonalises and rotates each triple once per instance.  The two kernels agree on regular instances but need not flag the same ones
-        (a pivot search there, the stiff-row rule here; a flagged instance gets LSQR's minimum-norm answer) -- hence opt-in.  In every other case the flag changes nothing."""
+        (a pivot search there, the stiff-row rule here; a flagged instance gets LSQR's minimum-norm answer) -- hence opt-in.  In every other case the flag changes nothing.
+        psd_many (opt-in, default False): on a template with PSD blocks (ce_vjp_psd_many_variant >= 0), under tri_many's conditions, one ce_vjp_psd_many call instead
+        of the K ce_vjp calls of the pivoting kernel (last_vjp_kernel == "ce_vjp_psd_many"): each block is decomposed and its rows rotated once per instance.  The
+        same caveat on flags (the stiff-row rule, carried over to PSD rows); in every other case the flag changes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
@@ -382,8 +385,11 @@ class ConeEngine:
         many_qp = (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
         many_tri = (not force_loop and tri_many and not many and path == "per_instance" and q_eval is not None and P_bm is None
                     and _lib.lib().ce_vjp_tri_many_variant(self._h) >= 0)
-        self.last_vjp_many_path = "many" if (many or many_qp or many_tri) else "loop"
-        self.last_vjp_kernel = "ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else ("ce_vjp_tri_many" if many_tri else None))
+        many_psd = (not force_loop and psd_many and not many and not many_tri and path == "per_instance" and q_eval is not None and P_bm is None
+                    and _lib.lib().ce_vjp_psd_many_variant(self._h) >= 0)
+        self.last_vjp_many_path = "many" if (many or many_qp or many_tri or many_psd) else "loop"
+        self.last_vjp_kernel = ("ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else ("ce_vjp_tri_many" if many_tri else
+                                                                                             ("ce_vjp_psd_many" if many_psd else None))))
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
             return out + ((torch.empty((K, B, self.nnz_p), **f64),) if P_bm is not None else ())
@@ -400,7 +406,7 @@ class ConeEngine:
                                            None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), dP.data_ptr(), adj.data_ptr(), self._stream())
             _lib.check(rc, "ce_vjp_qp_many")
             return dA, dq, adj, dP
-        if not (many or many_tri):
+        if not (many or many_tri or many_psd):
             zero_dy = torch.zeros((B, self.m), **f64) if dy is None else None
             outs = [self.vjp(A_bm, x, y, s, dx[k], zero_dy if dy is None else dy[k], P_bm=P_bm, path=path, lsqr=lsqr, q_eval=q_eval) for k in range(K)]
             res = (torch.stack([o[0].t() for o in outs]).contiguous(), torch.stack([o[1].t() for o in outs]).contiguous(), torch.stack([o[2] for o in outs]))
@@ -415,7 +421,8 @@ class ConeEngine:
         dA = torch.empty((K, B, self.nnz_aug), **f64)
         dq = torch.empty((K, B, self.n + 1), **f64)
         adj = torch.empty((K, B), dtype=torch.int32, device=dev)
-        fn, name = (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else (_lib.lib().ce_vjp_many, "ce_vjp_many")
+        fn, name = ((_lib.lib().ce_vjp_psd_many, "ce_vjp_psd_many") if many_psd else
+                    (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else (_lib.lib().ce_vjp_many, "ce_vjp_many"))
         rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
                 None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
         _lib.check(rc, name)
@@ -521,7 +528,7 @@ class ConeEngine:
         return dx, dy, ds, st
 
     def jvp_many(self, A_bm, x, y, s, tA, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "direct",
-                 P_bm=None, tP=None, force_loop: bool = False, tri_many: bool = False):
+                 P_bm=None, tP=None, force_loop: bool = False, tri_many: bool = False, psd_many: bool = False):
         """K tangents at one solution.  tA (K, B, nnz_aug), tq (K, B, n+1), tP (K, B, nnz_p) -- or (K, .) for a tangent every instance shares (batch stride 0: a
         parameter-space basis vector pushed through the parameter maps); at most two of the three may be None (zero).  Returns dx (K, B, n), dy (K, B, m),
         ds (K, B, m), status (K, B) and sets last_lsqr_iters (K, B): for every k what jvp(method=method) returns for the k-th tangent.
@@ -531,7 +538,11 @@ class ConeEngine:
         tri_many (opt-in, default False): on a template with exponential / power triples (ce_jvp_tri_many_variant >= 0), method "direct", no P_bm, any path but
         "const_a", one ce_jvp_tri_many call instead of the K ce_jvp calls (last_jvp_many_path == "many", last_jvp_kernel == "ce_jvp_tri_many"): each triple is
         diagonalised and rotated and each instance factored once for all K tangents, and one LSQR launch re-solves the flagged instances for every k.  Flags and
-        the re-solve's answers are those of the loop.  In every other case the flag changes nothing."""
+        the re-solve's answers are those of the loop.  In every other case the flag changes nothing.
+        psd_many (opt-in, default False): on a template with PSD blocks (ce_jvp_psd_many_variant >= 0), under tri_many's conditions, one ce_jvp_psd_many call
+        (last_jvp_kernel == "ce_jvp_psd_many") instead of the K calls of the loop, which are ce_jvp_lsqr calls on such a template: each block is decomposed, its rows
+        rotated and each instance factored once for all K tangents.  With force_loop the flag selects the loop's kernel instead: K ce_jvp_psd calls, the elimination
+        this mode repeats K times less -- its comparator.  In every other case the flag changes nothing."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp_many: method must be 'lsqr' or 'direct', got {method!r}")
         given = [t for t in (tA, tq, tP) if t is not None]
@@ -550,7 +561,10 @@ class ConeEngine:
         many = not force_loop and method == "direct" and (L.ce_jvp_qp_many_variant(self._h) >= 0 if P_bm is not None else (path != "const_a" and L.ce_jvp_many_variant(self._h) >= 0))
         many_tri = (not force_loop and tri_many and not many and method == "direct" and P_bm is None and path != "const_a"
                     and L.ce_jvp_tri_many_variant(self._h) >= 0)
-        many = many or many_tri
+        psd_ok = (psd_many and not many and not many_tri and method == "direct" and P_bm is None and path != "const_a"
+                  and L.ce_jvp_psd_many_variant(self._h) >= 0)
+        many_psd = psd_ok and not force_loop
+        many = many or many_tri or many_psd
         self.last_jvp_many_path = "many" if many else "loop"
         i32 = dict(dtype=torch.int32, device=dev)
         if B == 0 or K == 0:
@@ -564,7 +578,7 @@ class ConeEngine:
             for k in range(K):
                 tqk = of(tq, k)
                 outs.append(self.jvp(A_bm, x, y, s, of(tA, k), None if tqk is None else tqk.t(), path=path, lsqr=lsqr, q_eval=q_eval, conlim=conlim, method=method,
-                                     P_bm=P_bm, tP_bm=of(tP, k)))
+                                     P_bm=P_bm, tP_bm=of(tP, k), psd_ns=psd_ok))
                 its.append(self.last_lsqr_iters)
             self.last_lsqr_iters = torch.stack(its)
             return tuple(torch.stack([o[i] for o in outs]) for i in range(4))
@@ -587,7 +601,8 @@ class ConeEngine:
             if system == "reduced":
                 q_eval = None
             qd, q_args = self._q_args(q_eval)
-            fn, name = (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many, "ce_jvp_many")
+            fn, name = ((L.ce_jvp_psd_many, "ce_jvp_psd_many") if many_psd else
+                        (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many, "ce_jvp_many"))
             rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
                     *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream())
         _lib.check(rc, name)

@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, psd_elimination, psd_elimination_active, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -156,6 +156,8 @@ class _Saved(NamedTuple):
     tri_adjoint: str = "pivoting"           # tri_adjoint() of this call: "search_free" sends adjoint_many of a node with exponential / power cones to ce_vjp_tri_many (backward() ignores it)
     tri_tangents: str = "loop"              # tri_tangents() of this call: "many" sends tangent_many of a node with exponential / power cones to ce_jvp_tri_many (one-tangent forward-mode AD ignores it)
     psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
+    psd_adjoint: bool = False               # psd_many_active(psd_adjoint()) of this call: adjoint_many of a node with PSD blocks runs ce_vjp_psd_many (backward() ignores it)
+    psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -190,7 +192,10 @@ class _ConeLayer(torch.autograd.Function):
         tri_adj = tri_adjoint(merged_args)        # (likewise)
         tri_tan = tri_tangents(merged_args)       # (likewise; read by tangent_many alone)
         n_newton = newton_first(merged_args)
-        psd_ns = psd_elimination_active(psd_elimination(merged_args), eng.psd_ns_variant, bool(len(eng.cone_dict.get("s", []) or [])))
+        has_psd = bool(len(eng.cone_dict.get("s", []) or []))
+        psd_ns = psd_elimination_active(psd_elimination(merged_args), eng.psd_ns_variant, has_psd)
+        psd_adj = psd_many_active("psd_adjoint", psd_adjoint(merged_args) == "search_free", eng.psd_ns_variant, has_psd)      # (read by adjoint_many alone)
+        psd_tan = psd_many_active("psd_tangents", psd_tangents(merged_args) == "many", eng.psd_ns_variant, has_psd)          # (read by tangent_many alone)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
         with torch.cuda.device(dev):
@@ -253,7 +258,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -408,12 +413,12 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
             dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
             x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
         out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm, qp_many=(saved.qp_adjoint == "search_free"),
-                           tri_many=(saved.tri_adjoint == "search_free"))
+                           tri_many=(saved.tri_adjoint == "search_free"), psd_many=saved.psd_adjoint)
         dA, dq, adj = out[:3]
         dP = out[3] if saved.P_bm is not None else None
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
-            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many"):
+            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many"):
                 info["adjoint"]["path"] = eng.last_vjp_kernel
         if K > 0 and batch_size > 0:
             any_k = adj[0].clone()
@@ -453,10 +458,11 @@ def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=Non
         if qp:
             dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, method="direct", P_bm=saved.P_bm, tP=tP)
         else:
-            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method, tri_many=(saved.tri_tangents == "many"))
+            dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method, tri_many=(saved.tri_tangents == "many"),
+                                         psd_many=saved.psd_tangents)
         if isinstance(info, dict):
             info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel,
-                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many") else "lsqr"}
+                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many", "ce_jvp_psd_many") else "lsqr"}
     return dx, dy, failed
 
 

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -167,6 +167,48 @@ def psd_elimination_active(mode: str, psd_ns_variant: int, has_psd: bool) -> boo
     if has_psd:
         _warn_once("psd_elimination_none", "MI355 solver: solver_args psd_elimination='search_free' is ignored on this template: the search-free elimination does not "
                                            "serve it (exponential / power cones or a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
+    return False
+
+
+def psd_adjoint(merged_args: dict) -> str:
+    """Which elimination serves MANY cotangents at one solution (CvxpyLayer.jacobian in the reverse direction, interfaces.mi355_if.adjoint_many) on a template with
+    PSD blocks:
+    absent / "pivoting" -> K calls of ce_vjp, the pivoting kernel: the blocks' Jacobi decompositions and the whole factorisation once per cotangent;
+    "search_free" -> one ce_vjp_psd_many call per chunk: the search-free elimination decomposes each block, rotates its rows and factors each instance once for
+    every cotangent (info["adjoint"]["path"] tells which ran).  The two agree on regular instances but need not flag the same ones (a pivot search there; here a
+    weighted PSD row with 1 - B < 1e-5 flags too -- the triples' rule, carried over, not measured on PSD rows); a flagged instance gets LSQR's minimum-norm answer,
+    hence opt-in.
+    Independent of psd_elimination, which keeps its documented routes.  The single-cotangent backward of .backward() ignores the key: one cotangent belongs to
+    ce_vjp.  Templates the mode does not serve ignore it: psd_many_active says so once where the template has a PSD block."""
+    mode = str(merged_args.get("psd_adjoint", "pivoting"))
+    if mode not in ("pivoting", "search_free"):
+        raise ValueError(f"MI355 solver: psd_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
+    return mode
+
+
+def psd_tangents(merged_args: dict) -> str:
+    """How MANY tangents at one solution (CvxpyLayer.jacobian in the forward direction, interfaces.mi355_if.tangent_many) are served on a template with PSD blocks:
+    absent / "loop" -> K single-tangent calls (ce_jvp_lsqr on such a template, under psd_elimination="search_free" too);
+    "many" -> one ce_jvp_psd_many call per chunk: each block decomposed, its rows rotated and each instance factored once for the whole chunk, and one LSQR launch
+    for the flagged instances of every tangent (info["jvp"]["kernel"] tells which ran).  Opt-in: the flagging rule for stiff rows is the triples', carried over.
+    Independent of psd_elimination.  Forward-mode AD with one tangent ignores the key.  Templates the mode does not serve ignore it, as psd_adjoint."""
+    mode = str(merged_args.get("psd_tangents", "loop"))
+    if mode not in ("loop", "many"):
+        raise ValueError(f"MI355 solver: psd_tangents must be 'loop' or 'many', got {mode!r}")
+    return mode
+
+
+def psd_many_active(key: str, asked: bool, psd_ns_variant: int, has_psd: bool) -> bool:
+    """True when adjoint_many / tangent_many of this call take the many-right-hand-side mode with PSD blocks: `key` (psd_adjoint / psd_tangents) asks for it and
+    the engine serves the template (ConeEngine.psd_ns_variant >= 0: the modes run on that row).  A template with a PSD block that is not served gets one notice
+    per key; a template without one is silent (the key is inert there)."""
+    if not asked:
+        return False
+    if psd_ns_variant >= 0:
+        return True
+    if has_psd:
+        _warn_once(key + "_none", f"MI355 solver: solver_args {key} is ignored on this template: the search-free elimination does not serve it (exponential / power "
+                                  "cones or a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
     return False
 
 

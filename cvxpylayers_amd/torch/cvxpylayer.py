@@ -467,6 +467,10 @@ class CvxpyLayer(torch.nn.Module):
         chunk; chunking by max_bytes is unchanged; info["adjoint"]["path"] == "ce_vjp_tri_many").  Opt-in: the two kernels need not flag the same instances (a pivot
         search there; here a weighted triple row with 1 - lambda < 1e-5 flags too), and a flagged instance gets LSQR's minimum-norm answer.  .backward() ignores
         the key; direction="forward" and "auto" keep their rules (the forward direction has a key of its own, below).
+        A template with PSD blocks runs the loop of K ce_vjp calls (the pivoting kernel, the blocks' decompositions with it) here by default; solver_args
+        {"psd_adjoint": "search_free"} makes one ce_vjp_psd_many call per chunk instead (each block decomposed, its rows rotated and each instance factored once for
+        the chunk; chunking by max_bytes is unchanged; info["adjoint"]["path"] == "ce_vjp_psd_many").  Opt-in for the triples' reason, with the triples' stiff-row
+        rule carried over to PSD rows; independent of psd_elimination; .backward() ignores the key.
         Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
 
         direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q
@@ -477,7 +481,10 @@ class CvxpyLayer(torch.nn.Module):
         default anyone wants.  A template with exponential / power cones runs the loop of K ce_jvp calls here by default (every triple diagonalised, its rows
         rotated and every instance factored once per parameter entry); solver_args {"tri_tangents": "many"} makes one ce_jvp_tri_many call per chunk instead: all
         of that once per instance for the chunk, and one LSQR launch for the flagged instances of every tangent (info["jvp"]["kernel"] == "ce_jvp_tri_many",
-        info["jvp"]["path"] stays "direct"; chunking is unchanged).  Opt-in; forward-mode AD with one tangent ignores the key.  direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
+        info["jvp"]["path"] stays "direct"; chunking is unchanged).  Opt-in; forward-mode AD with one tangent ignores the key.  A template with PSD blocks runs K single-tangent calls
+        here by default (ce_jvp_lsqr, under psd_elimination="search_free" too); solver_args {"psd_tangents": "many"} makes one ce_jvp_psd_many call per chunk instead
+        (info["jvp"]["kernel"] == "ce_jvp_psd_many", info["jvp"]["path"] "direct"; chunking is unchanged).  Opt-in; one-tangent forward-mode AD ignores the key.
+        direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
         because solver_args["mode"] means something else.)  Any other value: ValueError, before anything touches the device."""
         from cvxpylayers_amd.interfaces.mi355_if import adjoint_many, tangent_many
         from cvxpylayers_amd.interfaces.solver_args import LPGD_MODES

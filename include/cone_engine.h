@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -624,6 +624,41 @@ int ce_jvp_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
 /* >= 0: the template has the many-tangent mode with triples; the value is ce_tri_ns_variant's row (the rebuild lives in the buffers of the triples' footprint: no
  * shape is excluded, the launch plan is unchanged).  -1 otherwise, and for a NULL handle. */
 int ce_jvp_tri_many_variant(ce_handle h);
+
+/* MANY COTANGENTS AT ONE SOLUTION, PSD BLOCKS: for every k < K what ce_vjp returns for (dx[k], dy[k]) on a template with PSD blocks beside plain cones (linear
+ * objective, no exponential / power cone), from ONE factorisation per instance by the search-free elimination -- where ce_vjp runs the pivoting kernel, and with it
+ * the blocks' Jacobi decompositions, once per cotangent.  Once per instance smat(v_c) = U Lambda U^T of every block, its rows of A are rotated into the basis in
+ * which D Pi is diagonal with eigenvalue B (a rotated row is an equality, a dropped row or one weighted row of the reduced Hessian) and steps 1-4 run on a zero
+ * right-hand side; per cotangent the kernel rebuilds what ce_vjp_many rebuilds plus h = Q^T dy_c per block (d_B entry, 0, or d = B h with the share theta h of f),
+ * and rotates r_y back, r_y,c = Q r~_y,c, in front of the dA row (csrc/ce_backward_ns.h, MANY + PSD without FWD).
+ *   Arguments, layouts, dy == NULL, K == 1, q_vals == NULL / a switched-off re-solve (K ce_vjp calls inside) and the error rules are exactly ce_vjp_many's.
+ * Flags belong to the matrix: a vanishing pivot, more active rows than variables, or a weighted PSD row with 1 - B < 1e-5 (the forward derivative's rule for a stiff
+ * row of a triple, carried over again: not measured on PSD rows) flag the instance for every k; it is listed once and one launch of the LSQR kernel serves all K
+ * cotangents of the listed instances (status 4 | 8).  The pivoting kernel behind ce_vjp need not flag the same instances.
+ * CE_E_UNSUPPORTED with a ce_last_error that names the reason when ce_vjp_psd_many_variant(h) < 0.  ce_vjp_many and ce_vjp_tri_many keep refusing such templates. */
+int ce_vjp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                    double *dA_vals, double *dq_vals, int *adj_status, void *stream);
+/* >= 0: the template has the many-cotangent mode with PSD blocks; the value is ce_psd_ns_variant's row (same footprint, the launch plan is unchanged).  -1
+ * otherwise, and for a NULL handle. */
+int ce_vjp_psd_many_variant(ce_handle h);
+
+/* MANY TANGENTS AT ONE SOLUTION, PSD BLOCKS: for every k < K what ce_jvp_psd returns for the k-th tangent, from ONE factorisation per instance -- the forward twin of
+ * ce_vjp_psd_many, where ce_jvp_psd re-decomposes every block, re-rotates its rows and re-factors every instance once per tangent.  Per tangent the kernel rebuilds
+ * what ce_jvp_many rebuilds plus gamma_c = Q^T g_y,c per block (a B = 1 row: its entry of d_B; a B = 0 row: nothing; a weighted row: theta gamma in f and theta t in
+ * the list), then step 5 and the blocks' forward epilogue, dy_c = Q (B o eta), ds_c = -Q ((1 - B) o eta) (csrc/ce_backward_ns.h, FWD + MANY + PSD).
+ *   Arguments, layouts, strides (a batch stride of 0: one tangent row for the whole batch), K == 1 and the error rules are exactly ce_jvp_many's.
+ * Flags as ce_vjp_psd_many (ce_jvp_psd's own rule for a stiff row); a flagged instance is listed once and ONE launch of the LSQR kernel re-solves all K tangents of
+ * the listed instances (status 4 | 8, iterations > 0, the answers of K ce_jvp_lsqr calls on those instances).
+ * CE_E_UNSUPPORTED with a ce_last_error that names the entry point and the reason when ce_jvp_psd_many_variant(h) < 0; nothing is written then.  ce_jvp_many and
+ * ce_jvp_tri_many keep refusing templates with PSD blocks. */
+int ce_jvp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                    const double *x, const double *y, const double *s,
+                    const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                    double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
+                    double atol, double btol, double conlim, int iter_lim, void *stream);
+/* >= 0: the template has the many-tangent mode with PSD blocks; the value is ce_psd_ns_variant's row.  -1 otherwise, and for a NULL handle. */
+int ce_jvp_psd_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
