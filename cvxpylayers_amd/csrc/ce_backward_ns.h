@@ -55,7 +55,7 @@
 // REF: y-hat of a triple is exp_project_dual / pow_project_dual_of_entry from the cold start exp_dual_eig / pow_dual_eig evaluate at -- the same decision, the
 // rule of ns_soc_kind.  W and lambda live behind the index arrays in LDS (ns_layout's TRI mode).
 //
-// PSD = true (with FWD, REF or not, or with MANY, FWD or not -- below; never QP or TRI): PSD blocks beside the plain cones (cone_engine.hip ce_jvp_psd, ce_refine_psd: entry points of their own, ce_jvp
+// PSD = true (with FWD, REF or not, or with MANY, FWD or not -- below; never QP; with TRI: the last paragraph of this list): PSD blocks beside the plain cones (cone_engine.hip ce_jvp_psd, ce_refine_psd: entry points of their own, ce_jvp
 // and ce_refine keep refusing such templates).  smat(v_c) = U Lambda U^T by the workgroup's Jacobi sweeps (ce_psd_jacobi.h); in the basis E_ab = svec(sym(u_a u_b^T))
 // D Pi is diagonal with eigenvalue B_ab (1 / 0 / l+ / (l+ - l-), k_backward_rt's comparisons, no snap).  The block's rows of A are rotated in place,
 // a~ = svec(U^T smat(a) U) per column, gamma = Q^T g_y with them; afterwards a rotated row is an equality, a dropped row or ONE weighted row of the list, exactly a
@@ -99,6 +99,14 @@
 // boundary convention).  It is the one adjoint with PSD blocks this kernel has.  Flags belong to the matrix: a vanishing pivot, neq > n or a weighted PSD row with
 // 1 - B < NS_TRI_STIFF flag the instance for every k and it is listed once -- the threshold is carried over AGAIN (the triples' forward law -> the triples' adjoint ->
 // PSD rows, in both directions): not measured on PSD rows, not measured for an adjoint.  A flagged instance runs to the same barriers as any other.
+// TRI and PSD together (never QP; FWD, FWD + REF, MANY, FWD + MANY -- cone_engine.hip ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many; a
+// single-cotangent adjoint stays k_backward_rt's): a template with PSD blocks AND triples (log_det: one block beside one exponential cone per diagonal entry).  The rows
+// are z, l, q, then the blocks' (psd0 .. T.eoff - 1), then the triples' (T.eoff .. m - 1), and every phase of either kind above is a branch of its own on its own rows:
+// the mixed kind runs both, in sequence -- each triple's D Pi diagonalised, snapped, its rows rotated; each block decomposed and its rows rotated; both kinds' weighted
+// rows numbered behind the boundary cones' (the triples' first, then the blocks': each pass reads misc[3] behind the other's barrier; at most m entries together);
+// steps 1-4; both epilogues and both rotations back.  MANY: per right-hand side both gamma_c = W^T g per triple and gamma = Q^T g per block.  REF: y-hat of a triple
+// from its cold-start decision and y-hat of a block from its decomposition inside one acceptance test, with the PSD kind's shortened steps.  NS_TRI_STIFF flags from
+// either kind's weighted rows (carried over once more).  The segments are ns_layout's with both counts: Wt, lamt, then psdU .. psdXW (psd_tri_ns_variant, psd_tri_ns_lds).
 //
 // Plain cones (zero / nonnegative / second-order), with TRI exponential / power triples in the forward modes (one tangent or many) and in the many-cotangent adjoint.  PSD blocks in the forward
 // derivative, the refinement, and the two many-modes with PSD.  The SINGLE-cotangent adjoint of PSD templates keeps k_backward_rt, and so do the single-cotangent adjoint
@@ -151,6 +159,10 @@ template <> struct NsFwdArg<true, false, false, false, false, true> { typedef Ns
 template <> struct NsFwdArg<true, true, false, false, false, true> { typedef NsRefinePsd type; };
 template <> struct NsFwdArg<false, false, false, false, true, true> { typedef NsVjpManyPsd type; };
 template <> struct NsFwdArg<true, false, false, false, true, true> { typedef NsJvpManyPsd type; };
+template <> struct NsFwdArg<true, false, false, true, false, true> { typedef NsJvpPsdTri type; };
+template <> struct NsFwdArg<true, true, false, true, false, true> { typedef NsRefinePsdTri type; };
+template <> struct NsFwdArg<false, false, false, true, true, true> { typedef NsVjpManyPsdTri type; };
+template <> struct NsFwdArg<true, false, false, true, true, true> { typedef NsJvpManyPsdTri type; };
 
 // (QP: 20 KB more LDS at the config-2 shape -- two workgroups per CU, and the registers that go with two; TRI: the triples' eigen-decompositions are calls with
 // frames of their own, planned for two as well; PSD: the block's segments on top of A leave room for two at the shapes it serves)
@@ -164,12 +176,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     static_assert((FWD && !QP) || (!FWD && !REF && !QP && MANY) || !TRI,
                   "exponential / power triples: the forward modes with a linear objective (one tangent, many tangents, refinement), and the many-cotangent adjoint "
                   "with one (their single-cotangent adjoint lives in k_backward_rt)");
-    static_assert(!MANY || (!FWD && !REF && !(TRI && QP) && !(PSD && (QP || TRI))) || (FWD && !REF && !(TRI && QP) && !(PSD && (QP || TRI))),
+    static_assert(!MANY || (!FWD && !REF && !(TRI && QP) && !(PSD && QP)) || (FWD && !REF && !(TRI && QP) && !(PSD && QP)),
                   "many right-hand sides on one factorisation: the adjoint (K cotangents) or the forward derivative (K tangents), each with plain cones, P or not, or "
-                  "with triples and a linear objective, or with PSD blocks and a linear objective; never the refinement, never triples or PSD blocks with P, never both");
-    static_assert(!PSD || (!QP && !TRI && ((FWD && !MANY) || (MANY && !REF))),
-                  "PSD blocks: the forward derivative and the refinement on one right-hand side, K tangents and K cotangents on one factorisation; linear objective, no "
-                  "triple beside them (their single-cotangent adjoint lives in k_backward_rt)");
+                  "with triples, PSD blocks or both and a linear objective; never the refinement, never triples or PSD blocks with P");
+    static_assert(!PSD || (!QP && ((FWD && !MANY) || (MANY && !REF))),
+                  "PSD blocks, triples beside them or not: the forward derivative and the refinement on one right-hand side, K tangents and K cotangents on one "
+                  "factorisation; linear objective (their single-cotangent adjoint lives in k_backward_rt)");
     extern __shared__ __attribute__((aligned(16))) double sm[];
     constexpr int NWB = NTHR / 64, LDP = bwd_ns_ldp(NTILE), NSL = bwd_ns_nsl(NTILE), NCOLP = 64 * NSL, PUBP = NCOLP + 2;
     constexpr int NLOC = (16 * NTILE - 4 + NWB - 1) / NWB;          // equality rows per wave (rows are dealt cyclically to the waves)
@@ -228,9 +240,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
         ip += (ip - (int *)sm) & 1;
         Wt = (double *)ip;           // per triple: W (row-major 3 x 3, eigenvectors in the columns) of D Pi_K*(v)
         lamt = Wt + 9 * ntri;        // per rotated triple row: its eigenvalue after the snap
+        if constexpr (PSD) ip = (int *)(lamt + 3 * ntri);          // (both kinds: the blocks' segments follow the triples', ns_layout's order)
     }
     // PSD: per block U and Lambda of smat(v_c), per rotated row its eigenvalue B of D Pi, the Jacobi scratch and one (X, W) pair per wave for the rotations (ns_layout's
-    // PSD mode: nothing here aliases the union region).  The blocks' rows are psd0 .. T.eoff - 1 (no triple follows them in this mode).
+    // PSD mode: nothing here aliases the union region).  The blocks' rows are psd0 .. T.eoff - 1; with TRI the triples' rows follow them, T.eoff .. m - 1.
     const int psd0 = PSD ? T.soff[0] : 0, msq = PSD ? T.maxs * T.maxs : 0;
     double *psdU = nullptr, *psdEv = nullptr, *lamp = nullptr, *psdScr = nullptr, *psdXW = nullptr;
     if constexpr (PSD) {

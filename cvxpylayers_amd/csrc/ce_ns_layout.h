@@ -73,7 +73,8 @@ struct NsLayout {
 };
 
 // the modes of the layout: the plain one, the one with the dense P behind the ints (qp), the one with the triples' segments there (ntri > 0 triples; never with qp),
-// and the one with the PSD blocks' segments there (ns > 0 blocks of order <= maxs that own psdrows rows together; never with qp or triples)
+// the one with the PSD blocks' segments there (ns > 0 blocks of order <= maxs that own psdrows rows together; never with qp), and the one with both cone kinds
+// (ntri > 0 and ns > 0: the triples' two segments, then the blocks' five, no segment of its own)
 __host__ __device__ constexpr NsLayout ns_layout(int n, int m, int nq, int NTILE, int NTHR, bool qp, int ntri = 0, int ns = 0, int maxs = 0, int psdrows = 0) {
     const int nqs = nq > 0 ? nq : 1, npad = n + (n & 1), kw = bwd_ns_kwmax(m), nwb = NTHR / 64;
     NsLayout L{};
@@ -148,3 +149,4 @@ __host__ __device__ constexpr size_t bwd_ns_lds_bytes_of(int n, int m, int nq, i
 __host__ __device__ constexpr size_t bwd_ns_qp_lds_bytes_of(int n, int m, int nq, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, true).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_tri_lds_bytes_of(int n, int m, int nq, int ntri, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, ntri).bytes; }
 __host__ __device__ constexpr size_t bwd_ns_psd_lds_bytes_of(int n, int m, int nq, int ns, int maxs, int psdrows, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, 0, ns, maxs, psdrows).bytes; }
+__host__ __device__ constexpr size_t bwd_ns_psd_tri_lds_bytes_of(int n, int m, int nq, int ntri, int ns, int maxs, int psdrows, int NTILE, int NTHR) { return ns_layout(n, m, nq, NTILE, NTHR, false, ntri, ns, maxs, psdrows).bytes; }

@@ -49,6 +49,7 @@ struct CePlan {
     int qp_ns_variant = -1; size_t qp_ns_lds = 0;  // row of CE_NS_VARIANTS with the QP footprint: forward derivative and refinement of a qp_native template (-1: none)
     int tri_ns_variant = -1; size_t tri_ns_lds = 0;      // row of CE_NS_VARIANTS with the TRI footprint: forward derivative and refinement of a template with exponential / power triples (-1: none)
     int psd_ns_variant = -1; size_t psd_ns_lds = 0;      // row of CE_NS_VARIANTS with the PSD footprint: the opt-in forward derivative and refinement of a template with PSD blocks (ce_jvp_psd, ce_refine_psd; -1: none)
+    int psd_tri_ns_variant = -1; size_t psd_tri_ns_lds = 0;      // row of CE_NS_VARIANTS with both kinds' segments: the opt-in modes of a template with PSD blocks AND triples (ce_jvp_psd_tri, ...; -1: none)
 };
 
 #ifdef CE_TIMING
@@ -105,7 +106,8 @@ static bool resolve_lds_fits(const DevT &T, int psd_first) {
 // -1: none.  *lds: its footprint
 static int ns_first_fit(const DevT &T, bool qp, size_t *lds, int ntri = 0, int psdrows = 0) {      // (ntri > 0: the layout's TRI mode, the triples' W and lambda on top;
     for (int v = 0; v < (int)std::size(NS_ROWS); v++) {                                               //  psdrows > 0: its PSD mode, the rows the T.ns blocks own together)
-        const size_t by = psdrows > 0 ? bwd_ns_psd_lds_bytes_of(T.n, T.m, T.nq, T.ns, T.maxs, psdrows, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
+        const size_t by = (psdrows > 0 && ntri > 0) ? bwd_ns_psd_tri_lds_bytes_of(T.n, T.m, T.nq, ntri, T.ns, T.maxs, psdrows, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)      // (both counts: both kinds' segments)
+                        : psdrows > 0 ? bwd_ns_psd_lds_bytes_of(T.n, T.m, T.nq, T.ns, T.maxs, psdrows, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
                         : ntri > 0 ? bwd_ns_tri_lds_bytes_of(T.n, T.m, T.nq, ntri, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR)
                         : qp ? bwd_ns_qp_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR) : bwd_ns_lds_bytes_of(T.n, T.m, T.nq, NS_ROWS[v].NTILE, NS_ROWS[v].NTHR);
         if (4 * ((T.n + 3) / 4) + 1 <= 16 * NS_ROWS[v].NTILE && by <= LDS_LIMIT) { *lds = by; return v; }
@@ -269,6 +271,14 @@ static int plan_engine(const ce_template *tpl, const DevT &T, int nnz_p, const P
         int psdrows = 0;
         for (int c = 0; c < tpl->ns; c++) psdrows += tpl->s[c] * (tpl->s[c] + 1) / 2;
         if (resolve_lds_fits(T, T.eoff - psdrows)) P.psd_ns_variant = ns_first_fit(T, false, &P.psd_ns_lds, 0, psdrows);
+    }
+    // And with BOTH, PSD blocks and triples beside the plain cones (k_backward_ns<..., TRI, ..., PSD>): the forward derivative, the refinement and the two
+    // many-modes behind entry points of their own (ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many), linear objective, planned on the
+    // footprint with both kinds' segments -- when the LSQR vectors of the re-solve fit LDS too.  The four fields above stay -1 for such a template.
+    if (T.ns > 0 && T.nep + T.np > 0 && nnz_p == 0 && !E.ns_off && !E.force_generic) {
+        int psdrows = 0;
+        for (int c = 0; c < tpl->ns; c++) psdrows += tpl->s[c] * (tpl->s[c] + 1) / 2;
+        if (resolve_lds_fits(T, T.eoff - psdrows)) P.psd_tri_ns_variant = ns_first_fit(T, false, &P.psd_tri_ns_lds, T.nep + T.np, psdrows);
     }
     return CE_OK;
 }

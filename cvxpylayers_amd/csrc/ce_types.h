@@ -112,6 +112,14 @@ struct NsJvpManyTri : NsJvpMany {};
 // (tests/test_psd_many_args.py pins the names)
 struct NsVjpManyPsd : NsMany {};
 struct NsJvpManyPsd : NsJvpMany {};
+// k_backward_ns<..., TRI = true, ..., PSD = true>: PSD blocks AND exponential / power triples beside the plain cones, in the four modes the kernel has for the mixed
+// kind (cone_engine.hip ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many).  The arguments of the PSD siblings (both cone kinds are
+// described by DevT); types of their own select the launchers.  The two many-modes' names do not end in "Many", for NsJvpManyTri's reason: their edge ledger
+// lives in tests/test_gpu_psd_tri_edges.py
+struct NsJvpPsdTri : NsJvp {};
+struct NsRefinePsdTri : NsRefine {};
+struct NsVjpManyPsdTri : NsMany {};
+struct NsJvpManyPsdTri : NsJvpMany {};
 
 // ---- shared-A kernels (ce_shared_a_fwd.h, ce_shared_a.h, ce_shared_a_ops.h): what the host hands their launchers ----
 // fields the product routines read (SaFwd and SaSplit both carry them):
@@ -268,6 +276,10 @@ int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefinePsd &w);          //  with PSD blocks)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpManyPsd &w);         // (ce_tu_ns_vjp_psd_many.hip: the adjoint with PSD blocks for K cotangents)
 int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyPsd &w);         // (ce_tu_ns_jvp_psd_many.hip: the forward derivative with PSD blocks for K tangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpPsdTri &w);          // (ce_tu_ns_psd_tri.hip: the forward derivative and the refinement
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefinePsdTri &w);       //  with PSD blocks and triples)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsVjpManyPsdTri &w);      // (ce_tu_ns_vjp_psd_tri_many.hip: the adjoint with both for K cotangents)
+int ce_launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpManyPsdTri &w);      // (ce_tu_ns_jvp_psd_tri_many.hip: the forward derivative with both for K tangents)
 int ce_launch_bwd_rt_psd(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_bwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 int ce_launch_sa_fwd(int variant, int B, size_t lds, hipStream_t st, const CeSaFwdArgs &a);     // row of CE_SA_FWD_VARIANTS (its thread count is the row's)
@@ -311,6 +323,9 @@ hipError_t ce_setattr_ns_jvp_tri_many(int bytes);
 hipError_t ce_setattr_ns_psd(int bytes);
 hipError_t ce_setattr_ns_vjp_psd_many(int bytes);
 hipError_t ce_setattr_ns_jvp_psd_many(int bytes);
+hipError_t ce_setattr_ns_psd_tri(int bytes);
+hipError_t ce_setattr_ns_vjp_psd_tri_many(int bytes);
+hipError_t ce_setattr_ns_jvp_psd_tri_many(int bytes);
 hipError_t ce_setattr_bwd_generic(int bytes);
 hipError_t ce_setattr_sa_fwd(int bytes);
 hipError_t ce_setattr_sa_lsqr(int bytes);

@@ -264,7 +264,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     if (h.plan.qp_native) { HIPCHK(h.d_idx_p.upload(G.ip)); HIPCHK(h.d_pmap.upload(G.pmap)); HIPCHK(h.d_prow.upload(h.p_rows)); HIPCHK(h.d_pcol.upload(h.p_cols)); }
     HIPCHK(ce_setattr_fwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd_rt((int)LDS_LIMIT));
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
-    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_many((int)LDS_LIMIT));
+    HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_tri_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     return CE_OK;
 }
@@ -331,6 +331,12 @@ int ce_jvp_tri_many_variant(ce_handle h) { return (h && h->plan.tri_ns_variant >
 // that the LSQR vectors of the re-solve fit LDS; the rotation of a right-hand side lives in the (X, W) pairs the single-tangent mode rotates A on)
 int ce_vjp_psd_many_variant(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? h->plan.psd_ns_variant : -1; }
 int ce_jvp_psd_many_variant(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? h->plan.psd_ns_variant : -1; }
+// a template with PSD blocks AND triples: one row and footprint (both kinds' segments) for its four modes; the planner already asks that the LSQR vectors of the
+// re-solve fit LDS
+int ce_psd_tri_ns_variant(ce_handle h) { return h ? h->plan.psd_tri_ns_variant : -1; }
+long ce_psd_tri_ns_lds(ce_handle h) { return (h && h->plan.psd_tri_ns_variant >= 0) ? (long)h->plan.psd_tri_ns_lds : 0; }
+int ce_vjp_psd_tri_many_variant(ce_handle h) { return (h && h->plan.psd_tri_ns_variant >= 0) ? h->plan.psd_tri_ns_variant : -1; }
+int ce_jvp_psd_tri_many_variant(ce_handle h) { return (h && h->plan.psd_tri_ns_variant >= 0) ? h->plan.psd_tri_ns_variant : -1; }
 int ce_set_adjoint_resolve(ce_handle h, int enable, double atol, double btol, double conlim, int iter_lim) {
     if (!h) { g_err = "null argument"; return CE_E_BADARG; }
     h->resolve = enable != 0;
@@ -606,7 +612,7 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 // Without an armed re-solve (q_vals == NULL, ce_set_adjoint_resolve(h, 0)) ce_vjp itself does not run the elimination: K calls of it then, the same rule.
 // (kind NS_MANY_TRI: ce_vjp_tri_many -- the same body on the triples' variant and footprint; NS_MANY_PSD: ce_vjp_psd_many -- on the PSD blocks'; `who` names the
 // entry point in the messages)
-enum NsManyKind { NS_MANY_PLAIN = 0, NS_MANY_TRI = 1, NS_MANY_PSD = 2 };
+enum NsManyKind { NS_MANY_PLAIN = 0, NS_MANY_TRI = 1, NS_MANY_PSD = 2, NS_MANY_PSD_TRI = 3 };          // (NS_MANY_PSD_TRI: ce_vjp_psd_tri_many / ce_jvp_psd_tri_many -- on the row with both kinds' segments)
 static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                         const double *x, const double *y, const double *s, const double *dx, const double *dy,
                         double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
@@ -639,7 +645,8 @@ static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, in
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
     ba.adj = adj_status; ba.fix = fix.cur;
     h->last_fast = -1;
-    if (kind == NS_MANY_PSD ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsVjpManyPsd{W})
+    if (kind == NS_MANY_PSD_TRI ? ce_launch_ns(P.psd_tri_ns_variant, B, P.psd_tri_ns_lds, st, ba, NsVjpManyPsdTri{W})
+        : kind == NS_MANY_PSD ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsVjpManyPsd{W})
         : kind == NS_MANY_TRI ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsVjpTriMany{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) {
         g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG;
     }
@@ -690,6 +697,19 @@ int ce_vjp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
         return CE_E_UNSUPPORTED;
     }
     return vjp_many_run(h, NS_MANY_PSD, "ce_vjp_psd_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+}
+// K cotangents at one solution of a template with PSD blocks AND exponential / power triples (include/cone_engine.h): ce_vjp_many's body with
+// k_backward_ns<..., TRI, MANY, PSD> on the variant and footprint with both kinds' segments.  Without an armed re-solve K calls of ce_vjp.
+int ce_vjp_psd_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                        const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                        double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_psd_tri_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    if (ce_vjp_psd_tri_many_variant(h) < 0) {
+        g_err = "ce_vjp_psd_tri_many: this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, "
+                "has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); call ce_vjp once per cotangent";
+        return CE_E_UNSUPPORTED;
+    }
+    return vjp_many_run(h, NS_MANY_PSD_TRI, "ce_vjp_psd_tri_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
 }
 
 // summary of an int32 vector v[B] (status of a forward call, or adj_status of a backward call): out[0] = min v, out[1] = #{v == 2} ("solved,
@@ -1171,23 +1191,25 @@ static int qp_ns_check(ce_handle h, const char *who) {
 // re-solves the instances it listed as rank deficient -- the same re-solve list.  With P_vals (ce_jvp_qp: k_backward_ns<..., FWD, QP>) one launch and no re-solve list: no LSQR has a P term.
 static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
-                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false) {
+                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false, bool psd_tri = false) {          // (psd_tri: ce_jvp_psd_tri -- PSD blocks and triples, the row with both kinds' segments)
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_jvp_qp" : (psd ? "ce_jvp_psd" : "ce_jvp");
+    const std::string who = qp ? "ce_jvp_qp" : (psd_tri ? "ce_jvp_psd_tri" : (psd ? "ce_jvp_psd" : "ce_jvp"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     int rc = CE_OK;
     if (qp) { rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc; }
-    else if (psd) {      // (the opt-in entry point of PSD templates: ce_jvp itself keeps refusing them)
+    else if (psd_tri) {  // (the opt-in entry point of templates with PSD blocks and triples: ce_jvp and ce_jvp_psd keep refusing them)
+        if (P.psd_tri_ns_variant < 0) { g_err = "ce_jvp_psd_tri: this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
+    } else if (psd) {      // (the opt-in entry point of PSD templates: ce_jvp itself keeps refusing them)
         if (P.psd_ns_variant < 0) { g_err = "ce_jvp_psd: this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
     } else {
         if (P.qp_native) { g_err = "forward derivative: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
         if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_jvp: this template has no search-free elimination (PSD / exponential / power cones, or n > 108); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
         if (!resolve_fits(h)) { g_err = "ce_jvp: the LSQR vectors of the re-solve exceed LDS; use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
     }
-    const bool tri = !qp && !psd && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, TRI> on its own footprint, the same re-solve list behind it
-    const int variant = qp ? P.qp_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant));
-    const size_t lds = qp ? P.qp_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds));
+    const bool tri = !qp && !psd && !psd_tri && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, TRI> on its own footprint, the same re-solve list behind it
+    const int variant = qp ? P.qp_ns_variant : (psd_tri ? P.psd_tri_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant)));
+    const size_t lds = qp ? P.qp_ns_lds : (psd_tri ? P.psd_tri_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds)));
     if (B > 1 && (sA_b != T.nnz_aug || (tA_vals_bm && stA_b != T.nnz_aug))) { g_err = who + ": A_vals_bm and tA_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1198,6 +1220,7 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
     const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
+                  : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsdTri{W})
                   : psd ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsd{W})
                   : tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
     if (lrc) { g_err = "internal: no forward elimination kernel for the planned variant"; return CE_E_BADARG; }
@@ -1223,6 +1246,12 @@ int ce_jvp_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const dou
     if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream, true);
 }
+int ce_jvp_psd_tri(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "ce_jvp_psd_tri: null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream, false, true);
+}
 int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
               const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
               double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
@@ -1237,13 +1266,14 @@ static int jvp_many_ns(ce_handle h, NsManyKind kind, int B, int K, const double 
                        const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                        const double *tP_vals, long stP_k, long stP_b, double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
                        double atol, double btol, double conlim, int iter_lim, void *stream) {
-    const bool qp = P_vals != nullptr, tri = kind == NS_MANY_TRI, psd = kind == NS_MANY_PSD;
-    const std::string who = qp ? "ce_jvp_qp_many" : (psd ? "ce_jvp_psd_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many"));
+    const bool qp = P_vals != nullptr, tri = kind == NS_MANY_TRI, psd = kind == NS_MANY_PSD, psd_tri = kind == NS_MANY_PSD_TRI;
+    const std::string who = qp ? "ce_jvp_qp_many" : (psd_tri ? "ce_jvp_psd_tri_many" : (psd ? "ce_jvp_psd_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many")));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (qp) { const int rc = qp_ns_check(h, "ce_jvp_qp_many"); if (rc) return rc; }
-    if ((qp ? ce_jvp_qp_many_variant(h) : (psd ? ce_jvp_psd_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h)))) < 0) {
+    if ((qp ? ce_jvp_qp_many_variant(h) : psd_tri ? ce_jvp_psd_tri_many_variant(h) : (psd ? ce_jvp_psd_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h)))) < 0) {
         g_err = who + (qp ? ": this template has no many-tangent elimination with a quadratic objective; call ce_jvp_qp once per tangent"
+                       : psd_tri ? ": this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); call ce_jvp_lsqr once per tangent"
                        : psd ? ": this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its "
                                "footprint exceeds LDS, or CE_BWD_NS=0); call ce_jvp_lsqr once per tangent"
                        : tri ? ": this template has no search-free elimination with triples (no exponential / power cone, PSD cones, a quadratic objective inside the "
@@ -1269,6 +1299,7 @@ static int jvp_many_ns(ce_handle h, NsManyKind kind, int B, int K, const double 
     const NsJvpMany W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), K, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b,
                       dx, dy, ds, sxk, syk, sak, lsqr_iters};
     const int lrc = qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
+                       : psd_tri ? ce_launch_ns(P.psd_tri_ns_variant, B, P.psd_tri_ns_lds, st, ba, NsJvpManyPsdTri{W})
                        : psd ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsJvpManyPsd{W})
                        : tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsJvpManyTri{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
     if (lrc) { g_err = "internal: no many-tangent kernel for the planned variant"; return CE_E_BADARG; }
@@ -1315,6 +1346,17 @@ int ce_jvp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
         g_err = "ce_jvp_psd_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
     }
     return jvp_many_ns(h, NS_MANY_PSD, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+                       atol, btol, conlim, iter_lim, stream);
+}
+// K tangents at one solution of a template with PSD blocks AND triples (include/cone_engine.h): ce_jvp_many's body with k_backward_ns<..., FWD, ..., TRI, MANY, PSD> on
+// the variant and footprint with both kinds' segments; the re-solve behind it is the same one launch.  Refusals come before any device call.
+int ce_jvp_psd_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                        const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                        double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
+        g_err = "ce_jvp_psd_tri_many: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    return jvp_many_ns(h, NS_MANY_PSD_TRI, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
                        atol, btol, conlim, iter_lim, stream);
 }
 int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
@@ -1364,21 +1406,23 @@ int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
 static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
-                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false) {
+                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false, bool psd_tri = false) {
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_refine_qp" : (psd ? "ce_refine_psd" : "ce_refine");
+    const std::string who = qp ? "ce_refine_qp" : (psd_tri ? "ce_refine_psd_tri" : (psd ? "ce_refine_psd" : "ce_refine"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (qp) { const int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc; }
-    else if (psd) {      // (the opt-in entry point of PSD templates: ce_refine itself keeps refusing them)
+    else if (psd_tri) {  // (the opt-in entry point of templates with PSD blocks and triples: ce_refine and ce_refine_psd keep refusing them)
+        if (P.psd_tri_ns_variant < 0) { g_err = "ce_refine_psd_tri: this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
+    } else if (psd) {      // (the opt-in entry point of PSD templates: ce_refine itself keeps refusing them)
         if (P.psd_ns_variant < 0) { g_err = "ce_refine_psd: this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
     } else {
         if (P.qp_native) { g_err = "ce_refine: not available with a quadratic objective inside the kernels; use the epigraph form (cone form) of the problem"; return CE_E_UNSUPPORTED; }
         if (P.ns_variant < 0 && P.tri_ns_variant < 0) { g_err = "ce_refine: this template has no search-free elimination (PSD / exponential / power cones, or n > 108)"; return CE_E_UNSUPPORTED; }
     }
-    const bool tri = !qp && !psd && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, REF, TRI>
-    const int variant = qp ? P.qp_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant));
-    const size_t lds = qp ? P.qp_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds));
+    const bool tri = !qp && !psd && !psd_tri && P.ns_variant < 0;      // exponential / power triples: k_backward_ns<..., FWD, REF, TRI>
+    const int variant = qp ? P.qp_ns_variant : (psd_tri ? P.psd_tri_ns_variant : (psd ? P.psd_ns_variant : (tri ? P.tri_ns_variant : P.ns_variant)));
+    const size_t lds = qp ? P.qp_ns_lds : (psd_tri ? P.psd_tri_ns_lds : (psd ? P.psd_ns_lds : (tri ? P.tri_ns_lds : P.ns_lds)));
     if (B > 1 && sA_b != T.nnz_aug) { g_err = who + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1388,6 +1432,7 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
         const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
+                      : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsdTri{W})
                       : psd ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsd{W})
                       : tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefineTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
         if (lrc) { g_err = "internal: no refinement kernel for the planned variant"; return CE_E_BADARG; }
@@ -1404,6 +1449,11 @@ int ce_refine_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
                   const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_psd: null argument or negative step count"; return CE_E_BADARG; }
     return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream, true);
+}
+int ce_refine_psd_tri(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+                      const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_psd_tri: null argument or negative step count"; return CE_E_BADARG; }
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream, false, true);
 }
 int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
                  const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {

@@ -85,6 +85,7 @@ class ConeEngine:
         _lib.check(rc, "ce_create")
         self._h = h
         self.qp_native = bool(self.nnz_p) and bool(L.ce_qp_native(h))     # P runs inside the kernels (else: epigraph form upstream)
+        self.psd_tri_ns_variant = int(L.ce_psd_tri_ns_variant(h))         # >= 0: PSD blocks AND triples -- the psd_ns / psd_many flags below call the ce_*_psd_tri* entries on this template
         self.psd_ns_variant = int(L.ce_psd_ns_variant(h))                 # >= 0: ce_jvp_psd / ce_refine_psd serve this template (solver_args psd_elimination)
         a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()          # fixed by ce_create (plan_engine)
         L.ce_get_launch_info(h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -375,7 +376,8 @@ class ConeEngine:
         (a pivot search there, the stiff-row rule here; a flagged instance gets LSQR's minimum-norm answer) -- hence opt-in.  In every other case the flag changes nothing.
         psd_many (opt-in, default False): on a template with PSD blocks (ce_vjp_psd_many_variant >= 0), under tri_many's conditions, one ce_vjp_psd_many call instead
         of the K ce_vjp calls of the pivoting kernel (last_vjp_kernel == "ce_vjp_psd_many"): each block is decomposed and its rows rotated once per instance.  The
-        same caveat on flags (the stiff-row rule, carried over to PSD rows); in every other case the flag changes nothing."""
+        same caveat on flags (the stiff-row rule, carried over to PSD rows); in every other case the flag changes nothing.  On a template with PSD blocks AND
+        triples (ce_vjp_psd_tri_many_variant >= 0) the flag makes the one call ce_vjp_psd_tri_many (last_vjp_kernel names it)."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
@@ -386,10 +388,11 @@ class ConeEngine:
         many_tri = (not force_loop and tri_many and not many and path == "per_instance" and q_eval is not None and P_bm is None
                     and _lib.lib().ce_vjp_tri_many_variant(self._h) >= 0)
         many_psd = (not force_loop and psd_many and not many and not many_tri and path == "per_instance" and q_eval is not None and P_bm is None
-                    and _lib.lib().ce_vjp_psd_many_variant(self._h) >= 0)
+                    and (_lib.lib().ce_vjp_psd_many_variant(self._h) >= 0 or _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0))
+        mixed = many_psd and _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0          # (PSD blocks and triples: the mixed entry, the same arguments)
         self.last_vjp_many_path = "many" if (many or many_qp or many_tri or many_psd) else "loop"
         self.last_vjp_kernel = ("ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else ("ce_vjp_tri_many" if many_tri else
-                                                                                             ("ce_vjp_psd_many" if many_psd else None))))
+                                                                                             (("ce_vjp_psd_tri_many" if mixed else "ce_vjp_psd_many") if many_psd else None))))
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
             return out + ((torch.empty((K, B, self.nnz_p), **f64),) if P_bm is not None else ())
@@ -421,7 +424,7 @@ class ConeEngine:
         dA = torch.empty((K, B, self.nnz_aug), **f64)
         dq = torch.empty((K, B, self.n + 1), **f64)
         adj = torch.empty((K, B), dtype=torch.int32, device=dev)
-        fn, name = ((_lib.lib().ce_vjp_psd_many, "ce_vjp_psd_many") if many_psd else
+        fn, name = ((_lib.lib().ce_vjp_psd_tri_many, "ce_vjp_psd_tri_many") if mixed else (_lib.lib().ce_vjp_psd_many, "ce_vjp_psd_many") if many_psd else
                     (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else (_lib.lib().ce_vjp_many, "ce_vjp_many"))
         rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
                 None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
@@ -483,7 +486,8 @@ class ConeEngine:
         P_bm (B, nnz_p): the quadratic objective of a qp_native engine, with its tangent tP_bm (or None: zero) -- method="direct" only: ce_jvp_qp, the same elimination
         with P inside and NO LSQR behind it (a flagged instance keeps the elimination's answer, status 4, 0 iterations); NotImplementedError under method="lsqr".
         psd_ns=True (with method="direct"): ce_jvp_psd in the place of ce_jvp -- the elimination with PSD blocks (psd_ns_plan()["psd_ns_variant"] >= 0), which
-        ce_jvp refuses; the same fall to the LSQR call where the library has none for the template.  Without it a PSD template runs the LSQR call, as ever."""
+        ce_jvp refuses; the same fall to the LSQR call where the library has none for the template.  Without it a PSD template runs the LSQR call, as ever.
+        On a template with PSD blocks AND triples (psd_tri_ns_variant >= 0) the flag calls ce_jvp_psd_tri, the elimination with both kinds."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
@@ -514,7 +518,8 @@ class ConeEngine:
                       float(atol), float(btol), float(conlim), int(lim), self._stream())
         rc = -2
         if method == "direct" and not shared:
-            direct, dname = (_lib.lib().ce_jvp_psd, "ce_jvp_psd") if psd_ns else (_lib.lib().ce_jvp, "ce_jvp")
+            direct, dname = (((_lib.lib().ce_jvp_psd_tri, "ce_jvp_psd_tri") if self.psd_tri_ns_variant >= 0 else (_lib.lib().ce_jvp_psd, "ce_jvp_psd")) if psd_ns
+                             else (_lib.lib().ce_jvp, "ce_jvp"))
             rc = call(direct, A_c if A_c.stride(0) == self.nnz_aug else A_c.contiguous())
             if rc != -2:          # (CE_E_UNSUPPORTED: no elimination for this template -- the LSQR call below serves it)
                 name = dname
@@ -542,7 +547,8 @@ class ConeEngine:
         psd_many (opt-in, default False): on a template with PSD blocks (ce_jvp_psd_many_variant >= 0), under tri_many's conditions, one ce_jvp_psd_many call
         (last_jvp_kernel == "ce_jvp_psd_many") instead of the K calls of the loop, which are ce_jvp_lsqr calls on such a template: each block is decomposed, its rows
         rotated and each instance factored once for all K tangents.  With force_loop the flag selects the loop's kernel instead: K ce_jvp_psd calls, the elimination
-        this mode repeats K times less -- its comparator.  In every other case the flag changes nothing."""
+        this mode repeats K times less -- its comparator.  In every other case the flag changes nothing.  On a template with PSD blocks AND triples
+        (ce_jvp_psd_tri_many_variant >= 0) the one call is ce_jvp_psd_tri_many and the loop under force_loop is K ce_jvp_psd_tri calls."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp_many: method must be 'lsqr' or 'direct', got {method!r}")
         given = [t for t in (tA, tq, tP) if t is not None]
@@ -562,8 +568,9 @@ class ConeEngine:
         many_tri = (not force_loop and tri_many and not many and method == "direct" and P_bm is None and path != "const_a"
                     and L.ce_jvp_tri_many_variant(self._h) >= 0)
         psd_ok = (psd_many and not many and not many_tri and method == "direct" and P_bm is None and path != "const_a"
-                  and L.ce_jvp_psd_many_variant(self._h) >= 0)
+                  and (L.ce_jvp_psd_many_variant(self._h) >= 0 or L.ce_jvp_psd_tri_many_variant(self._h) >= 0))
         many_psd = psd_ok and not force_loop
+        mixed = many_psd and L.ce_jvp_psd_tri_many_variant(self._h) >= 0          # (PSD blocks and triples: the mixed entry, the same arguments)
         many = many or many_tri or many_psd
         self.last_jvp_many_path = "many" if many else "loop"
         i32 = dict(dtype=torch.int32, device=dev)
@@ -601,7 +608,7 @@ class ConeEngine:
             if system == "reduced":
                 q_eval = None
             qd, q_args = self._q_args(q_eval)
-            fn, name = ((L.ce_jvp_psd_many, "ce_jvp_psd_many") if many_psd else
+            fn, name = ((L.ce_jvp_psd_tri_many, "ce_jvp_psd_tri_many") if mixed else (L.ce_jvp_psd_many, "ce_jvp_psd_many") if many_psd else
                         (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many, "ce_jvp_many"))
             rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
                     *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream())
@@ -664,6 +671,8 @@ class ConeEngine:
         if P_bm is not None:
             P_c = P_bm.detach().to(**f64).contiguous()
             rc, name = _lib.lib().ce_refine_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp"
+        elif psd_ns and self.psd_tri_ns_variant >= 0:          # (PSD blocks and triples: the mixed entry, the same arguments)
+            rc, name = _lib.lib().ce_refine_psd_tri(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine_psd_tri"
         elif psd_ns:
             rc, name = _lib.lib().ce_refine_psd(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine_psd"
         else:
@@ -794,6 +803,13 @@ class ConeEngine:
         buf = (C.c_int * cnt)()
         L.ce_get_plan(self._h, buf, cnt)
         return dict(zip(self.PLAN_FIELDS, list(buf)))
+
+    def psd_tri_ns_plan(self):
+        """The plan of the opt-in search-free elimination with PSD blocks AND exponential / power triples (ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many,
+        ce_jvp_psd_tri_many), which ce_get_plan and PLAN_FIELDS do not carry: "psd_tri_ns_variant" (row of CE_NS_VARIANTS, -1: the template is not served) and
+        "psd_tri_ns_lds" (its LDS footprint in bytes, 0: none)."""
+        L = _lib.lib()
+        return {"psd_tri_ns_variant": int(L.ce_psd_tri_ns_variant(self._h)), "psd_tri_ns_lds": int(L.ce_psd_tri_ns_lds(self._h))}
 
     def psd_ns_plan(self):
         """The plan of the opt-in search-free elimination with PSD blocks (ce_jvp_psd / ce_refine_psd), which ce_get_plan and PLAN_FIELDS do not carry:

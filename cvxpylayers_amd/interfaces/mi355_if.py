@@ -193,9 +193,10 @@ class _ConeLayer(torch.autograd.Function):
         tri_tan = tri_tangents(merged_args)       # (likewise; read by tangent_many alone)
         n_newton = newton_first(merged_args)
         has_psd = bool(len(eng.cone_dict.get("s", []) or []))
-        psd_ns = psd_elimination_active(psd_elimination(merged_args), eng.psd_ns_variant, has_psd)
-        psd_adj = psd_many_active("psd_adjoint", psd_adjoint(merged_args) == "search_free", eng.psd_ns_variant, has_psd)      # (read by adjoint_many alone)
-        psd_tan = psd_many_active("psd_tangents", psd_tangents(merged_args) == "many", eng.psd_ns_variant, has_psd)          # (read by tangent_many alone)
+        psd_row = max(eng.psd_ns_variant, eng.psd_tri_ns_variant)          # (at most one is set: triples beside the blocks -> the mixed entries, ConeEngine picks them)
+        psd_ns = psd_elimination_active(psd_elimination(merged_args), psd_row, has_psd)
+        psd_adj = psd_many_active("psd_adjoint", psd_adjoint(merged_args) == "search_free", psd_row, has_psd)      # (read by adjoint_many alone)
+        psd_tan = psd_many_active("psd_tangents", psd_tangents(merged_args) == "many", psd_row, has_psd)          # (read by tangent_many alone)
         warm = _resolve_warm_start(warm_start, merged_args, batch_size, eng)
         box = eng.mailbox
         with torch.cuda.device(dev):
@@ -340,7 +341,7 @@ class _ConeLayer(torch.autograd.Function):
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd") else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd", "ce_jvp_psd_tri") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod
@@ -418,7 +419,7 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
         dP = out[3] if saved.P_bm is not None else None
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
-            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many"):
+            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many", "ce_vjp_psd_tri_many"):
                 info["adjoint"]["path"] = eng.last_vjp_kernel
         if K > 0 and batch_size > 0:
             any_k = adj[0].clone()
@@ -462,7 +463,7 @@ def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=Non
                                          psd_many=saved.psd_tangents)
         if isinstance(info, dict):
             info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel,
-                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many", "ce_jvp_psd_many") else "lsqr"}
+                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many", "ce_jvp_psd_many", "ce_jvp_psd_tri", "ce_jvp_psd_tri_many") else "lsqr"}
     return dx, dy, failed
 
 

@@ -149,8 +149,9 @@ def psd_elimination(merged_args: dict) -> str:
     of D Pi, then the elimination of the plain cones):
     absent / "off" -> today's routes: forward-mode AD by LSQR whatever jvp_mode says, no refine_steps, no newton_first;
     "search_free" -> jvp_mode="direct" runs ce_jvp_psd (LSQR behind it for the instances it flags), refine_steps and newton_first are served by ce_refine_psd.
-    Opt-in: the flagging rule for stiff rows is the triples', not measured on PSD rows.  Templates the mode does not serve (no PSD block, triples or a quadratic
-    objective beside them, n > 108) ignore the key; psd_elimination_active says so once where the template has a PSD block."""
+    Opt-in: the flagging rule for stiff rows is the triples', not measured on PSD rows.  A template with exponential / power cones beside the blocks is served by
+    the mixed entries (ce_jvp_psd_tri, ce_refine_psd_tri) under the same key.  Templates the mode does not serve (no PSD block, a quadratic objective beside
+    them, n > 108) ignore the key; psd_elimination_active says so once where the template has a PSD block."""
     mode = str(merged_args.get("psd_elimination", "off"))
     if mode not in ("off", "search_free"):
         raise ValueError(f"MI355 solver: psd_elimination must be 'off' or 'search_free', got {mode!r}")
@@ -158,7 +159,8 @@ def psd_elimination(merged_args: dict) -> str:
 
 
 def psd_elimination_active(mode: str, psd_ns_variant: int, has_psd: bool) -> bool:
-    """True when this call runs the PSD elimination: the key asks for it and the engine serves the template (ConeEngine.psd_ns_variant >= 0).  A template with a
+    """True when this call runs the PSD elimination: the key asks for it and the engine serves the template (ConeEngine.psd_ns_variant >= 0, or
+    psd_tri_ns_variant >= 0 where triples stand beside the blocks: the caller passes the one that is set).  A template with a
     PSD block that is not served gets one notice; a template without one is silent (the key is inert there)."""
     if mode != "search_free":
         return False
@@ -166,7 +168,7 @@ def psd_elimination_active(mode: str, psd_ns_variant: int, has_psd: bool) -> boo
         return True
     if has_psd:
         _warn_once("psd_elimination_none", "MI355 solver: solver_args psd_elimination='search_free' is ignored on this template: the search-free elimination does not "
-                                           "serve it (exponential / power cones or a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
+                                           "serve it (a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
     return False
 
 
@@ -179,7 +181,8 @@ def psd_adjoint(merged_args: dict) -> str:
     weighted PSD row with 1 - B < 1e-5 flags too -- the triples' rule, carried over, not measured on PSD rows); a flagged instance gets LSQR's minimum-norm answer,
     hence opt-in.
     Independent of psd_elimination, which keeps its documented routes.  The single-cotangent backward of .backward() ignores the key: one cotangent belongs to
-    ce_vjp.  Templates the mode does not serve ignore it: psd_many_active says so once where the template has a PSD block."""
+    ce_vjp.  With exponential / power cones beside the blocks the one call is ce_vjp_psd_tri_many.  Templates the mode does not serve ignore it: psd_many_active
+    says so once where the template has a PSD block."""
     mode = str(merged_args.get("psd_adjoint", "pivoting"))
     if mode not in ("pivoting", "search_free"):
         raise ValueError(f"MI355 solver: psd_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
@@ -191,7 +194,8 @@ def psd_tangents(merged_args: dict) -> str:
     absent / "loop" -> K single-tangent calls (ce_jvp_lsqr on such a template, under psd_elimination="search_free" too);
     "many" -> one ce_jvp_psd_many call per chunk: each block decomposed, its rows rotated and each instance factored once for the whole chunk, and one LSQR launch
     for the flagged instances of every tangent (info["jvp"]["kernel"] tells which ran).  Opt-in: the flagging rule for stiff rows is the triples', carried over.
-    Independent of psd_elimination.  Forward-mode AD with one tangent ignores the key.  Templates the mode does not serve ignore it, as psd_adjoint."""
+    Independent of psd_elimination.  Forward-mode AD with one tangent ignores the key.  With exponential / power cones beside the blocks the one call is
+    ce_jvp_psd_tri_many.  Templates the mode does not serve ignore it, as psd_adjoint."""
     mode = str(merged_args.get("psd_tangents", "loop"))
     if mode not in ("loop", "many"):
         raise ValueError(f"MI355 solver: psd_tangents must be 'loop' or 'many', got {mode!r}")
@@ -200,15 +204,16 @@ def psd_tangents(merged_args: dict) -> str:
 
 def psd_many_active(key: str, asked: bool, psd_ns_variant: int, has_psd: bool) -> bool:
     """True when adjoint_many / tangent_many of this call take the many-right-hand-side mode with PSD blocks: `key` (psd_adjoint / psd_tangents) asks for it and
-    the engine serves the template (ConeEngine.psd_ns_variant >= 0: the modes run on that row).  A template with a PSD block that is not served gets one notice
+    the engine serves the template (ConeEngine.psd_ns_variant >= 0, or psd_tri_ns_variant >= 0 where triples stand beside the blocks: the modes run on that
+    row).  A template with a PSD block that is not served gets one notice
     per key; a template without one is silent (the key is inert there)."""
     if not asked:
         return False
     if psd_ns_variant >= 0:
         return True
     if has_psd:
-        _warn_once(key + "_none", f"MI355 solver: solver_args {key} is ignored on this template: the search-free elimination does not serve it (exponential / power "
-                                  "cones or a quadratic objective beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
+        _warn_once(key + "_none", f"MI355 solver: solver_args {key} is ignored on this template: the search-free elimination does not serve it (a quadratic objective "
+                                  "beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
     return False
 
 

@@ -470,7 +470,8 @@ class CvxpyLayer(torch.nn.Module):
         A template with PSD blocks runs the loop of K ce_vjp calls (the pivoting kernel, the blocks' decompositions with it) here by default; solver_args
         {"psd_adjoint": "search_free"} makes one ce_vjp_psd_many call per chunk instead (each block decomposed, its rows rotated and each instance factored once for
         the chunk; chunking by max_bytes is unchanged; info["adjoint"]["path"] == "ce_vjp_psd_many").  Opt-in for the triples' reason, with the triples' stiff-row
-        rule carried over to PSD rows; independent of psd_elimination; .backward() ignores the key.
+        rule carried over to PSD rows; independent of psd_elimination; .backward() ignores the key.  With exponential / power cones beside the blocks the one call
+        is ce_vjp_psd_tri_many (tri_adjoint stays inert there).
         Refused (NotImplementedError): gp=True layers, a quadratic objective that reaches the engine as a torch-op epigraph, solver_args `mode` of the LPGD family.
 
         direction="forward": the Jacobian by COLUMNS -- one plugin forward, then one tangent per parameter entry (the columns of the forward parameter maps of A, q
@@ -484,6 +485,7 @@ class CvxpyLayer(torch.nn.Module):
         info["jvp"]["path"] stays "direct"; chunking is unchanged).  Opt-in; forward-mode AD with one tangent ignores the key.  A template with PSD blocks runs K single-tangent calls
         here by default (ce_jvp_lsqr, under psd_elimination="search_free" too); solver_args {"psd_tangents": "many"} makes one ce_jvp_psd_many call per chunk instead
         (info["jvp"]["kernel"] == "ce_jvp_psd_many", info["jvp"]["path"] "direct"; chunking is unchanged).  Opt-in; one-tangent forward-mode AD ignores the key.
+        With exponential / power cones beside the blocks the one call is ce_jvp_psd_tri_many (tri_tangents stays inert there).
         direction="auto": forward when the parameter entries are fewer than the output elements, reverse otherwise.  (Named `direction`
         because solver_args["mode"] means something else.)  Any other value: ValueError, before anything touches the device."""
         from cvxpylayers_amd.interfaces.mi355_if import adjoint_many, tangent_many

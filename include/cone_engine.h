@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -659,6 +659,43 @@ int ce_jvp_psd_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_
                     double atol, double btol, double conlim, int iter_lim, void *stream);
 /* >= 0: the template has the many-tangent mode with PSD blocks; the value is ce_psd_ns_variant's row.  -1 otherwise, and for a NULL handle. */
 int ce_jvp_psd_many_variant(ce_handle h);
+
+/* PSD BLOCKS AND EXPONENTIAL / POWER TRIPLES IN ONE TEMPLATE (log_det and its kin: one PSD block beside one exponential cone per diagonal entry): the four
+ * search-free modes on a template with both cone kinds beside plain cones, linear objective.  Per instance the kernel does what the two kinds do on their own, in
+ * sequence: each triple's D Pi is diagonalised, snapped, and its three rows of A rotated; each block is Jacobi-decomposed and its rows rotated; every rotated row is
+ * an equality, a dropped row or one weighted row; steps 1-4; both epilogues, both rotations back (csrc/ce_backward_ns.h, TRI + PSD).  Entry points of their own, each
+ * with the arguments, layouts, strides, statuses and error rules of its PSD sibling:
+ *   ce_jvp_psd_tri       as ce_jvp_psd       (one tangent; flagged instances re-solved by LSQR behind it, status 4 | 8)
+ *   ce_refine_psd_tri    as ce_refine_psd    (safeguarded Newton steps, the PSD kind's shortened steps 1/2, 1/4, 1/8; y-hat of a triple from its cold-start decision
+ *                                             and y-hat of a block from its decomposition inside one acceptance test)
+ *   ce_vjp_psd_tri_many  as ce_vjp_psd_many  (K cotangents on one factorisation; per cotangent h = W^T dy_c per triple and h = Q^T dy_c per block)
+ *   ce_jvp_psd_tri_many  as ce_jvp_psd_many  (K tangents on one factorisation; per tangent gamma_c = W^T g_y,c per triple and gamma_c = Q^T g_y,c per block)
+ * Flags (status 4 | 8 behind the re-solve): a vanishing pivot, more active rows than variables, or a weighted triple OR PSD row with 1 - lambda < 1e-5 -- the forward
+ * derivative's measured rule for a stiff row of a triple, carried over again to the mixed kind: not measured on PSD rows, not measured for an adjoint.  A flagged
+ * instance is listed once, and in the many-modes ONE launch of the LSQR kernel serves all K right-hand sides.  The refinement flags no stiff row.
+ *   ce_psd_tri_ns_variant: the row of the kernel's variant list the four modes run on (>= 0: a PSD block and a triple, no quadratic objective, n <= 108, the footprint
+ * with both kinds' segments on top fits LDS, and the LSQR vectors of the re-solve fit LDS); -1: none, or h == NULL.  ce_psd_tri_ns_lds: that footprint in bytes
+ * (0 when there is none).  ce_vjp_psd_tri_many_variant / ce_jvp_psd_tri_many_variant: the same row, or -1.
+ *   CE_E_UNSUPPORTED with a ce_last_error that names the entry point and the reason when the variant is < 0; nothing is written then.  ce_jvp, ce_refine, ce_jvp_psd,
+ * ce_refine_psd, ce_vjp_many, ce_jvp_many, ce_vjp_tri_many, ce_jvp_tri_many, ce_vjp_psd_many and ce_jvp_psd_many keep refusing such templates; ce_get_plan keeps its
+ * 18 entries. */
+int ce_jvp_psd_tri(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_refine_psd_tri(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+                      const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream);
+int ce_vjp_psd_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                        const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                        double *dA_vals, double *dq_vals, int *adj_status, void *stream);
+int ce_jvp_psd_tri_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                        const double *x, const double *y, const double *s,
+                        const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                        double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
+                        double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_psd_tri_ns_variant(ce_handle h);
+long ce_psd_tri_ns_lds(ce_handle h);
+int ce_vjp_psd_tri_many_variant(ce_handle h);
+int ce_jvp_psd_tri_many_variant(ce_handle h);
 
 /* Introspection used by bench.py / tests: per-kernel HIP-event timing on the launch stream.  enable: 0 off, 1 every launch, or a sum of 2 (forward launches),
  * 4 (adjoint launches), 8 (layout passes) to bracket only those kinds (two event records per bracketed launch are host work in front of the launch). */
