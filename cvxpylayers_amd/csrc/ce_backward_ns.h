@@ -115,6 +115,7 @@
 #include "ce_common.h"
 #include "ce_expcone.h"            // TRI: exp_dual_eig, pow_dual_eig, exp_project_dual, pow_project_dual_of_entry
 #include "ce_psd_jacobi.h"         // PSD: psd_jacobi
+#include "ce_dA_entry.h"           // ce_dA_entry: the entry of the dA row, shared with k_expand_dA
 
 #include "ce_ns_layout.h"          // ns_layout: the LDS segments of this kernel and its footprint (what the launch plan and tests/test_ns_layout_host.py use); bwd_ns_ldp, bwd_ns_nsl,
                                    // bwd_ns_kwmax, bwd_ns_union_doubles.  The carve below is still the kernel's own statement of the same layout.
@@ -1935,6 +1936,15 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     NS_STAMP(9);
     // ---- outputs in the boundary convention: dA_eval = [-dA.data, db[b_idx]], dq_eval = [dc, 0]   (diffcp_if.py:91-92)
     double *const xs = fvec, *const ys = dv;
+    // factor mode (the single-cotangent adjoint alone, W.dA_factors: ce_vjp_qp asks for it when k_expand_dA writes the caller's batch-minor dA): every entry of the
+    // row is a product of x, y (the forward's outputs), r_x = -dq (written below) and r_y, so r_y[0 .. m) at the head of the instance's row is all the row needs;
+    // one contiguous store instead of nnz_aug.  The flag is the launch's: uniform, the barrier below is skipped by all threads or none.
+    bool factors = false;
+    if constexpr (!FWD && !MANY) factors = W.dA_factors != 0;
+    if (factors) {
+        double *const dArow = dAk + (size_t)inst * T.nnz_aug;
+        for (int i = tid; i < m; i += NTHR) dArow[i] = vv[i];
+    } else {
     for (int j = tid; j < n; j += NTHR) xs[j] = xg[(size_t)inst * n + j];
     for (int i = tid; i < m; i += NTHR) ys[i] = yg[(size_t)inst * m + i];
     __syncthreads();
@@ -1953,11 +1963,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < OU; u++) {
-                const double va = -(xv[u] * vi[u] - yi[u] * rv[u]);
+                const double va = ce_dA_entry(xv[u], vi[u], yi[u], rv[u]);
                 const double val = (jj[u] < n) ? va : -vi[u];
                 if (k0 + u * NTHR < nnz) dArow[k0 + u * NTHR] = val;
             }
         }
+    }
     }
     for (int j = tid; j <= n; j += NTHR) dqk[j * sdqk + inst * sdqb] = (j < n) ? -rx[j] : 0.0;
     if constexpr (QP && MANY && !FWD) {

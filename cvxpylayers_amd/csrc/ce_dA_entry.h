@@ -1,0 +1,8 @@
+// ce_dA_entry.h -- one entry of the adjoint's dA row in the boundary convention, stated once for the two kernels that evaluate it: k_backward_ns's batch-major
+// output loop (ce_backward_ns.h) and the batch-minor expansion from the factor vectors (k_expand_dA, ce_layout_kernels.h).  Both must produce the same bits.
+#pragma once
+
+// dA_eval[k] of the structural entry (i, j), j < n:  -(x_j r_y,i - y_i r_x,j).  Written out as one multiply and one fma so that no compiler decides the
+// contraction per kernel: t = y r, then fma(x, v, -t), then the sign -- the form the output loop compiled to before this header existed (fp-contract=fast:
+// v_mul_f64, v_fma_f64 with a negated addend, the sign folded into the select), so the values are unchanged.  The b column (j == n) is -v: the caller selects.
+__device__ __forceinline__ double ce_dA_entry(double x, double v, double y, double r) { return -fma(x, v, -(y * r)); }

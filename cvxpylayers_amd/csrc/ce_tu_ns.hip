@@ -32,7 +32,9 @@ namespace {
 namespace {
 // (a mode reads the fields of CeBwdArgs it needs; the host leaves the others null)
 template <bool FWD, bool REF, bool QP, bool TRI, class Args>
-int launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const Args &w) {
+int launch_ns(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const Args &w0) {
+    Args w = w0;
+    if constexpr (std::is_same<Args, NsNoJvp>::value) w.dA_factors = a.dA_factors;          // (the single-cotangent adjoint's factor mode: CeBwdArgs states it, the kernel reads its mode struct)
     switch (variant) {
 #define X(V, NTILE, NTHR) case V: hipLaunchKernelGGL((k_backward_ns<NTILE, NTHR, FWD, REF, QP, TRI>), dim3(B), dim3(NTHR), lds, st, a.T, a.Abm, a.x, a.y, a.s, a.dx, a.dy, a.dA, a.dq, a.sdqk, a.sdqb, a.adj, a.fix, w); return 0;
         CE_NS_VARIANTS(X)

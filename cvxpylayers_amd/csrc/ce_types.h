@@ -32,6 +32,8 @@ struct CeBwdArgs {
     int *fix;                   // fix[0]: counter, fix[1 ...]: instances whose adjoint system the elimination found rank deficient (or too large for the tile), appended
                                 // by the kernels for the LSQR re-solve behind them (cone_engine.hip ce_vjp_qp); NULL: not wanted
     int nonfinal;               // k_backward_rt: 1 = first launch of a two-tile plan (an instance this tile does not hold is not listed: the retry launch serves it)
+    int dA_factors;             // k_backward_ns, single-cotangent adjoint only: 1 = store r_y[0 .. m) at the head of the instance's dA row instead of the row's nnz_aug entries
+                                // (k_expand_dA behind the launch writes the caller's batch-minor dA from the factors: cone_engine.hip ce_vjp_qp); the launcher hands it to NsNoJvp
 };
 
 // k_backward_ns<..., FWD = true> (ce_backward_ns.h): what the forward derivative's elimination reads and writes beside CeBwdArgs' A, x, y, s, adj and fix
@@ -46,7 +48,7 @@ struct NsJvp {
     double *dx, *dy, *ds;    // [B][n], [B][m], [B][m] (ds may be NULL)
     int *iters;              // [B] <- 0: a directly solved instance took no LSQR iteration (NULL: not wanted)
 };
-struct NsNoJvp {};
+struct NsNoJvp { int dA_factors = 0; };          // (CeBwdArgs::dA_factors, copied by the launcher: the kernel's own arguments are unpacked)
 // k_backward_ns<..., MANY = true> (the adjoint of plain cones with a linear objective): K cotangents on one factorisation of the instance (cone_engine.hip
 // ce_vjp_many).  CeBwdArgs' dx, dy, dA, dq and adj point at cotangent 0; cotangent k lies the strides below further (elements; syk = 0: one dy for all)
 struct NsMany {

@@ -266,6 +266,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     HIPCHK(ce_setattr_fwd2_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_fwd2_qp((int)LDS_LIMIT));
     HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_tri_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
+    HIPCHK(hipFuncSetAttribute((const void *)k_expand_dA, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXPAND_LDS_MAX));
     return CE_OK;
 }
 
@@ -364,6 +365,20 @@ static void launch_transpose(hipStream_t st, const double *in, double *out, int 
     static const int ts = [] { const char *e = getenv("CE_TR_TILE"); return (e && atoi(e) == 32) ? 32 : 64; }();
     if (ts == 32) hipLaunchKernelGGL(k_transpose<32>, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, st, in, out, rows, cols);
     else hipLaunchKernelGGL(k_transpose<64>, dim3((cols + 63) / 64, (rows + 63) / 64), dim3(256), 0, st, in, out, rows, cols);
+}
+// k_expand_dA's launch shape for a batch: slabs of the value order so that tiles x slabs is about four workgroups per CU (two are resident on one: a tile's
+// x, y and v take 8 (n + 2 m) 33 bytes, 66 KB at the metric shape), no slab shorter than 256 entries.  false: the template is not the kernel's (a tile beyond
+// EXPAND_LDS_MAX, indices beyond the packed (i, j) pair, a row too short for the m factors) -- the caller keeps the layout pass.
+struct ExpandPlan { int slab, slabs; size_t lds; };
+static bool expand_dA_plan(const DevT &T, int B, ExpandPlan *ex) {
+    const int K = T.nnz_aug;
+    if (T.m >= (1 << 16) || T.n >= (1 << 15) || K < T.m) return false;
+    const int tiles = (B + EXP_TB - 1) / EXP_TB;
+    int slabs = std::max(1, std::min((K + 255) / 256, (1024 + tiles - 1) / tiles));
+    ex->slab = (K + slabs - 1) / slabs;
+    ex->slabs = (K + ex->slab - 1) / ex->slab;
+    ex->lds = expand_dA_lds_bytes(T.n, T.m, ex->slab);
+    return ex->lds <= EXPAND_LDS_MAX;
 }
 struct ProfScope {
     ce_engine *h; int which; hipStream_t st; hipEvent_t a{}, b{}; bool on;
@@ -543,6 +558,11 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     const bool do_fix = h->resolve && h->call_q && !P_vals && resolve_fits(h);
     FixLists fix{nullptr, nullptr};
     if (do_fix) { rc = resolve_lists(h, B, st, &fix); if (rc) return rc; }
+    // Factor mode: a batch-minor dA behind the search-free adjoint is written once, by k_expand_dA from (x, y, -dq, r_y), instead of batch-major by the adjoint and
+    // again by the layout pass; the adjoint stores r_y at the head of the instance's row of wsdA, where a re-solved instance's whole row lands as before.  The
+    // expansion tells the two apart by bit 8 of adj_status, so a call without one keeps the layout pass (as does a template whose tile exceeds the kernel's LDS).
+    ExpandPlan ex{};
+    const bool factors = need_tr && do_fix && P.ns_variant >= 0 && adj_status && expand_dA_plan(T, B, &ex);
     {
         ProfScope ps(h, 1, st);
         CeBwdArgs ba{};
@@ -554,6 +574,7 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         h->last_fast = -1;
         if (do_fix && P.ns_variant >= 0) {
             ba.T.lda = T.n;
+            ba.dA_factors = factors ? 1 : 0;
             lrc = ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, NsNoJvp{});
         } else if (P.bwd_mode == BWD_RT) {
             ba.T.lda = T.n;
@@ -601,7 +622,10 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     }
     if (need_tr) {
         ProfScope ps(h, 2, st);
-        launch_transpose(st, dAbm, dA_vals, B, K);
+        if (factors)
+            hipLaunchKernelGGL(k_expand_dA, dim3((B + EXP_TB - 1) / EXP_TB, ex.slabs), dim3(EXP_NT), ex.lds, st, T.n, T.m, K, B, ex.slab, T.rowidx, T.colidx, x, y,
+                               dAbm, (long)K, dq_vals, sdq_k, sdq_b, adj_status, dA_vals);
+        else launch_transpose(st, dAbm, dA_vals, B, K);
     }
     HIPCHK(hipGetLastError());
     return flush_dispatch_order(h, st, nullptr, nullptr);
