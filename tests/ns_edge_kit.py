@@ -58,12 +58,16 @@ def _triple_eigs(w, a):
     from oracle import oracle
     D = oracle.dproj_exp(w, dual=True) if a is None else oracle.dproj_pow(w, a, dual=True)
     e = np.linalg.eigvalsh(0.5 * (D + D.T))
-    return int((e > 1 - EIG_SNAP).sum()), int(((e > EIG_SNAP) & (e < 1 - EIG_SNAP)).sum())
+    mid = e[(e > EIG_SNAP) & (e < 1 - EIG_SNAP)]
+    return int((e > 1 - EIG_SNAP).sum()), int(mid.size), float(np.minimum(mid, 1 - mid).min()) if mid.size else 1.0
 
 
-def plant(shape, B=None, seed=0, active=None):
+def plant(shape, B=None, seed=0, active=None, extra_units=0, extra_L=0, triple_kinds=None, triple_margin=0.0):
     """The planted batch of a shape (kind, n, cones, states): dict with A, b, c, x, y, s, v, Pm (QP kind, else None), cones, kind, n, m, and per instance k1 (unit
-    directions), L (directions with an eigenvalue in (0, 1)), nf.  active: the number of active nonnegative rows, instead of the rule of the module docstring."""
+    directions), L (directions with an eigenvalue in (0, 1)), nf.  active: the number of active nonnegative rows, instead of the rule of the module docstring.
+    extra_units, extra_L: unit and interior directions of cones the caller plants itself (psd_edge_kit: the PSD blocks), counted by the rule and in k1, L.
+    triple_kinds: the (unit, interior) eigenvalue counts a triple may be drawn with, beside the room rule (None: any); triple_margin: the least distance of a
+    triple's interior eigenvalue from 0 and 1."""
     import tri_ns_kit as TK
     kind, n, cones, states = shape
     m = P.cone_rows(cones)
@@ -75,7 +79,7 @@ def plant(shape, B=None, seed=0, active=None):
     x = rng.standard_normal((B, n))
     v = np.zeros((B, m))
     v[:, :z] = rng.standard_normal((B, z))
-    units = np.full(B, z); L = np.zeros(B, int)
+    units = np.full(B, z + extra_units); L = np.full(B, extra_L)
     o = z + l
     for d, st in zip(q, states):
         u = rng.standard_normal((B, d - 1)); nu = np.linalg.norm(u, axis=1)
@@ -95,8 +99,8 @@ def plant(shape, B=None, seed=0, active=None):
         for r0, a in TK.triples(cones):
             for attempt in range(400):
                 w = rng.standard_normal(3)
-                k, mid = _triple_eigs(w, a)
-                if k <= room:
+                k, mid, margin = _triple_eigs(w, a)
+                if k <= room and margin >= triple_margin and (triple_kinds is None or (k, mid) in triple_kinds):
                     break
             else:
                 raise AssertionError(f"no triple state with at most {room} unit eigenvalues in 400 draws: {shape}")

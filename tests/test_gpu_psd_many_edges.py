@@ -5,8 +5,8 @@ dense references of psd_many_kit, with the tolerances of test_gpu_vjp_psd_many.p
 1 + max |reference| on status-0 instances, >= 80 %).  Every instance is Solved by the oracle, the dense systems have condition numbers <= 1.4e3, and the smallest
 min(B, 1 - B) of a weighted row is 3.0e-3 (checked on the CPU): nothing is filtered, nothing is flagged by the stiff rule.
 
-Ledger: every row of CE_NS_VARIANTS (parsed from ce_variants.h) must be reached by a compared call of each mode.  The footprint edge (a block of order 26 at
-n = 24) is left to a follow-up."""
+Ledger: every row of CE_NS_VARIANTS (parsed from ce_variants.h) must be reached by a compared call of each mode.  The footprint edges, n = 108 and the structure
+shapes are in tests/test_gpu_psd_mode_edges.py."""
 import pytest
 
 import plan_kit as pk

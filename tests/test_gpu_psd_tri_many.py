@@ -191,7 +191,8 @@ def test_the_three_modes_at_the_edges_of_the_plan(n):
     """ce_jvp_psd_tri against ce_jvp_lsqr (1e-5 worst on status-0 instances under the tight rule, 1e-6 on re-solved ones), both many-modes (K = 2, B = 4) against
     the loop.  With these cones m = 15 < n: checked on the CPU with the oracle, every instance is Solved but its x is not unique, so the elimination finds the
     reduced Hessian singular and hands every instance to the re-solve (status 4 | 8) -- the rows' kernels run at their largest and smallest n all the same, and what
-    is compared is the re-solved answer (LSQR's minimum-norm one in every route), not a share of directly solved instances."""
+    is compared is the re-solved answer (LSQR's minimum-norm one in every route), not a share of directly solved instances.  The directly solved half -- the same
+    edges at planted KKT points with m > n, every instance status 0, against dense references -- is tests/test_gpu_psd_mode_edges.py."""
     r = _edge(n)
     eng, L = r["eng"], _lib.lib()
     assert L.ce_psd_tri_ns_variant(eng._h) == L.ce_vjp_psd_tri_many_variant(eng._h) == L.ce_jvp_psd_tri_many_variant(eng._h) == EDGE_ROWS[n] == K.host_plan(n, EDGE_CONES)["psd_tri_ns_variant"]
