@@ -749,6 +749,10 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             if (tid == 0 && W.iters) W.iters[inst] = 0;
         } else if constexpr (MANY) {          // (for every cotangent; the instance is listed once)
             for (int kc = 0; kc < W.K; kc++) {
+                bool records = false;          // (record mode, the plain kind alone: a zero record instead of the zero row)
+                if constexpr (!QP && !TRI && !PSD) records = W.rec != nullptr;
+                if (records) { if constexpr (!QP && !TRI && !PSD) for (int k = tid; k < m + 1 + n; k += NTHR) W.rec[kc * W.srk + (size_t)inst * W.rpitch + k] = 0.0; }
+                else
                 for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[kc * W.sAk + (size_t)inst * T.nnz_aug + k] = 0.0;
                 for (int j = tid; j <= n; j += NTHR) dqo[kc * W.sqk + j * sdqk + inst * sdqb] = 0.0;
                 if constexpr (QP) { for (int k = tid; k < W.Q.nnz_p; k += NTHR) W.dP[kc * W.sPk + (size_t)inst * W.Q.nnz_p + k] = 0.0; }
@@ -1941,9 +1945,20 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     // one contiguous store instead of nnz_aug.  The flag is the launch's: uniform, the barrier below is skipped by all threads or none.
     bool factors = false;
     if constexpr (!FWD && !MANY) factors = W.dA_factors != 0;
+    // record mode (the plain many-cotangent adjoint alone, W.rec: ce_vjp_many_params): no dA row either; the pair's record (r_y, r_tau = 0: the elimination pins
+    // it, r_x) goes to the record buffer, and k_param_grad behind the launch evaluates the entries the parameter maps touch.  Uniform like the flag above.
+    bool records = false;
+    if constexpr (MANY && !FWD && !QP && !TRI && !PSD) records = W.rec != nullptr;
     if (factors) {
         double *const dArow = dAk + (size_t)inst * T.nnz_aug;
         for (int i = tid; i < m; i += NTHR) dArow[i] = vv[i];
+    } else if (records) {
+        if constexpr (MANY && !FWD && !QP && !TRI && !PSD) {
+            double *const rec = W.rec + kc * W.srk + (size_t)inst * W.rpitch;
+            for (int i = tid; i < m; i += NTHR) rec[i] = vv[i];
+            for (int j = tid; j < n; j += NTHR) rec[m + 1 + j] = rx[j];
+            if (tid == 0) rec[m] = 0.0;
+        }
     } else {
     for (int j = tid; j < n; j += NTHR) xs[j] = xg[(size_t)inst * n + j];
     for (int i = tid; i < m; i += NTHR) ys[i] = yg[(size_t)inst * m + i];

@@ -6,3 +6,8 @@
 // contraction per kernel: t = y r, then fma(x, v, -t), then the sign -- the form the output loop compiled to before this header existed (fp-contract=fast:
 // v_mul_f64, v_fma_f64 with a negated addend, the sign folded into the select), so the values are unchanged.  The b column (j == n) is -v: the caller selects.
 __device__ __forceinline__ double ce_dA_entry(double x, double v, double y, double r) { return -fma(x, v, -(y * r)); }
+
+// dA_eval[k] of a structural entry (i, n) of the b column:  db_i = y_i r_tau - r_y,i.  One fma, the form the LSQR re-solve's epilogue writes (ce_shared_a.h); the
+// elimination pins r_tau to 0, where this is -r_y,i: the -v its output loop and k_expand_dA store.  Stated here for the kernel that evaluates both kinds of entry
+// from the factor records (k_param_grad, ce_param_grad.h).
+__device__ __forceinline__ double ce_db_entry(double y, double rt, double v) { return fma(y, rt, -v); }

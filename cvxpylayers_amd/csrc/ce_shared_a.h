@@ -538,10 +538,17 @@ k_sa_lsqr(DevT T, SaStruct S, SaSplit F, const double *__restrict__ Avals0, long
     } else {
         // ---- outputs in the boundary convention: dA_eval = [-dA.data, db[b_idx]], dq_eval = [dc, 0]  (diffcp_if.py:91-92);
         //      dA_ij = x_j r_y,i - y_i r_x,j ,  db = y r_tau - r_y ,  dc = x r_tau - r_x        (oracle/cone_oracle.c adjoint_one: dQ = r Pi(z)^T antisymmetrised)
+        if (WM.rec) {          // record mode (ce_vjp_many_params): the pair's factors (r_y, r_tau, r_x) instead of the row; k_param_grad evaluates the formula below from them
+            double *rec = WM.rec + ko * WM.srk + (size_t)inst * WM.rpitch;
+            for (int i = tid; i < m; i += NT) rec[i] = ry[i];
+            for (int j = tid; j < n; j += NT) rec[m + 1 + j] = rx[j];
+            if (tid == 0) rec[m] = rt;
+        } else {
         double *dA = dAo + ko * WM.sAk + (size_t)inst * T.nnz_aug;
         for (int k = tid; k < T.nnz_aug; k += NT) {
             const int r = T.rowidx[k], c = T.colidx[k];
             dA[k] = (c < n) ? -(x[c] * ry[r] - y[r] * rx[c]) : fma(y[r], rt, -ry[r]);
+        }
         }
         for (int j = tid; j <= n; j += NT) dqo[ko * WM.sqk + j * sdqk + inst * sdqb] = (j < n) ? fma(x[j], rt, -rx[j]) : 0.0;
     }

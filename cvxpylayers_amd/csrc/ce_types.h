@@ -51,9 +51,12 @@ struct NsJvp {
 struct NsNoJvp { int dA_factors = 0; };          // (CeBwdArgs::dA_factors, copied by the launcher: the kernel's own arguments are unpacked)
 // k_backward_ns<..., MANY = true> (the adjoint of plain cones with a linear objective): K cotangents on one factorisation of the instance (cone_engine.hip
 // ce_vjp_many).  CeBwdArgs' dx, dy, dA, dq and adj point at cotangent 0; cotangent k lies the strides below further (elements; syk = 0: one dy for all)
+// rec != NULL (the plain kind alone, ce_vjp_many_params): the kernel writes NO dA row; it stores the factor record of pair (k, instance) at rec + k * srk +
+// instance * rpitch instead -- r_y[0 .. m), r_tau = 0, r_x[0 .. n): rpitch >= m + 1 + n -- from which k_param_grad (ce_param_grad.h) evaluates the entries it needs
 struct NsMany {
     int K;
     long sxk, syk, sAk, sqk, sak;
+    double *rec = nullptr; long rpitch = 0, srk = 0;
 };
 // k_backward_ns<..., FWD = true, ..., MANY = true> (plain cones, P or not): K tangents on one factorisation of the instance (cone_engine.hip ce_jvp_many /
 // ce_jvp_qp_many).  Tangent k of instance i: its value row at tA + k * stAk + i * stAb, its q_eval row (n + 1 contiguous entries) at tq + k * stqk + i * stqb; a batch
@@ -162,6 +165,7 @@ struct SaWalkMany {
     long sxk = 0, syk = 0, sAk = 0, sqk = 0;     // adjoint: dx, dy (0: one dy for all), dA, dq
     long stAk = 0, stqk = 0, sok = 0, sosk = 0;  // forward: tA, tq, dx (sok), dy and ds (sosk)
     long sak = 0;                                // both: adj_status and iters
+    double *rec = nullptr; long rpitch = 0, srk = 0;      // adjoint, rec != NULL (ce_vjp_many_params): the factor record (r_y, r_tau, r_x) of NsMany instead of the dA row
 };
 
 struct SaFwd {
@@ -250,6 +254,20 @@ struct CeCheckArgs {
     unsigned char *solved; int *status, *iters; double *resid;
 };
 
+// ---- parameter gradients from the adjoint's factors (ce_param_grad.h): one streaming kernel, no plan row ----
+// k_param_grad: the composed transposed parameter maps of a layer (ptr [rows + 1]; code, kidx, val per entry), the point, the pairs' dq rows and factor records
+// (mode PG_RECORDS: the records of NsMany::rec; PG_ROWHEAD, K == 1: r_y at the head of row b of the batch-major dA workspace, the whole row where adj[b] & 8)
+enum { PG_RECORDS = 0, PG_ROWHEAD = 1 };
+struct CeParamGradArgs {
+    int n, m, B, K, rows, slab, mode;
+    const int *ptr, *code, *kidx; const double *val;
+    const double *x, *y;                                   // [B][n], [B][m]
+    const double *dq; long sqK, sqk, sqb;                  // entry j of pair (k, b) at k * sqK + j * sqk + b * sqb
+    const double *rec; long rpitch, srk;                   // factors of pair (k, b) at k * srk + b * rpitch
+    const int *adj;                                        // [K][B] (PG_ROWHEAD reads bit 8; PG_RECORDS does not read it)
+    double *g;                                             // [K][B][rows]
+};
+
 // launchers (one per kernel object file; `variant` is a row index of the family's list in ce_variants.h): 0 on success, -1 when the variant is not
 // instantiated for the launcher's kind
 int ce_launch_fwd2_plain(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);   // zero / nonneg / SOC
@@ -305,6 +323,10 @@ void ce_launch_lpgd_grad_rows(size_t lds, hipStream_t st, const CeLpgdGradArgs &
 void ce_launch_lpgd_grad_tile(bool staged, int chunks, int kchunk, int wdq, size_t lds, hipStream_t st, const CeLpgdGradArgs &a);
 size_t ce_lpgd_grad_rows_lds(int n, int m);      // k_lpgd_grad_rows
 size_t ce_lpgd_grad_tile_lds(int n, int m);      // k_lpgd_grad_tile<STAGED = true>
+// ce_tu_param_grad.hip: tiles of 16, 8, 4 or 2 pairs (the largest whose footprint leaves two workgroups per CU; 2 whenever it fits at all) x slabs of rows; a.slab is
+// the launcher's to set.  -1: the factors of two pairs exceed LDS (nothing is launched)
+int ce_launch_param_grad(hipStream_t st, const CeParamGradArgs &a);
+hipError_t ce_setattr_param_grad(int bytes);
 // raise the dynamic-LDS limit of every kernel of the family
 hipError_t ce_setattr_fwd2_plain(int bytes);
 hipError_t ce_setattr_fwd2_psd(int bytes);

@@ -112,6 +112,8 @@ struct ce_engine {
     int lsqr_variant = 0;                          // 0: LSQR, 1: LSMR (ce_set_lsqr_variant; the calls that solve EVERY instance iteratively: ce_vjp_shared_a, ce_vjp_lsqr)
     DevBuf<int> d_summary; unsigned summary_next = 0;   // ce_status_summary staging (8 slots of 3 ints)
     DevBuf<double> d_dy0;        // ce_vjp_many with dy == NULL: one zero dy [B][m] that every cotangent reads
+    DevBuf<double> d_rec;        // ce_vjp_many_params: the factor records [K][B][m + 1 + n] the adjoint leaves for k_param_grad
+    const CeParamGradArgs *pg = nullptr;      // (ce_vjp_params -> ce_vjp_qp: the call in flight wants the parameter gradient, not the dA row)
     DevBuf<double> d_qT;       // batch-major copy of the objective values for the LSQR adjoint kernels (vjp_lsqr_launch)
     DevBuf<double> d_aa_ws;      // Anderson-acceleration history of the shared-A forward kernel ([B][4][lp])
     DevBuf<unsigned long long> d_psd_stats;        // CE_PSD_STATS=1: counters of the PSD projection (printed to stderr by ce_destroy)
@@ -267,6 +269,7 @@ static int upload_engine(const ce_template *tpl, ce_engine &h, const HostIndex &
     HIPCHK(ce_setattr_bwd_rt_plain((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_rt_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_bwd_generic((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_qp((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_qp_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_psd_tri((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_vjp_psd_tri_many((int)LDS_LIMIT)); HIPCHK(ce_setattr_ns_jvp_psd_tri_many((int)LDS_LIMIT));
     HIPCHK(ce_setattr_value((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_lpgd((int)VALUE_LDS_MAX)); HIPCHK(ce_setattr_check((int)VALUE_LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void *)k_expand_dA, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EXPAND_LDS_MAX));
+    HIPCHK(ce_setattr_param_grad((int)LDS_LIMIT));
     return CE_OK;
 }
 
@@ -316,6 +319,10 @@ long ce_psd_ns_lds(ce_handle h) { return (h && h->plan.psd_ns_variant >= 0) ? (l
 // the many-cotangent mode rebuilds every cotangent's vectors in the buffers of the plain adjoint: its row and footprint are ns_variant's, and like the kernel
 // behind ce_vjp it only runs in front of the LSQR re-solve
 int ce_vjp_many_variant(ce_handle h) { return (h && h->plan.ns_variant >= 0 && resolve_lds_fits(h->T, h->psd_first)) ? h->plan.ns_variant : -1; }
+// the parameter gradient from the factors runs behind that mode (ce_vjp_many_params) and behind the single-cotangent adjoint's factor mode (ce_vjp_params): the same
+// templates -- k_param_grad's smallest tile holds two pairs' factors, 16 (3 n + 2 m + 2) bytes, wherever the elimination's own footprint fits -- and the packed
+// (i, j) of a map entry asks for m < 2^16, n < 2^15, which n <= 108 and an A that fits LDS imply
+int ce_param_grad_variant(ce_handle h) { return (ce_vjp_many_variant(h) >= 0 && h->T.m < (1 << 16)) ? h->plan.ns_variant : -1; }
 // the many-tangent modes rebuild every tangent's vectors in the buffers of ce_jvp / ce_jvp_qp: their rows and footprints.  Plain kind: the rule of ce_jvp without the
 // triples (TRI keeps K launches: ce_backward_ns.h).  Either kind is kept in-kernel only while its K = 8 bracket lies below K single-tangent calls
 // (profiles/jvp_many/): a kind that fails that is switched off here, and ConeEngine.jvp_many runs its loop.
@@ -531,7 +538,8 @@ static int resolve_run(ce_handle h, int B, const FixLists &L, F &&lsqr) {
 int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *P_vals,
               const double *x, const double *y, const double *s, const double *dx, const double *dy,
               double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, double *dP_vals, int *adj_status, void *stream) {
-    if (!h || B <= 0 || !x || !y || !s || !dx || !dy || !dA_vals || !dq_vals) { g_err = "null argument"; return CE_E_BADARG; }
+    const CeParamGradArgs *const pg = h ? h->pg : nullptr;          // (ce_vjp_params: no dA_vals; the workspace row of an instance holds its factors, or its re-solved row)
+    if (!h || B <= 0 || !x || !y || !s || !dx || !dy || (!dA_vals && !pg) || !dq_vals) { g_err = "null argument"; return CE_E_BADARG; }
     const CePlan &P = h->plan;
     if ((P_vals != nullptr) != P.qp_native || (P_vals && !dP_vals)) { g_err = "quadratic objective: P_vals / dP_vals must be given exactly when ce_qp_native(h) == 1"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
@@ -544,7 +552,8 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     else { if (!h->retained_A || h->retained_B != B) { g_err = "no retained forward inputs"; return CE_E_STATE; } Abm = h->retained_A; }
     const int K = T.nnz_aug;
     double *dAbm = nullptr; bool need_tr = false;
-    if (sdA_k == 1 && sdA_b == K) dAbm = dA_vals;
+    if (pg) { HIPCHK(h->wsdA.reserve((size_t)B * K)); dAbm = h->wsdA.get(); }
+    else if (sdA_k == 1 && sdA_b == K) dAbm = dA_vals;
     else if (sdA_b == 1 && sdA_k == B) { HIPCHK(h->wsdA.reserve((size_t)B * K)); dAbm = h->wsdA.get(); need_tr = true; }
     else { g_err = "dA_vals must be contiguous batch-minor or batch-major"; return CE_E_BADARG; }
     double *gA = nullptr, *gK = nullptr;
@@ -562,7 +571,8 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     // again by the layout pass; the adjoint stores r_y at the head of the instance's row of wsdA, where a re-solved instance's whole row lands as before.  The
     // expansion tells the two apart by bit 8 of adj_status, so a call without one keeps the layout pass (as does a template whose tile exceeds the kernel's LDS).
     ExpandPlan ex{};
-    const bool factors = need_tr && do_fix && P.ns_variant >= 0 && adj_status && expand_dA_plan(T, B, &ex);
+    const bool factors = pg ? true : (need_tr && do_fix && P.ns_variant >= 0 && adj_status && expand_dA_plan(T, B, &ex));
+    if (pg && !(do_fix && P.ns_variant >= 0 && adj_status && K >= T.m)) { g_err = "ce_vjp_params: internal, the factor mode is not available"; return CE_E_STATE; }
     {
         ProfScope ps(h, 1, st);
         CeBwdArgs ba{};
@@ -620,6 +630,12 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
             h->nk_pending = true; h->nk_B = B;
         }
     }
+    if (pg) {
+        ProfScope ps(h, 2, st);
+        CeParamGradArgs ga = *pg;
+        ga.rec = dAbm; ga.rpitch = K; ga.srk = 0;
+        if (ce_launch_param_grad(st, ga)) { g_err = "ce_vjp_params: the factors of two instances exceed LDS"; return CE_E_TOO_LARGE; }
+    }
     if (need_tr) {
         ProfScope ps(h, 2, st);
         if (factors)
@@ -639,7 +655,8 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 enum NsManyKind { NS_MANY_PLAIN = 0, NS_MANY_TRI = 1, NS_MANY_PSD = 2, NS_MANY_PSD_TRI = 3 };          // (NS_MANY_PSD_TRI: ce_vjp_psd_tri_many / ce_jvp_psd_tri_many -- on the row with both kinds' segments)
 static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                         const double *x, const double *y, const double *s, const double *dx, const double *dy,
-                        double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+                        double *dA_vals, double *dq_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0) {
+    // rec (ce_vjp_many_params, the plain kind with an armed re-solve): both kernels store the pairs' factor records [K][B][rpitch] instead of dA rows; dA_vals is unused
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (B > 1 && sA_b != T.nnz_aug) { g_err = std::string(who) + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
@@ -652,7 +669,8 @@ static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, in
         HIPCHK(hipMemsetAsync(h->d_dy0.get(), 0, sizeof(double) * (size_t)B * m, st));
         dy = h->d_dy0.get(); syk = 0;
     }
-    const NsMany W{K, (long)((size_t)B * n), syk, (long)((size_t)B * nnz), (long)((size_t)B * (n + 1)), (long)B};
+    NsMany W{K, (long)((size_t)B * n), syk, (long)((size_t)B * nnz), (long)((size_t)B * (n + 1)), (long)B};
+    if (rec) { W.rec = rec; W.rpitch = rpitch; W.srk = (long)((size_t)B * rpitch); dA_vals = rec; }          // (a non-null dA for the launchers' checks: neither kernel writes through it)
     if (!(h->resolve && q_vals)) {
         for (int k = 0; k < K; k++) {
             const int rc = ce_vjp(h, B, A_vals_bm, 1, (long)nnz, q_vals, sq_k, sq_b, x, y, s, dx + k * W.sxk, dy + k * W.syk, dA_vals + k * W.sAk, 1, (long)nnz,
@@ -676,7 +694,7 @@ static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, in
     }
     const int grid = B < 768 ? B : 768;          // (resolve_run's grid)
     const int prof_keep = h->prof; h->prof = 0;
-    SaWalkMany wm; wm.K = K; wm.sxk = W.sxk; wm.syk = W.syk; wm.sAk = W.sAk; wm.sqk = W.sqk; wm.sak = W.sak;
+    SaWalkMany wm; wm.K = K; wm.sxk = W.sxk; wm.syk = W.syk; wm.sAk = W.sAk; wm.sqk = W.sqk; wm.sak = W.sak; wm.rec = W.rec; wm.rpitch = W.rpitch; wm.srk = W.srk;
     rc = vjp_lsqr_launch(h, grid, A_vals_bm, (long)nnz, 1, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, 1, (long)(n + 1),
                          adj_status, nullptr, h->rs_atol, h->rs_btol, h->rs_conlim, h->rs_iter_lim, stream, fix.cur, 4 | 8, fix.oth, nullptr, &wm);
     h->fix_par ^= 1;
@@ -695,6 +713,70 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
         return CE_E_UNSUPPORTED;
     }
     return vjp_many_run(h, NS_MANY_PLAIN, "ce_vjp_many", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream);
+}
+// The parameter gradients of K cotangents at one solution, no dA (include/cone_engine.h): ce_vjp_many's two launches in record mode -- the elimination and the LSQR
+// walk leave (r_y, r_tau, r_x) per pair in d_rec -- and k_param_grad behind them, which applies the composed transposed parameter maps to the entries it
+// evaluates from the records.  The pitch m + 1 + n keeps r_x beside r_y: a re-solved pair's r_x is NOT x r_tau - dq to the last bit, and the entries are to be
+// the ones the dA route stores.
+static const char *const PG_REFUSAL = ": this template has no parameter gradient from the factors (ce_param_grad_variant < 0: PSD / exponential / power cones, a quadratic "
+                                      "objective inside the kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); use the dA entry points";
+static int pg_check(ce_handle h, const char *who, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val, const double *q_vals) {
+    if (rows <= 0 || !map_ptr || !map_code || !map_k || !map_val) { g_err = std::string(who) + ": null map argument or rows <= 0"; return CE_E_BADARG; }
+    if (ce_param_grad_variant(h) < 0) { g_err = std::string(who) + PG_REFUSAL; return CE_E_UNSUPPORTED; }
+    if (!(h->resolve && q_vals)) { g_err = std::string(who) + ": the re-solve must be armed (q_vals given, ce_set_adjoint_resolve enabled): the factor modes run in front of it alone"; return CE_E_UNSUPPORTED; }
+#ifdef CE_TIMING
+    g_err = std::string(who) + ": not available in the timing build (its stamps go to the dA rows)"; return CE_E_UNSUPPORTED;
+#endif
+    return CE_OK;
+}
+int ce_vjp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                       double *g, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) { g_err = "ce_vjp_many_params: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    int rc = pg_check(h, "ce_vjp_many_params", rows, map_ptr, map_code, map_k, map_val, q_vals);
+    if (rc) return rc;
+    const DevT &T = h->T;
+    const long rpitch = (long)T.m + 1 + T.n;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(h->d_rec.reserve((size_t)K * B * rpitch));
+    rc = vjp_many_run(h, NS_MANY_PLAIN, "ce_vjp_many_params", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, nullptr, dq_vals, adj_status, stream, h->d_rec.get(), rpitch);
+    if (rc) return rc;
+    CeParamGradArgs ga{T.n, T.m, B, K, rows, 0, PG_RECORDS, map_ptr, map_code, map_k, map_val, x, y, dq_vals, (long)((size_t)B * (T.n + 1)), 1, (long)(T.n + 1),
+                       h->d_rec.get(), rpitch, (long)((size_t)B * rpitch), adj_status, g};
+    {
+        ProfScope ps(h, 2, (hipStream_t)stream);
+        if (ce_launch_param_grad((hipStream_t)stream, ga)) { g_err = "ce_vjp_many_params: the factors of two pairs exceed LDS"; return CE_E_TOO_LARGE; }
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+// the factor records the last ce_vjp_many_params call of this (B, K) left in the engine's workspace, [K][B][m + 1 + n], copied to `out` on the stream (introspection
+// for tests: r_tau of a pair is not observable from g and dq)
+int ce_param_grad_records(ce_handle h, int B, int K, double *out, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !out) { g_err = "ce_param_grad_records: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    const size_t cnt = (size_t)K * B * ((size_t)h->T.m + 1 + h->T.n);
+    if (!h->d_rec.get() || h->d_rec.capacity() < cnt) { g_err = "ce_param_grad_records: no ce_vjp_many_params call of this size has run"; return CE_E_STATE; }
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(out, h->d_rec.get(), sizeof(double) * cnt, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CE_OK;
+}
+// One cotangent: the single-cotangent adjoint in its factor mode (r_y at the head of the instance's workspace row, the whole row of a re-solved instance -- today's
+// convention, the NsNoJvp kernel untouched) and k_param_grad in its row-head mode behind it.  K = 1 of the many-mode loses to ce_vjp (README), hence an entry of its own.
+int ce_vjp_params(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                  const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                  int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                  double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream) {
+    if (!h || B <= 0 || !x || !y || !s || !dx || !dy || !g || !dq_vals || !adj_status) { g_err = "ce_vjp_params: null argument or B <= 0"; return CE_E_BADARG; }
+    int rc = pg_check(h, "ce_vjp_params", rows, map_ptr, map_code, map_k, map_val, q_vals);
+    if (rc) return rc;
+    const DevT &T = h->T;
+    if (T.nnz_aug < T.m) { g_err = "ce_vjp_params: a value row shorter than m cannot hold the factors (nnz_aug < m); call ce_vjp_many_params with K = 1"; return CE_E_UNSUPPORTED; }
+    const CeParamGradArgs ga{T.n, T.m, B, 1, rows, 0, PG_ROWHEAD, map_ptr, map_code, map_k, map_val, x, y, dq_vals, 0, sdq_k, sdq_b, nullptr, 0, 0, adj_status, g};
+    h->pg = &ga; h->call_q = q_vals; h->call_sqk = sq_k; h->call_sqb = sq_b;
+    rc = ce_vjp_qp(h, B, A_vals, sA_k, sA_b, nullptr, x, y, s, dx, dy, nullptr, 0, 0, dq_vals, sdq_k, sdq_b, nullptr, adj_status, stream);
+    h->pg = nullptr; h->call_q = nullptr;
+    return rc;
 }
 // K cotangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_vjp_many's body with k_backward_ns<..., TRI, MANY> on the
 // triples' variant and footprint.  Without an armed re-solve K calls of ce_vjp, whose pivoting kernel serves such templates.

@@ -431,6 +431,81 @@ class ConeEngine:
         _lib.check(rc, name)
         return dA, dq, adj
 
+    @property
+    def param_grad_variant(self) -> int:
+        """>= 0: vjp_many_params / vjp_params serve this template (ce_param_grad_variant: exactly where ce_vjp_many_variant >= 0)"""
+        return int(_lib.lib().ce_param_grad_variant(self._h))
+
+    def _param_grad_prologue(self, maps, lsqr, q_eval, who):
+        if maps.n != self.n or maps.m != self.m or maps.nnz_aug != self.nnz_aug:
+            raise ValueError(f"ConeEngine.{who}: the composed maps belong to another structure (n, m, nnz_aug) = ({maps.n}, {maps.m}, {maps.nnz_aug})")
+        if q_eval is None:
+            raise ValueError(f"ConeEngine.{who}: q_eval is required (the factor modes run in front of the armed LSQR re-solve)")
+        rule = unpack_rule(lsqr, self.n, self.m)[:4]
+        if rule[:3] != self._resolve_rule:
+            _lib.check(_lib.lib().ce_set_adjoint_resolve(self._h, 1, float(rule[0]), float(rule[1]), 1e8, int(rule[2])), "ce_set_adjoint_resolve")
+            self._resolve_rule = rule[:3]
+        return maps.on(self.device)
+
+    def vjp_many_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None, out: torch.Tensor | None = None):
+        """The parameter gradients of K cotangents at one solution, with no dA in memory: dx (K, B, n), dy (K, B, m) or None (zero), maps a
+        param_grad.ComposedMaps of this template.  Returns g (K, B, maps.rows) -- written into `out` when given (contiguous, that shape) --, dq (K, B, n + 1) and
+        adj (K, B).  g[k, b] is what the transposed parameter maps make of vjp_many's dA[k, b] and dq[k, b]: to the bit on a parameter with one map entry, within
+        the terms' rounding elsewhere.  One ce_vjp_many_params call (last_vjp_many_path == "many_params"); templates without the mode
+        (param_grad_variant < 0) raise _lib.EngineError with the library's reason and write nothing."""
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        K, B = int(dx.shape[0]), int(A_bm.shape[0])
+        ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_many_params")
+        g = out if out is not None else torch.empty((K, B, maps.rows), **f64)
+        if tuple(g.shape) != (K, B, maps.rows) or not g.is_contiguous() or g.dtype != torch.float64:
+            raise ValueError(f"ConeEngine.vjp_many_params: out must be a contiguous float64 tensor of shape {(K, B, maps.rows)}")
+        dq = torch.empty((K, B, self.n + 1), **f64)
+        adj = torch.empty((K, B), dtype=torch.int32, device=dev)
+        self.last_vjp_many_path, self.last_vjp_kernel = "many_params", "ce_vjp_many_params"
+        if B == 0 or K == 0:
+            return g, dq, adj
+        dx = dx.to(**f64).contiguous()
+        dy = None if dy is None else dy.to(**f64).contiguous()
+        A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
+        xc, yc, sc_ = (t.to(torch.float64).contiguous() for t in (x, y, s))
+        qd, q_args = self._q_args(q_eval)
+        rc = _lib.lib().ce_vjp_many_params(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                           None if dy is None else dy.data_ptr(), maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(),
+                                           g.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
+        _lib.check(rc, "ce_vjp_many_params")
+        return g, dq, adj
+
+    def param_grad_records(self, K: int, B: int) -> torch.Tensor:
+        """(K, B, m + 1 + n): the factor records (r_y, r_tau, r_x) the last vjp_many_params call of this size left in the engine (introspection for tests)"""
+        out = torch.empty((K, B, self.m + 1 + self.n), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.lib().ce_param_grad_records(self._h, B, K, out.data_ptr(), self._stream()), "ce_param_grad_records")
+        return out
+
+    def vjp_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None):
+        """One cotangent: dx (B, n), dy (B, m).  Returns g (B, maps.rows), dq (n + 1, B), adj (B,) from ce_vjp_params -- the single-cotangent kernel in its factor
+        mode and k_param_grad behind it (K = 1 of the many-mode is the slower kernel for one cotangent).  A value row shorter than m cannot carry the factors:
+        that template takes vjp_many_params with K = 1."""
+        dev = self.device
+        B = int(A_bm.shape[0])
+        if self.nnz_aug < self.m:
+            g, dq, adj = self.vjp_many_params(A_bm, x, y, s, dx[None], None if dy is None else dy[None], maps, lsqr=lsqr, q_eval=q_eval)
+            return g[0], dq[0].t(), adj[0]
+        ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_params")
+        g = torch.empty((B, maps.rows), dtype=torch.float64, device=dev)
+        dq = torch.empty((self.n + 1, B), dtype=torch.float64, device=dev)
+        adj = torch.empty((B,), dtype=torch.int32, device=dev)
+        if B == 0:
+            return g, dq, adj
+        A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
+        xc, yc, sc_, dxc, dyc = (t.to(torch.float64).contiguous() for t in (x, y, s, dx, dy))
+        qd, q_args = self._q_args(q_eval)
+        rc = _lib.lib().ce_vjp_params(self._h, B, A_c.data_ptr(), 1, self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dxc.data_ptr(), dyc.data_ptr(),
+                                      maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(), g.data_ptr(), dq.data_ptr(), B, 1, adj.data_ptr(),
+                                      self._stream())
+        _lib.check(rc, "ce_vjp_params")
+        return g, dq, adj
+
     def _q_args(self, q_eval):
         """(tensor to keep alive, (pointer, stride0, stride1)) of an optional (n+1, B) objective as the C ABI takes it; None -> (None, (None, 0, 0))"""
         if q_eval is None:

@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -190,6 +190,7 @@ class _ConeLayer(torch.autograd.Function):
         n_refine = refine_steps(merged_args)
         qp_adj = qp_adjoint(merged_args)          # (validated with the other arguments; read by adjoint_many alone)
         tri_adj = tri_adjoint(merged_args)        # (likewise)
+        param_grad(merged_args)                   # (validated with the other arguments; read by the frontend alone: the plugin boundary has no parameters)
         tri_tan = tri_tangents(merged_args)       # (likewise; read by tangent_many alone)
         n_newton = newton_first(merged_args)
         has_psd = bool(len(eng.cone_dict.get("s", []) or []))
@@ -427,6 +428,76 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
                 any_k |= adj[k]
             eng.mailbox.note_adjoint_flags(any_k, batch_size)
     return dA, dq, dP, failed
+
+
+def param_grad_served(backward_data) -> bool:
+    """the node whose forward returned `backward_data` can hand its parameter gradient over from the adjoint's factors (solver_args param_grad="factors"): the
+    default adjoint mode on the per-instance path, a linear objective, and a template with the mode (ConeEngine.param_grad_variant >= 0)"""
+    saved = backward_data[0]
+    return (saved is not None and saved.lpgd is None and saved.P_bm is None and saved.path == "per_instance" and saved.q_eval is not None
+            and saved.eng.param_grad_variant >= 0)
+
+
+def _masked_point(saved, cots):
+    """what _ConeLayer.backward does to the point and the cotangents of a raise_on_error=False call: a zero cotangent at a zero point for the masked instances"""
+    x, y, s, failed = saved.x, saved.y, saved.s, saved.failed
+    if failed is not None:
+        keep = ~failed[:, None]
+        cots = [None if c is None else torch.where(keep, c, torch.zeros_like(c)) for c in cots]
+        x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
+    return x, y, s, cots
+
+
+def adjoint_many_params(backward_data, dprimal, ddual, info, maps, out=None):
+    """adjoint_many with the transposed parameter maps applied inside the engine: K cotangents through the node whose forward returned `backward_data`, no dA in
+    memory.  maps: the layer's param_grad.ComposedMaps.  Returns g (K, B, Ptot + 1) batch-major on the engine's device -- written into `out` when given --, dq
+    (K, B, n + 1) and the `failed` mask or None.  Applies what adjoint_many applies (device moves, the `failed` mask, the saved lsqr rule and q_eval,
+    note_adjoint_flags on the OR over the cotangents, info["adjoint"]["status"] as (K, B), info["adjoint"]["path"] == "ce_vjp_many_params") and calls
+    ConeEngine.vjp_many_params.  The node must be served (param_grad_served): NotImplementedError otherwise, before anything is enqueued."""
+    saved, batch_size, _unbatched, _in_device = backward_data
+    if saved is None:
+        raise RuntimeError("adjoint_many_params called on a layer evaluated with needs_grad=False")
+    if not param_grad_served(backward_data):
+        raise NotImplementedError("MI355 solver: this node has no parameter gradient from the adjoint's factors (PSD / exponential / power cones, a quadratic "
+                                  "objective, n > 108, a shared A, CE_BWD_NS=0, or a solver_args mode other than the default); use adjoint_many")
+    eng = saved.eng
+    ref = dprimal if dprimal is not None else ddual
+    K = int(ref.shape[0])
+    with torch.cuda.device(eng.device):
+        f64 = dict(device=eng.device, dtype=torch.float64)
+        dx = dprimal.to(**f64).contiguous() if dprimal is not None else torch.zeros((K, batch_size, eng.n), **f64)
+        dy = ddual.to(**f64).contiguous() if ddual is not None else None
+        x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
+        g, dq, adj = eng.vjp_many_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, out=out)
+        if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
+            info["adjoint"]["status"] = adj
+            info["adjoint"]["path"] = eng.last_vjp_kernel
+            info["adjoint"]["param_grad"] = "factors"
+        if K > 0 and batch_size > 0:
+            any_k = adj[0].clone()
+            for k in range(1, K):
+                any_k |= adj[k]
+            eng.mailbox.note_adjoint_flags(any_k, batch_size)
+    return g, dq, saved.failed
+
+
+def adjoint_params(backward_data, dprimal, ddual, info, maps):
+    """One cotangent (the .backward() of a layer under param_grad="factors"): dprimal (B, n) and / or ddual (B, m) -> g (B, Ptot + 1) from ConeEngine.vjp_params,
+    with what _ConeLayer.backward applies around its vjp call.  None when nothing flows back."""
+    saved, batch_size, _unbatched, _in_device = backward_data
+    if dprimal is None and ddual is None:
+        return None
+    eng = saved.eng
+    with torch.cuda.device(eng.device):
+        f64 = dict(device=eng.device, dtype=torch.float64)
+        dx = dprimal.to(**f64).contiguous() if dprimal is not None else eng.zeros_like_cached(saved.x)
+        dy = ddual.to(**f64).contiguous() if ddual is not None else eng.zeros_like_cached(saved.y)
+        x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
+        g, _dq, adj = eng.vjp_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval)
+        if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
+            info["adjoint"]["status"] = adj
+        eng.mailbox.note_adjoint_flags(adj, batch_size)
+    return g
 
 
 def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=None):

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -113,6 +113,21 @@ def qp_adjoint(merged_args: dict) -> str:
     mode = str(merged_args.get("qp_adjoint", "pivoting"))
     if mode not in ("pivoting", "search_free"):
         raise ValueError(f"MI355 solver: qp_adjoint must be 'pivoting' or 'search_free', got {mode!r}")
+    return mode
+
+
+def param_grad(merged_args: dict) -> str:
+    """How the parameter gradient of a CvxpyLayer is formed from the adjoint's solution:
+    absent / "dA" -> the engine writes dA (nnz_aug entries per instance and cotangent) and dq, and the transposed parameter maps read them back;
+    "factors" -> the adjoint kernels keep their small solution (r_x, r_y, r_tau) per (cotangent, instance) pair and one streaming kernel applies the transposed maps
+    to the dA entries it evaluates from them: no dA in memory (ce_vjp_many_params behind CvxpyLayer.jacobian(direction="reverse"), ce_vjp_params behind
+    .backward(); info["adjoint"]["param_grad"] == "factors").  A parameter with one map entry gets the same bits, the others agree within their terms' rounding.
+    Served where ce_param_grad_variant >= 0 on the default adjoint mode (plain cones, a linear objective, n <= 108, per-instance A); every other template or
+    path -- PSD / exponential / power cones, a quadratic objective, mode "dense" / "lsqr" / "lsmr" / the LPGD family, a shared A, CE_BWD_NS=0, forward-mode AD --
+    ignores the key with one notice and runs the dA route.  The plugin boundary (_CvxpyLayer.apply) has no parameters and ignores it."""
+    mode = merged_args.get("param_grad", "dA")
+    if not isinstance(mode, str) or mode not in ("dA", "factors"):
+        raise ValueError(f"MI355 solver: param_grad must be 'dA' or 'factors', got {mode!r}")
     return mode
 
 

@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -537,6 +537,40 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
  * adjoint's buffers: same footprint, the launch plan is unchanged).  -1: PSD / exponential / power cones, a quadratic objective inside the kernels, n > 108,
  * CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS. */
 int ce_vjp_many_variant(ce_handle h);
+
+/* PARAMETER GRADIENTS STRAIGHT FROM THE ADJOINT'S FACTORS: what a caller with parameter maps wants from ce_vjp_many / ce_vjp is not dA (nnz_aug entries per pair) but
+ * its product with the transposed maps.  Every dA entry is made of x, y and the adjoint's small solution (r_x, r_y, r_tau), so these entries keep the dA row out of
+ * memory: the adjoint kernels store the factors per (cotangent, instance) pair and one streaming kernel (csrc/ce_param_grad.h) writes
+ *     g[k][b][p] = sum_e val_e . dA_entry(i_e, j_e)  +  sum_e' val_e' . dq[j_e']          p = 0 .. rows - 1
+ * for the map of the layer, COMPOSED by the caller once (cvxpylayers_amd/interfaces/param_grad.py): CSR over the rows (parameter columns, the constant column
+ * included), the entries of the transposed A-map first and those of the transposed q-map behind them:
+ *   map_ptr [rows + 1];  per entry  map_code, map_k (int), map_val (double):
+ *     map_code >= 0: entry map_k of the value order, packed (i, j) = (map_code & 0xffff, map_code >> 16) -- its row and column, j == n: the b column
+ *     map_code <  0: entry j = map_code & 0x7fffffff of dq (map_k unused)
+ *   Every index must be in range (i < m, j <= n, map_k < nnz_aug): the library cannot check device arrays.
+ * An entry is rounded as the dA entry first and multiplied by its value afterwards, in map order from a zero sum: a row with ONE entry has exactly the bits the dA
+ * route gives; other rows agree within their terms' rounding.  Rows without an entry are written as 0.0.
+ *   ce_vjp_many_params: ce_vjp_many's inputs (q_vals REQUIRED: the mode runs in front of the armed re-solve only) -> g [K][B][rows], dq_vals [K][B][n + 1],
+ *                       adj_status [K][B] (required), all contiguous.  The elimination and the LSQR walk of the flagged instances store records instead of rows.
+ *   ce_vjp_params     : one cotangent on the single-cotangent kernel (K = 1 of the many-mode is slower than ce_vjp): ce_vjp's inputs, g [B][rows], dq_vals with its
+ *                       strides, adj_status [B] (required).  CE_E_UNSUPPORTED also when nnz_aug < m (the factors ride in the workspace row): use K = 1 above.
+ *   ce_param_grad_variant: >= 0 exactly where ce_vjp_many_variant(h) >= 0 (the value is the same tile variant); -1: both entries return CE_E_UNSUPPORTED with a
+ *                       ce_last_error that names the reason and write nothing.
+ * CE_E_BADARG (before any device call): null handle or required pointer, B <= 0, K <= 0, rows <= 0.  No host synchronisation, no allocation after the first call
+ * of a (B, K). */
+int ce_vjp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                       double *g, double *dq_vals, int *adj_status, void *stream);
+int ce_vjp_params(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                  const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                  int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                  double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream);
+int ce_param_grad_variant(ce_handle h);
+/* Introspection (tests): the factor records the last ce_vjp_many_params call left in the engine's workspace, copied to out [K][B][m + 1 + n] on the stream: per pair
+ * r_y[0 .. m), r_tau, r_x[0 .. n).  r_tau is 0 on the elimination path and LSQR's on a re-solved pair; g and dq do not determine it.  CE_E_STATE when no call of at
+ * least this size has run. */
+int ce_param_grad_records(ce_handle h, int B, int K, double *out, void *stream);
 
 /* MANY TANGENTS AT ONE SOLUTION: for every k < K what ce_jvp (ce_jvp_qp) returns for the k-th tangent, from ONE factorisation per instance -- the forward twin of
  * ce_vjp_many, and the route by which a layer with few parameters and many outputs, or a native QP layer, gets its Jacobian by columns.  The matrix work is the
