@@ -15,6 +15,7 @@ SO_PATH = os.environ.get("CE_ENGINE_SO") or os.path.join(_HERE, "csrc", "libcone
 SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_default_settings", "ce_create", "ce_destroy", "ce_last_error", "ce_solve", "ce_vjp", "ce_solve_shared_a", "ce_vjp_shared_a", "ce_vjp_lsqr", "ce_jvp_lsqr", "ce_jvp_shared_a", "ce_jvp", "ce_refine", "ce_qp_native", "ce_solve_qp", "ce_vjp_qp",
            "ce_transpose", "ce_status_summary", "ce_parammap_apply", "ce_parammap_apply2", "ce_ca_step", "ce_ca_check", "ce_ca_psd", "ce_ca_psd_mfma", "ce_ca_triples", "ce_ca_triple_jac", "ce_ca_update", "ce_ca_finish", "ce_set_profiling", "ce_get_profile", "ce_reset_profile", "ce_get_launch_info", "ce_get_plan", "ce_set_dispatch_history", "ce_set_adjoint_resolve", "ce_adjoint_ns_variant", "ce_set_lsqr_variant", "ce_jvp_qp", "ce_refine_qp", "ce_qp_ns_variant", "ce_tri_ns_variant", "ce_vjp_many", "ce_vjp_many_variant", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_many_variant", "ce_jvp_qp_many_variant", "ce_vjp_qp_many", "ce_vjp_qp_many_variant", "ce_vjp_tri_many", "ce_vjp_tri_many_variant", "ce_jvp_tri_many", "ce_jvp_tri_many_variant", "ce_jvp_psd", "ce_refine_psd", "ce_psd_ns_variant", "ce_psd_ns_lds", "ce_vjp_psd_many", "ce_vjp_psd_many_variant", "ce_jvp_psd_many", "ce_jvp_psd_many_variant",
            "ce_vjp_many_params", "ce_vjp_params", "ce_param_grad_variant", "ce_param_grad_records",
+           "ce_vjp_qp_many_params", "ce_vjp_tri_many_params", "ce_vjp_psd_many_params", "ce_vjp_psd_tri_many_params",
            "ce_jvp_psd_tri", "ce_refine_psd_tri", "ce_vjp_psd_tri_many", "ce_jvp_psd_tri_many", "ce_psd_tri_ns_variant", "ce_psd_tri_ns_lds", "ce_vjp_psd_tri_many_variant", "ce_jvp_psd_tri_many_variant",
            "ce_value", "ce_value_jvp", "ce_value_vjp", "ce_lpgd_perturb", "ce_lpgd_grad", "ce_set_transient_solve", "ce_check_solved",
            "ce_cones_create", "ce_cones_destroy", "ce_cones_rows", "ce_cones_state_len", "ce_cone_project", "ce_cone_dproject"]
@@ -96,6 +97,8 @@ def lib():
     L.ce_vjp_many_variant.argtypes = [vp]
     L.ce_vjp_many_params.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, lg, lg, dp, dp, dp, dp, dp, C.c_int, ip, ip, ip, dp, dp, dp, ip, vp]
     L.ce_vjp_params.argtypes = [vp, C.c_int, dp, lg, lg, dp, lg, lg, dp, dp, dp, dp, dp, C.c_int, ip, ip, ip, dp, dp, dp, lg, lg, ip, vp]
+    L.ce_vjp_tri_many_params.argtypes = L.ce_vjp_psd_many_params.argtypes = L.ce_vjp_psd_tri_many_params.argtypes = L.ce_vjp_many_params.argtypes
+    L.ce_vjp_qp_many_params.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, dp, dp, dp, dp, dp, C.c_int, ip, ip, ip, dp, dp, dp, ip, vp]
     L.ce_param_grad_variant.argtypes = [vp]
     L.ce_param_grad_records.argtypes = [vp, C.c_int, C.c_int, dp, vp]
     L.ce_jvp_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, lg, lg, dp, dp, dp, dp, lg, lg, dp, lg, lg, dp, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, C.c_int, vp]

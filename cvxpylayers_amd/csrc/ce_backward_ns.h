@@ -749,13 +749,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
             if (tid == 0 && W.iters) W.iters[inst] = 0;
         } else if constexpr (MANY) {          // (for every cotangent; the instance is listed once)
             for (int kc = 0; kc < W.K; kc++) {
-                bool records = false;          // (record mode, the plain kind alone: a zero record instead of the zero row)
-                if constexpr (!QP && !TRI && !PSD) records = W.rec != nullptr;
-                if (records) { if constexpr (!QP && !TRI && !PSD) for (int k = tid; k < m + 1 + n; k += NTHR) W.rec[kc * W.srk + (size_t)inst * W.rpitch + k] = 0.0; }
+                const bool records = W.rec != nullptr;          // (record mode, every many-cotangent kind: a zero record instead of the zero row -- and no dP, which is null then)
+                if (records) { for (int k = tid; k < m + 1 + n; k += NTHR) W.rec[kc * W.srk + (size_t)inst * W.rpitch + k] = 0.0; }
                 else
                 for (int k = tid; k < T.nnz_aug; k += NTHR) dAo[kc * W.sAk + (size_t)inst * T.nnz_aug + k] = 0.0;
                 for (int j = tid; j <= n; j += NTHR) dqo[kc * W.sqk + j * sdqk + inst * sdqb] = 0.0;
-                if constexpr (QP) { for (int k = tid; k < W.Q.nnz_p; k += NTHR) W.dP[kc * W.sPk + (size_t)inst * W.Q.nnz_p + k] = 0.0; }
+                if constexpr (QP) { if (!records) for (int k = tid; k < W.Q.nnz_p; k += NTHR) W.dP[kc * W.sPk + (size_t)inst * W.Q.nnz_p + k] = 0.0; }
                 if (tid == 0 && adj_status) adj_status[kc * W.sak + inst] = QP ? 4 : 2;
             }
         } else {
@@ -1945,15 +1944,16 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     // one contiguous store instead of nnz_aug.  The flag is the launch's: uniform, the barrier below is skipped by all threads or none.
     bool factors = false;
     if constexpr (!FWD && !MANY) factors = W.dA_factors != 0;
-    // record mode (the plain many-cotangent adjoint alone, W.rec: ce_vjp_many_params): no dA row either; the pair's record (r_y, r_tau = 0: the elimination pins
-    // it, r_x) goes to the record buffer, and k_param_grad behind the launch evaluates the entries the parameter maps touch.  Uniform like the flag above.
+    // record mode (the many-cotangent adjoints of every kind, W.rec: ce_vjp_many_params and its QP / TRI / PSD twins): no dA row either; the pair's record (r_y
+    // -- in the original basis: vv stands behind the triples' W r~_y and the blocks' rotation above --, r_tau = 0: the elimination pins it, r_x) goes to the record
+    // buffer, and k_param_grad behind the launch evaluates the entries the parameter maps touch.  The QP kind writes no dP either (W.dP is null).  Uniform like the flag above.
     bool records = false;
-    if constexpr (MANY && !FWD && !QP && !TRI && !PSD) records = W.rec != nullptr;
+    if constexpr (MANY && !FWD) records = W.rec != nullptr;
     if (factors) {
         double *const dArow = dAk + (size_t)inst * T.nnz_aug;
         for (int i = tid; i < m; i += NTHR) dArow[i] = vv[i];
     } else if (records) {
-        if constexpr (MANY && !FWD && !QP && !TRI && !PSD) {
+        if constexpr (MANY && !FWD) {
             double *const rec = W.rec + kc * W.srk + (size_t)inst * W.rpitch;
             for (int i = tid; i < m; i += NTHR) rec[i] = vv[i];
             for (int j = tid; j < n; j += NTHR) rec[m + 1 + j] = rx[j];
@@ -1988,11 +1988,12 @@ k_backward_ns(DevT T, const double *__restrict__ Avals, const double *__restrict
     for (int j = tid; j <= n; j += NTHR) dqk[j * sdqk + inst * sdqb] = (j < n) ? -rx[j] : 0.0;
     if constexpr (QP && MANY && !FWD) {
         // dP = -sym(r_x x^T) through the structure, consecutive lanes on consecutive entries (x and r_x from LDS); a one-triangle entry stands for both matrix
-        // entries and takes both shares, as k_backward_rt writes it
+        // entries and takes both shares, as k_backward_rt writes it.  Record mode: k_param_grad evaluates the entries the P map touches from the record (xs is not staged)
         double *const dProw = W.dP + kc * W.sPk + (size_t)inst * W.Q.nnz_p;
+        if (!records)
         for (int k = tid; k < W.Q.nnz_p; k += NTHR) {
             const int i = W.prow[k], j = W.pcol[k];
-            const double v = -0.5 * (rx[i] * xs[j] + rx[j] * xs[i]);
+            const double v = ce_dP_entry(rx[i], xs[j], rx[j], xs[i]);
             dProw[k] = (W.p_tri && i != j) ? 2.0 * v : v;
         }
     }

@@ -1,7 +1,7 @@
 // ce_param_grad.h -- k_param_grad: the parameter gradient of K x B (cotangent, instance) pairs straight from the adjoint's factors: the transposed parameter
 // maps applied to the entries of dA and to dq WITHOUT a dA row in memory (cone_engine.hip ce_vjp_many_params, ce_vjp_params; tests/test_gpu_param_grad.py)
 #pragma once
-#include "ce_dA_entry.h"       // ce_dA_entry, ce_db_entry: the entries of the dA row, shared with k_backward_ns and k_expand_dA
+#include "ce_dA_entry.h"       // ce_dA_entry, ce_db_entry, ce_dP_entry: the entries of the dA row and of dP, shared with k_backward_ns and k_expand_dA
 
 // ================================================================================================
 // g (K, B, rows) batch-major, written once:   g[p] = sum_e val_e . entry(i_e, j_e)  +  sum_e' val_e' . dq[j_e']
@@ -9,7 +9,9 @@
 // The map of a layer, composed once on the host (interfaces/param_grad.py): CSR over the rows = parameter columns 0 .. Ptot (the constant column included), the
 // entries of the transposed A-map first, those of the transposed q-map behind them.  An entry is (code, k, val):
 //   code >= 0: entry k of the value order, (i, j) = (code & 0xffff, code >> 16): ce_dA_entry(x_j, r_y,i, y_i, r_x,j) for j < n, ce_db_entry(y_i, r_tau, r_y,i) for j == n
-//   code <  0: entry j = code & 0x7fffffff of the pair's dq row (k unused)
+//   code <  0, bit 30 clear: entry j = code & 0x3fffffff of the pair's dq row (k unused)
+//   code <  0, bit 30 set: entry k of P's structure order (a native QP: ce_vjp_qp_many_params), (i, j) = (code & 0x7fff, code >> 15 & 0x7fff): ce_dP_entry(r_x,i, x_j, r_x,j,
+//              x_i) = -1/2 (r_x,i x_j + r_x,j x_i), ONE share -- the doubling of a one-triangle structure and the frontend's symmetrisation are the host's, in val
 // Every entry is rounded as the dA entry first and multiplied by val afterwards (one fma onto the running sum, which starts at zero): a row with one entry
 // gets the bits of the product the parameter-map pass forms from a stored dA.
 //
@@ -87,7 +89,14 @@ __global__ void __launch_bounds__(PG_NT) k_param_grad(CeParamGradArgs a) {
     auto entries = [&](int c, int kk, int h, double (&e)[PG_HP]) __attribute__((always_inline)) {
         const int o = h * PG_HP;
         if (c < 0) {
-            const double *d = ds + (size_t)(c & 0x7fffffff) * PG_TP + o;
+            if (c & 0x40000000) {          // (an entry of dP: x and r_x of the staged tile; never met in PG_ROWHEAD, whose kinds have no P)
+                const int i = c & 0x7fff, j = (c >> 15) & 0x7fff;
+                const double *xi = xs + (size_t)i * PG_TP + o, *xj = xs + (size_t)j * PG_TP + o, *ri = rs + (size_t)i * PG_TP + o, *rj = rs + (size_t)j * PG_TP + o;
+#pragma unroll
+                for (int u = 0; u < PG_HP; u++) e[u] = ce_dP_entry(ri[u], xj[u], rj[u], xi[u]);
+                return;
+            }
+            const double *d = ds + (size_t)(c & 0x3fffffff) * PG_TP + o;
 #pragma unroll
             for (int u = 0; u < PG_HP; u++) e[u] = d[u];
             return;

@@ -51,7 +51,7 @@ struct NsJvp {
 struct NsNoJvp { int dA_factors = 0; };          // (CeBwdArgs::dA_factors, copied by the launcher: the kernel's own arguments are unpacked)
 // k_backward_ns<..., MANY = true> (the adjoint of plain cones with a linear objective): K cotangents on one factorisation of the instance (cone_engine.hip
 // ce_vjp_many).  CeBwdArgs' dx, dy, dA, dq and adj point at cotangent 0; cotangent k lies the strides below further (elements; syk = 0: one dy for all)
-// rec != NULL (the plain kind alone, ce_vjp_many_params): the kernel writes NO dA row; it stores the factor record of pair (k, instance) at rec + k * srk +
+// rec != NULL (ce_vjp_many_params and its QP / TRI / PSD twins; every type derived from this one carries it): the kernel writes NO dA row -- and the QP kind no dP --; it stores the factor record of pair (k, instance) at rec + k * srk +
 // instance * rpitch instead -- r_y[0 .. m), r_tau = 0, r_x[0 .. n): rpitch >= m + 1 + n -- from which k_param_grad (ce_param_grad.h) evaluates the entries it needs
 struct NsMany {
     int K;

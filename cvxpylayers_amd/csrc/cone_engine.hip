@@ -720,43 +720,88 @@ int ce_vjp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
 // the ones the dA route stores.
 static const char *const PG_REFUSAL = ": this template has no parameter gradient from the factors (ce_param_grad_variant < 0: PSD / exponential / power cones, a quadratic "
                                       "objective inside the kernels, n > 108, CE_BWD_NS=0, or the LSQR vectors of the re-solve exceed LDS); use the dA entry points";
-static int pg_check(ce_handle h, const char *who, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val, const double *q_vals) {
+// (served / refusal: the entry's own condition -- ce_param_grad_variant for the plain kind, the kind's many-cotangent variant for the others; need_resolve: every
+// kind but the QP one, which has no re-solve behind its launch)
+static int pg_check(ce_handle h, const char *who, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val, const double *q_vals,
+                    int served = -2, const char *refusal = nullptr, bool need_resolve = true) {
     if (rows <= 0 || !map_ptr || !map_code || !map_k || !map_val) { g_err = std::string(who) + ": null map argument or rows <= 0"; return CE_E_BADARG; }
-    if (ce_param_grad_variant(h) < 0) { g_err = std::string(who) + PG_REFUSAL; return CE_E_UNSUPPORTED; }
-    if (!(h->resolve && q_vals)) { g_err = std::string(who) + ": the re-solve must be armed (q_vals given, ce_set_adjoint_resolve enabled): the factor modes run in front of it alone"; return CE_E_UNSUPPORTED; }
+    if (served == -2) { served = ce_param_grad_variant(h); refusal = PG_REFUSAL; }
+    if (served < 0 || h->T.m >= (1 << 16)) { g_err = std::string(who) + refusal; return CE_E_UNSUPPORTED; }
+    if (need_resolve && !(h->resolve && q_vals)) { g_err = std::string(who) + ": the re-solve must be armed (q_vals given, ce_set_adjoint_resolve enabled): the factor modes run in front of it alone"; return CE_E_UNSUPPORTED; }
 #ifdef CE_TIMING
     g_err = std::string(who) + ": not available in the timing build (its stamps go to the dA rows)"; return CE_E_UNSUPPORTED;
 #endif
     return CE_OK;
 }
-int ce_vjp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
-                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
-                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
-                       double *g, double *dq_vals, int *adj_status, void *stream) {
-    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) { g_err = "ce_vjp_many_params: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
-    int rc = pg_check(h, "ce_vjp_many_params", rows, map_ptr, map_code, map_k, map_val, q_vals);
+// k_param_grad behind a record-mode launch of any kind: the records of the call in d_rec, the pairs' dq rows where the adjoint wrote them
+static int pg_records_launch(ce_handle h, const std::string &who, int B, int K, const double *x, const double *y, int rows, const int *map_ptr, const int *map_code,
+                             const int *map_k, const double *map_val, double *g, const double *dq_vals, const int *adj_status, void *stream) {
+    const DevT &T = h->T;
+    const long rpitch = (long)T.m + 1 + T.n;
+    CeParamGradArgs ga{T.n, T.m, B, K, rows, 0, PG_RECORDS, map_ptr, map_code, map_k, map_val, x, y, dq_vals, (long)((size_t)B * (T.n + 1)), 1, (long)(T.n + 1),
+                       h->d_rec.get(), rpitch, (long)((size_t)B * rpitch), adj_status, g};
+    {
+        ProfScope ps(h, 2, (hipStream_t)stream);
+        if (ce_launch_param_grad((hipStream_t)stream, ga)) { g_err = who + ": the factors of two pairs exceed LDS"; return CE_E_TOO_LARGE; }
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+// the body of ce_vjp_many_params and of its TRI / PSD / PSD + TRI twins: `served` is the kind's many-cotangent variant (-2: the plain kind's ce_param_grad_variant)
+static int vjp_many_params_run(ce_handle h, NsManyKind kind, const char *who, int served, const char *refusal, int B, int K, const double *A_vals_bm, long sA_b,
+                               const double *q_vals, long sq_k, long sq_b, const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                               int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                               double *g, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) { g_err = std::string(who) + ": null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    int rc = pg_check(h, who, rows, map_ptr, map_code, map_k, map_val, q_vals, served, refusal);
     if (rc) return rc;
     const DevT &T = h->T;
     const long rpitch = (long)T.m + 1 + T.n;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(h->d_rec.reserve((size_t)K * B * rpitch));
-    rc = vjp_many_run(h, NS_MANY_PLAIN, "ce_vjp_many_params", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, nullptr, dq_vals, adj_status, stream, h->d_rec.get(), rpitch);
+    rc = vjp_many_run(h, kind, who, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, nullptr, dq_vals, adj_status, stream, h->d_rec.get(), rpitch);
     if (rc) return rc;
-    CeParamGradArgs ga{T.n, T.m, B, K, rows, 0, PG_RECORDS, map_ptr, map_code, map_k, map_val, x, y, dq_vals, (long)((size_t)B * (T.n + 1)), 1, (long)(T.n + 1),
-                       h->d_rec.get(), rpitch, (long)((size_t)B * rpitch), adj_status, g};
-    {
-        ProfScope ps(h, 2, (hipStream_t)stream);
-        if (ce_launch_param_grad((hipStream_t)stream, ga)) { g_err = "ce_vjp_many_params: the factors of two pairs exceed LDS"; return CE_E_TOO_LARGE; }
-    }
-    HIPCHK(hipGetLastError());
-    return CE_OK;
+    return pg_records_launch(h, who, B, K, x, y, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
+}
+int ce_vjp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                       double *g, double *dq_vals, int *adj_status, void *stream) {
+    return vjp_many_params_run(h, NS_MANY_PLAIN, "ce_vjp_many_params", -2, nullptr, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val,
+                               g, dq_vals, adj_status, stream);
+}
+// The same for the other many-cotangent kinds (include/cone_engine.h): each is served exactly where its kind's ce_vjp_*_many_variant >= 0 and refuses every other
+// handle -- a plain one included -- before anything is enqueued.  The records are the plain kind's: r_y stands in the original basis behind the triples' / blocks' rotation.
+int ce_vjp_tri_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                           const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                           int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                           double *g, double *dq_vals, int *adj_status, void *stream) {
+    return vjp_many_params_run(h, NS_MANY_TRI, "ce_vjp_tri_many_params", ce_vjp_tri_many_variant(h),
+                               ": this template has no search-free elimination with triples (ce_vjp_tri_many_variant < 0); use the dA entry points, or the *_many_params entry of its kind",
+                               B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
+}
+int ce_vjp_psd_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                           const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                           int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                           double *g, double *dq_vals, int *adj_status, void *stream) {
+    return vjp_many_params_run(h, NS_MANY_PSD, "ce_vjp_psd_many_params", ce_vjp_psd_many_variant(h),
+                               ": this template has no search-free elimination with PSD blocks (ce_vjp_psd_many_variant < 0); use the dA entry points, or the *_many_params entry of its kind",
+                               B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
+}
+int ce_vjp_psd_tri_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                               const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                               int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                               double *g, double *dq_vals, int *adj_status, void *stream) {
+    return vjp_many_params_run(h, NS_MANY_PSD_TRI, "ce_vjp_psd_tri_many_params", ce_vjp_psd_tri_many_variant(h),
+                               ": this template has no search-free elimination with PSD blocks and triples (ce_vjp_psd_tri_many_variant < 0); use the dA entry points, or the *_many_params entry of its kind",
+                               B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
 }
 // the factor records the last ce_vjp_many_params call of this (B, K) left in the engine's workspace, [K][B][m + 1 + n], copied to `out` on the stream (introspection
 // for tests: r_tau of a pair is not observable from g and dq)
 int ce_param_grad_records(ce_handle h, int B, int K, double *out, void *stream) {
     if (!h || B <= 0 || K <= 0 || !out) { g_err = "ce_param_grad_records: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
     const size_t cnt = (size_t)K * B * ((size_t)h->T.m + 1 + h->T.n);
-    if (!h->d_rec.get() || h->d_rec.capacity() < cnt) { g_err = "ce_param_grad_records: no ce_vjp_many_params call of this size has run"; return CE_E_STATE; }
+    if (!h->d_rec.get() || h->d_rec.capacity() < cnt) { g_err = "ce_param_grad_records: no *_many_params call of this size has run"; return CE_E_STATE; }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpyAsync(out, h->d_rec.get(), sizeof(double) * cnt, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return CE_OK;
@@ -1477,15 +1522,12 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
 // K cotangents at one solution of a template with a quadratic objective inside the kernels (include/cone_engine.h).  One launch of k_backward_ns<..., QP, ..., MANY>
 // without FWD factors every instance once and writes all K answers, dP among them.  No re-solve list: no LSQR has a P term, the dropped-variable answer of a
 // rank-deficient instance stands with status 4 for every k (as ce_jvp_qp_many and ce_vjp_qp).
-int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
-                   const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream) {
-    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dA_vals || !dq_vals || !dP_vals) {
-        g_err = "ce_vjp_qp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
-    }
-    { const int rc = qp_ns_check(h, "ce_vjp_qp_many"); if (rc) return rc; }
+// (rec: ce_vjp_qp_many_params -- the kernel stores the pairs' factor records [K][B][rpitch] and neither dA rows nor dP; dA_vals and dP_vals are unused then)
+static int vjp_qp_many_run(ce_handle h, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                           const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0) {
     const CePlan &P = h->plan;
     const DevT &T = h->T;
-    if (B > 1 && sA_b != T.nnz_aug) { g_err = "ce_vjp_qp_many: A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
+    if (B > 1 && sA_b != T.nnz_aug) { g_err = std::string(who) + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const size_t n = T.n, m = T.m, nnz = T.nnz_aug, nnzp = (size_t)h->nnz_p;
@@ -1499,6 +1541,7 @@ int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
     W.K = K; W.sxk = (long)((size_t)B * n); W.syk = syk; W.sAk = (long)((size_t)B * nnz); W.sqk = (long)((size_t)B * (n + 1)); W.sak = (long)B;
     W.Q = NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p};
     W.prow = h->d_prow.get(); W.pcol = h->d_pcol.get(); W.p_tri = h->p_tri; W.dP = dP_vals; W.sPk = (long)((size_t)B * nnzp);
+    if (rec) { W.rec = rec; W.rpitch = rpitch; W.srk = (long)((size_t)B * rpitch); W.dP = nullptr; dA_vals = nullptr; }          // (record mode writes through neither)
     ProfScope ps(h, 1, st);
     CeBwdArgs ba{};
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
@@ -1507,6 +1550,33 @@ int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
     if (ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no many-cotangent kernel with a quadratic objective for the planned variant"; return CE_E_BADARG; }
     HIPCHK(hipGetLastError());
     return CE_OK;
+}
+int ce_vjp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                   const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dA_vals || !dq_vals || !dP_vals) {
+        g_err = "ce_vjp_qp_many: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
+    }
+    { const int rc = qp_ns_check(h, "ce_vjp_qp_many"); if (rc) return rc; }
+    return vjp_qp_many_run(h, "ce_vjp_qp_many", B, K, A_vals_bm, sA_b, P_vals, x, y, s, dx, dy, dA_vals, dq_vals, dP_vals, adj_status, stream);
+}
+// The parameter gradients of K cotangents of a native QP, neither dA nor dP in memory (include/cone_engine.h): ce_vjp_qp_many's one launch in record mode and
+// k_param_grad behind it, whose map carries P entries beside the A and q entries.  No re-solve: a rank-deficient instance keeps the dropped-variable answer, status 4.
+int ce_vjp_qp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                          const double *dx, const double *dy, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                          double *g, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) {
+        g_err = "ce_vjp_qp_many_params: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
+    }
+    int rc = pg_check(h, "ce_vjp_qp_many_params", rows, map_ptr, map_code, map_k, map_val, nullptr, ce_vjp_qp_many_variant(h),
+                      ": this template has no search-free elimination with a quadratic objective inside the kernels (ce_vjp_qp_many_variant < 0); use the dA entry points, or the *_many_params entry of its kind",
+                      false);
+    if (rc) return rc;
+    const long rpitch = (long)h->T.m + 1 + h->T.n;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(h->d_rec.reserve((size_t)K * B * rpitch));
+    rc = vjp_qp_many_run(h, "ce_vjp_qp_many_params", B, K, A_vals_bm, sA_b, P_vals, x, y, s, dx, dy, nullptr, dq_vals, nullptr, adj_status, stream, h->d_rec.get(), rpitch);
+    if (rc) return rc;
+    return pg_records_launch(h, "ce_vjp_qp_many_params", B, K, x, y, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
 }
 
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record

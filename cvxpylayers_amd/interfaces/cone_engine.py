@@ -436,9 +436,13 @@ class ConeEngine:
         """>= 0: vjp_many_params / vjp_params serve this template (ce_param_grad_variant: exactly where ce_vjp_many_variant >= 0)"""
         return int(_lib.lib().ce_param_grad_variant(self._h))
 
-    def _param_grad_prologue(self, maps, lsqr, q_eval, who):
+    def _param_grad_prologue(self, maps, lsqr, q_eval, who, need_q: bool = True):
         if maps.n != self.n or maps.m != self.m or maps.nnz_aug != self.nnz_aug:
             raise ValueError(f"ConeEngine.{who}: the composed maps belong to another structure (n, m, nnz_aug) = ({maps.n}, {maps.m}, {maps.nnz_aug})")
+        if getattr(maps, "nnz_p", 0) not in (0, self.nnz_p):
+            raise ValueError(f"ConeEngine.{who}: the composed maps carry a P map of another structure (nnz_p = {maps.nnz_p}, the engine's is {self.nnz_p})")
+        if not need_q:          # (the QP kind: no re-solve behind its launch)
+            return maps.on(self.device)
         if q_eval is None:
             raise ValueError(f"ConeEngine.{who}: q_eval is required (the factor modes run in front of the armed LSQR re-solve)")
         rule = unpack_rule(lsqr, self.n, self.m)[:4]
@@ -447,37 +451,52 @@ class ConeEngine:
             self._resolve_rule = rule[:3]
         return maps.on(self.device)
 
-    def vjp_many_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None, out: torch.Tensor | None = None):
+    def vjp_many_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None, out: torch.Tensor | None = None, P_bm=None,
+                        qp_many: bool = False, tri_many: bool = False, psd_many: bool = False):
         """The parameter gradients of K cotangents at one solution, with no dA in memory: dx (K, B, n), dy (K, B, m) or None (zero), maps a
         param_grad.ComposedMaps of this template.  Returns g (K, B, maps.rows) -- written into `out` when given (contiguous, that shape) --, dq (K, B, n + 1) and
-        adj (K, B).  g[k, b] is what the transposed parameter maps make of vjp_many's dA[k, b] and dq[k, b]: to the bit on a parameter with one map entry, within
-        the terms' rounding elsewhere.  One ce_vjp_many_params call (last_vjp_many_path == "many_params"); templates without the mode
-        (param_grad_variant < 0) raise _lib.EngineError with the library's reason and write nothing."""
+        adj (K, B).  g[k, b] is what the transposed parameter maps make of vjp_many's dA[k, b] and dq[k, b] (and dP[k, b]): to the bit on a parameter with one map
+        entry, within the terms' rounding elsewhere.  One C call (last_vjp_many_path == "many_params", last_vjp_kernel names the entry): ce_vjp_many_params, or under
+        the keywords of vjp_many the entry of that kind -- qp_many with P_bm: ce_vjp_qp_many_params (maps may carry a P map; q_eval and lsqr are not read: no
+        re-solve); tri_many: ce_vjp_tri_many_params; psd_many: ce_vjp_psd_many_params, on a template with triples beside the blocks ce_vjp_psd_tri_many_params.
+        The keyword SELECTS the entry: a template the entry does not serve raises _lib.EngineError with the library's reason and writes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
-        ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_many_params")
+        if qp_many and P_bm is None:
+            raise ValueError("ConeEngine.vjp_many_params: qp_many needs P_bm")
+        if sum(map(bool, (qp_many, tri_many, psd_many))) > 1 or (P_bm is not None and not qp_many):
+            raise ValueError("ConeEngine.vjp_many_params: at most one of qp_many / tri_many / psd_many, and P_bm with qp_many alone")
+        L = _lib.lib()
+        name = ("ce_vjp_qp_many_params" if qp_many else "ce_vjp_tri_many_params" if tri_many else
+                ("ce_vjp_psd_tri_many_params" if L.ce_vjp_psd_tri_many_variant(self._h) >= 0 else "ce_vjp_psd_many_params") if psd_many else "ce_vjp_many_params")
+        ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_many_params", need_q=not qp_many)
         g = out if out is not None else torch.empty((K, B, maps.rows), **f64)
         if tuple(g.shape) != (K, B, maps.rows) or not g.is_contiguous() or g.dtype != torch.float64:
             raise ValueError(f"ConeEngine.vjp_many_params: out must be a contiguous float64 tensor of shape {(K, B, maps.rows)}")
         dq = torch.empty((K, B, self.n + 1), **f64)
         adj = torch.empty((K, B), dtype=torch.int32, device=dev)
-        self.last_vjp_many_path, self.last_vjp_kernel = "many_params", "ce_vjp_many_params"
+        self.last_vjp_many_path, self.last_vjp_kernel = "many_params", name
         if B == 0 or K == 0:
             return g, dq, adj
         dx = dx.to(**f64).contiguous()
         dy = None if dy is None else dy.to(**f64).contiguous()
         A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
-        xc, yc, sc_ = (t.to(torch.float64).contiguous() for t in (x, y, s))
-        qd, q_args = self._q_args(q_eval)
-        rc = _lib.lib().ce_vjp_many_params(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
-                                           None if dy is None else dy.data_ptr(), maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(),
-                                           g.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
-        _lib.check(rc, "ce_vjp_many_params")
+        xc, yc, sc_ = (t.detach().to(torch.float64).contiguous() for t in (x, y, s))
+        map_args = (maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(), g.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
+        if qp_many:
+            P_c = P_bm.detach().to(**f64).contiguous()
+            rc = L.ce_vjp_qp_many_params(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                         None if dy is None else dy.data_ptr(), *map_args)
+        else:
+            qd, q_args = self._q_args(q_eval)
+            rc = getattr(L, name)(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                  None if dy is None else dy.data_ptr(), *map_args)
+        _lib.check(rc, name)
         return g, dq, adj
 
     def param_grad_records(self, K: int, B: int) -> torch.Tensor:
-        """(K, B, m + 1 + n): the factor records (r_y, r_tau, r_x) the last vjp_many_params call of this size left in the engine (introspection for tests)"""
+        """(K, B, m + 1 + n): the factor records (r_y, r_tau, r_x) the last vjp_many_params call of this size, of any kind, left in the engine (introspection for tests)"""
         out = torch.empty((K, B, self.m + 1 + self.n), dtype=torch.float64, device=self.device)
         _lib.check(_lib.lib().ce_param_grad_records(self._h, B, K, out.data_ptr(), self._stream()), "ce_param_grad_records")
         return out

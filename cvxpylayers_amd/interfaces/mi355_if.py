@@ -430,12 +430,34 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
     return dA, dq, dP, failed
 
 
-def param_grad_served(backward_data) -> bool:
-    """the node whose forward returned `backward_data` can hand its parameter gradient over from the adjoint's factors (solver_args param_grad="factors"): the
-    default adjoint mode on the per-instance path, a linear objective, and a template with the mode (ConeEngine.param_grad_variant >= 0)"""
+def param_grad_kind(backward_data):
+    """which entry hands the parameter gradient of the node whose forward returned `backward_data` over from the adjoint's factors (solver_args
+    param_grad="factors"), or None: "plain" (ce_vjp_many_params / ce_vjp_params: the default adjoint mode on the per-instance path, a linear objective, a template
+    with ConeEngine.param_grad_variant >= 0), or -- for MANY cotangents alone, under the rule that sends adjoint_many to the kind's one-factorisation kernel, its own
+    key included -- "qp" (a native QP under qp_adjoint="search_free": ce_vjp_qp_many_params), "tri" (exponential / power cones under tri_adjoint="search_free":
+    ce_vjp_tri_many_params), "psd" (PSD blocks under psd_adjoint="search_free": ce_vjp_psd_many_params, with triples beside them ce_vjp_psd_tri_many_params)"""
     saved = backward_data[0]
-    return (saved is not None and saved.lpgd is None and saved.P_bm is None and saved.path == "per_instance" and saved.q_eval is not None
-            and saved.eng.param_grad_variant >= 0)
+    if saved is None or saved.lpgd is not None or saved.path != "per_instance":
+        return None
+    eng, L = saved.eng, _lib.lib()
+    if saved.P_bm is not None:
+        return "qp" if (saved.qp_adjoint == "search_free" and L.ce_vjp_qp_many_variant(eng._h) >= 0) else None
+    if saved.q_eval is None:
+        return None
+    if eng.param_grad_variant >= 0:
+        return "plain"
+    if saved.tri_adjoint == "search_free" and L.ce_vjp_tri_many_variant(eng._h) >= 0:
+        return "tri"
+    if saved.psd_adjoint and (L.ce_vjp_psd_many_variant(eng._h) >= 0 or L.ce_vjp_psd_tri_many_variant(eng._h) >= 0):
+        return "psd"
+    return None
+
+
+def param_grad_served(backward_data, many: bool = False) -> bool:
+    """the node can hand its parameter gradient over from the adjoint's factors: the plain kind always, the QP / TRI / PSD kinds for many cotangents
+    (adjoint_many_params) under their own many-cotangent key -- one cotangent belongs to the pivoting kernels there (param_grad_kind)"""
+    kind = param_grad_kind(backward_data)
+    return kind == "plain" or (many and kind is not None)
 
 
 def _masked_point(saved, cots):
@@ -453,13 +475,16 @@ def adjoint_many_params(backward_data, dprimal, ddual, info, maps, out=None):
     memory.  maps: the layer's param_grad.ComposedMaps.  Returns g (K, B, Ptot + 1) batch-major on the engine's device -- written into `out` when given --, dq
     (K, B, n + 1) and the `failed` mask or None.  Applies what adjoint_many applies (device moves, the `failed` mask, the saved lsqr rule and q_eval,
     note_adjoint_flags on the OR over the cotangents, info["adjoint"]["status"] as (K, B), info["adjoint"]["path"] == "ce_vjp_many_params") and calls
-    ConeEngine.vjp_many_params.  The node must be served (param_grad_served): NotImplementedError otherwise, before anything is enqueued."""
+    ConeEngine.vjp_many_params.  A native QP, exponential / power cones or PSD blocks are served under the node's own many-cotangent key (qp_adjoint / tri_adjoint /
+    psd_adjoint = "search_free"): the entry of that kind, named by info["adjoint"]["path"]; the maps of a QP carry its P map.  The node must be served
+    (param_grad_served(many=True)): NotImplementedError otherwise, before anything is enqueued."""
     saved, batch_size, _unbatched, _in_device = backward_data
     if saved is None:
         raise RuntimeError("adjoint_many_params called on a layer evaluated with needs_grad=False")
-    if not param_grad_served(backward_data):
-        raise NotImplementedError("MI355 solver: this node has no parameter gradient from the adjoint's factors (PSD / exponential / power cones, a quadratic "
-                                  "objective, n > 108, a shared A, CE_BWD_NS=0, or a solver_args mode other than the default); use adjoint_many")
+    kind = param_grad_kind(backward_data)
+    if kind is None:
+        raise NotImplementedError("MI355 solver: this node has no parameter gradient from the adjoint's factors (PSD / exponential / power cones or a quadratic "
+                                  "objective without the kind's many-cotangent key, n > 108, a shared A, CE_BWD_NS=0, or a solver_args mode other than the default); use adjoint_many")
     eng = saved.eng
     ref = dprimal if dprimal is not None else ddual
     K = int(ref.shape[0])
@@ -468,7 +493,8 @@ def adjoint_many_params(backward_data, dprimal, ddual, info, maps, out=None):
         dx = dprimal.to(**f64).contiguous() if dprimal is not None else torch.zeros((K, batch_size, eng.n), **f64)
         dy = ddual.to(**f64).contiguous() if ddual is not None else None
         x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
-        g, dq, adj = eng.vjp_many_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, out=out)
+        g, dq, adj = eng.vjp_many_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, out=out, P_bm=saved.P_bm if kind == "qp" else None,
+                                         qp_many=kind == "qp", tri_many=kind == "tri", psd_many=kind == "psd")
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
             info["adjoint"]["path"] = eng.last_vjp_kernel

@@ -122,9 +122,12 @@ def param_grad(merged_args: dict) -> str:
     "factors" -> the adjoint kernels keep their small solution (r_x, r_y, r_tau) per (cotangent, instance) pair and one streaming kernel applies the transposed maps
     to the dA entries it evaluates from them: no dA in memory (ce_vjp_many_params behind CvxpyLayer.jacobian(direction="reverse"), ce_vjp_params behind
     .backward(); info["adjoint"]["param_grad"] == "factors").  A parameter with one map entry gets the same bits, the others agree within their terms' rounding.
-    Served where ce_param_grad_variant >= 0 on the default adjoint mode (plain cones, a linear objective, n <= 108, per-instance A); every other template or
-    path -- PSD / exponential / power cones, a quadratic objective, mode "dense" / "lsqr" / "lsmr" / the LPGD family, a shared A, CE_BWD_NS=0, forward-mode AD --
-    ignores the key with one notice and runs the dA route.  The plugin boundary (_CvxpyLayer.apply) has no parameters and ignores it."""
+    Served where ce_param_grad_variant >= 0 on the default adjoint mode (plain cones, a linear objective, n <= 108, per-instance A).  A native quadratic
+    objective, exponential / power cones and PSD blocks are served for MANY cotangents (jacobian in the reverse direction) when the layer's own many-cotangent key
+    is set beside this one -- qp_adjoint / tri_adjoint / psd_adjoint = "search_free": ce_vjp_qp_many_params / ce_vjp_tri_many_params / ce_vjp_psd_many_params /
+    ce_vjp_psd_tri_many_params; one cotangent belongs to the pivoting kernels there.  Every other template or path -- those kinds without their key or with one
+    cotangent, mode "dense" / "lsqr" / "lsmr" / the LPGD family, a shared A, CE_BWD_NS=0, forward-mode AD -- ignores the key with one notice and runs the dA
+    route.  The plugin boundary (_CvxpyLayer.apply) has no parameters and ignores it."""
     mode = merged_args.get("param_grad", "dA")
     if not isinstance(mode, str) or mode not in ("dA", "factors"):
         raise ValueError(f"MI355 solver: param_grad must be 'dA' or 'factors', got {mode!r}")

@@ -413,28 +413,52 @@ class CvxpyLayer(torch.nn.Module):
         self._pg = None          # (_pg_maps)
 
     def _pg_maps(self):
-        """the layer's transposed parameter maps composed for k_param_grad (interfaces/param_grad.py), built on first use"""
+        """the layer's transposed parameter maps composed for k_param_grad (interfaces/param_grad.py), built on first use.  The row of the constant column is left
+        empty: the layer never reads that column of g (jacobian slices by col_offsets, the ones column of p_bm has no gradient), yet it holds every constant entry
+        of A.  A native QP's transposed P map goes in with P's structure: the one-triangle doubling, or the transpose of the plugin's symmetrisation of a full
+        structure, in the values."""
         if self._pg is None:
             from cvxpylayers_amd.interfaces.param_grad import ComposedMaps
             tpl = self.template
-            self._pg = ComposedMaps(self._A.matT, self._q.matT, tpl.A_structure[0], tpl.A_structure[1], int(tpl.q_map.shape[0]) - 1, int(tpl.A_structure[2][0]))
+            own = lambda matT: sp.vstack([sp.csr_array(matT)[:-1], sp.csr_array((1, matT.shape[1]))], format="csr")          # (the constant column's row, emptied)
+            p_args = ()
+            quad = getattr(self.ctx.solver_ctx, "quad", None)
+            if self._P is not None and quad is not None and quad.sym_perm is not None:
+                p_args = (own(self._P.matT), quad.p_rows, quad.p_cols, quad.one_triangle, None if quad.one_triangle else quad.sym_perm)
+            self._pg = ComposedMaps(own(self._A.matT), own(self._q.matT), tpl.A_structure[0], tpl.A_structure[1], int(tpl.q_map.shape[0]) - 1, int(tpl.A_structure[2][0]), *p_args)
         return self._pg
 
-    def _param_grad_route(self, merged: dict, device, forward_ad: bool = False) -> bool:
+    def _param_grad_route(self, merged: dict, device, forward_ad: bool = False, many: bool = False) -> bool:
         """solver_args param_grad == "factors" AND this layer is served on `device` as far as the template and the arguments decide it (the engine's path of a
-        call -- a shared A -- is known only behind the solve).  Not served: one notice, the dA route."""
-        from cvxpylayers_amd.interfaces.solver_args import _warn_once, adjoint_mode, lpgd_rule, param_grad
+        call -- a shared A -- is known only behind the solve).  many: the call makes many-cotangent calls (jacobian in the reverse direction), where a native QP,
+        exponential / power cones and PSD blocks are served under their own key (qp_adjoint / tri_adjoint / psd_adjoint = "search_free"); one cotangent
+        (.backward(), forward-mode AD) belongs to the pivoting kernels there, as those keys say.  Not served: one notice, the dA route."""
+        from cvxpylayers_amd import _lib
+        from cvxpylayers_amd.interfaces.solver_args import _warn_once, adjoint_mode, lpgd_rule, param_grad, psd_adjoint, qp_adjoint, tri_adjoint
         if param_grad(merged) != "factors":
             return False
         why = None
-        if self._P is not None or self.template.gp:
+        eng = None if self.template.gp else self.ctx.solver_ctx.engine(device)
+        h = None if eng is None else eng._h
+        L = _lib.lib()
+        if self.template.gp:
             why = "a quadratic objective or a gp=True layer"
         elif adjoint_mode(merged) != "direct" or lpgd_rule(merged) is not None:
             why = f"solver_args mode={merged.get('mode')!r}"
         elif forward_ad:
             why = "forward-mode AD"
-        elif self.ctx.solver_ctx.engine(device).param_grad_variant < 0:
-            why = "this template (PSD / exponential / power cones, n > 108, or CE_BWD_NS=0)"
+        elif self._P is not None:
+            if qp_adjoint(merged) != "search_free" or L.ce_vjp_qp_many_variant(h) < 0:
+                why = "a quadratic objective or a gp=True layer"
+            elif not many:
+                why = "one cotangent through a quadratic objective (qp_adjoint='search_free' serves jacobian(direction='reverse') alone)"
+        elif eng.param_grad_variant < 0:
+            tri = tri_adjoint(merged) == "search_free" and L.ce_vjp_tri_many_variant(h) >= 0
+            psd = psd_adjoint(merged) == "search_free" and (L.ce_vjp_psd_many_variant(h) >= 0 or L.ce_vjp_psd_tri_many_variant(h) >= 0)
+            if not (tri or psd):
+                why = "this template (PSD / exponential / power cones without tri_adjoint / psd_adjoint='search_free', n > 108, or CE_BWD_NS=0)"
+            elif not many:
+                why = "one cotangent on this template (tri_adjoint / psd_adjoint='search_free' serve jacobian(direction='reverse') alone)"
         if why is None:
             return True
         _warn_once("param_grad_unserved", f"MI355 solver: solver_args param_grad='factors' is not served for {why}; the dA route runs (the key is ignored)")
@@ -635,9 +659,10 @@ class CvxpyLayer(torch.nn.Module):
             n_out = sum(int(self._rec[src][0].mat.shape[0]) for src in self._rec)
             forward = direction == "forward" or (direction == "auto" and tpl.n_params_total < n_out)
             # solver_args param_grad="factors", reverse direction: one adjoint_many_params call per chunk straight into g_all[t0:t1] -- no dA; a chunk holds its
-            # factor records and dq, B ((m + 1 + n) + (n + 1)) 8 bytes per cotangent (the records keep r_x beside r_y and r_tau), g_all is the result itself
-            factors = want_factors and not forward and self._param_grad_route(merged, dev)
-            if factors and not param_grad_served(data):          # (the engine took another path for this call: a shared A decided from the values)
+            # factor records and dq, B ((m + 1 + n) + (n + 1)) 8 bytes per cotangent (the records keep r_x beside r_y and r_tau), g_all is the result itself.  The
+            # same for a native QP, exponential / power cones and PSD blocks under their own many-cotangent key (no dP is counted: none is written)
+            factors = want_factors and not forward and self._param_grad_route(merged, dev, many=True)
+            if factors and not param_grad_served(data, many=True):          # (the engine took another path for this call: a shared A decided from the values)
                 _warn_once("param_grad_unserved", "MI355 solver: solver_args param_grad='factors' is not served on the path this call took; the dA route runs (the key is ignored)")
                 factors = False
             if factors:

@@ -91,7 +91,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -571,6 +571,35 @@ int ce_param_grad_variant(ce_handle h);
  * r_y[0 .. m), r_tau, r_x[0 .. n).  r_tau is 0 on the elimination path and LSQR's on a re-solved pair; g and dq do not determine it.  CE_E_STATE when no call of at
  * least this size has run. */
 int ce_param_grad_records(ce_handle h, int B, int K, double *out, void *stream);
+
+/* THE SAME FOR THE OTHER MANY-COTANGENT KINDS (additions under ABI 17).  Each entry is its kind's many-cotangent adjoint in record mode -- the record is the plain
+ * kind's, r_y in the ORIGINAL basis (behind the triples' and the blocks' rotation), r_tau = 0 on the elimination path, r_x -- and k_param_grad behind it:
+ *   ce_vjp_tri_many_params / ce_vjp_psd_many_params / ce_vjp_psd_tri_many_params: the arguments, layouts and rules of ce_vjp_many_params; served exactly where
+ *       ce_vjp_tri_many_variant / ce_vjp_psd_many_variant / ce_vjp_psd_tri_many_variant (h) >= 0, with the re-solve armed (q_vals given).  A flagged instance is
+ *       re-solved by LSQR per cotangent (4 | 8) and its records hold LSQR's (r_y, r_tau, r_x).
+ *   ce_vjp_qp_many_params: ce_vjp_qp_many's inputs with the map and g in place of dA_vals / dP_vals; served where ce_vjp_qp_many_variant(h) >= 0.  Neither dA nor dP
+ *       is written.  No re-solve: a rank-deficient instance keeps the dropped-variable answer with status 4, exactly as ce_vjp_qp_many.  The map may carry entries of dP:
+ *         map_code < 0 with bit 30 CLEAR: entry j = map_code & 0x3fffffff of dq (as above: n < 2^15)
+ *         map_code < 0 with bit 30 SET  : entry map_k of P's structure order, packed (i, j) = (map_code & 0x7fff, map_code >> 15 & 0x7fff): the value is ONE share
+ *                                         -1/2 (r_x,i x_j + r_x,j x_i); ce_vjp_qp_many's doubling of a one-triangle entry with i != j (and a frontend's symmetrisation)
+ *                                         belongs in map_val.  Per row the P entries stand behind the q entries.
+ * Every entry refuses a handle of another kind with CE_E_UNSUPPORTED before anything is enqueued and writes nothing; ce_vjp_many_params, ce_vjp_params and
+ * ce_param_grad_variant keep refusing every handle that is not plain.  ce_param_grad_records serves the last call of any kind. */
+int ce_vjp_tri_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                           const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                           int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                           double *g, double *dq_vals, int *adj_status, void *stream);
+int ce_vjp_psd_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                           const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                           int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                           double *g, double *dq_vals, int *adj_status, void *stream);
+int ce_vjp_psd_tri_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                               const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                               int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                               double *g, double *dq_vals, int *adj_status, void *stream);
+int ce_vjp_qp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                          const double *dx, const double *dy, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                          double *g, double *dq_vals, int *adj_status, void *stream);
 
 /* MANY TANGENTS AT ONE SOLUTION: for every k < K what ce_jvp (ce_jvp_qp) returns for the k-th tangent, from ONE factorisation per instance -- the forward twin of
  * ce_vjp_many, and the route by which a layer with few parameters and many outputs, or a native QP layer, gets its Jacobian by columns.  The matrix work is the
