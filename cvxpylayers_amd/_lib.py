@@ -18,7 +18,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_vjp_qp_many_params", "ce_vjp_tri_many_params", "ce_vjp_psd_many_params", "ce_vjp_psd_tri_many_params",
            "ce_jvp_psd_tri", "ce_refine_psd_tri", "ce_vjp_psd_tri_many", "ce_jvp_psd_tri_many", "ce_psd_tri_ns_variant", "ce_psd_tri_ns_lds", "ce_vjp_psd_tri_many_variant", "ce_jvp_psd_tri_many_variant",
            "ce_value", "ce_value_jvp", "ce_value_vjp", "ce_lpgd_perturb", "ce_lpgd_grad", "ce_set_transient_solve", "ce_check_solved",
-           "ce_cones_create", "ce_cones_destroy", "ce_cones_rows", "ce_cones_state_len", "ce_cone_project", "ce_cone_dproject"]
+           "ce_cones_create", "ce_cones_destroy", "ce_cones_rows", "ce_cones_state_len", "ce_cone_project", "ce_cone_dproject",
+           "ce_solve_wave", "ce_wave_variant", "ce_wave_lds", "ce_wave_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -76,6 +77,8 @@ def lib():
     L.ce_destroy.argtypes = [vp]
     L.ce_last_error.restype = C.c_char_p
     L.ce_solve.argtypes = [vp, C.c_int, dp, lg, lg, dp, lg, lg, C.POINTER(CeSettings), dp, dp, dp, ip, ip, dp, vp]
+    L.ce_solve_wave.argtypes = L.ce_solve.argtypes
+    L.ce_wave_variant.argtypes = [vp]; L.ce_wave_lds.argtypes = [vp]; L.ce_wave_occupancy.argtypes = [vp]
     L.ce_vjp.argtypes = [vp, C.c_int, dp, lg, lg, dp, lg, lg, dp, dp, dp, dp, dp, dp, lg, lg, dp, lg, lg, ip, vp]
     L.ce_solve_shared_a.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, ip, ip, dp, ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, C.POINTER(CeSettings),
                                     dp, dp, dp, dp, dp, dp, ip, ip, dp, vp]

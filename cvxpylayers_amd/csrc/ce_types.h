@@ -275,6 +275,9 @@ int ce_launch_fwd2_psd(int variant, int B, size_t lds, hipStream_t st, const CeF
 int ce_launch_fwd2_qp(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);      // quadratic objective inside the kernel
 int ce_launch_fwd_rt(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
+// ce_tu_fwd_wave.hip: k_fwd_wave, one instance per wave (row of CE_WAVE_VARIANTS, ce_variants_wave.h); the resident workgroups per CU of a row
+int ce_launch_fwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
+hipError_t ce_occupancy_fwd_wave(int variant, size_t lds, int *blocks);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
 // search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement

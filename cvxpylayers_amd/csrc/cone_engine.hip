@@ -35,6 +35,7 @@
 #include "cone_engine.h"
 #include "ce_types.h"
 #include "ce_plan.h"           // the launch plan (host only): CePlan, plan_engine, the shared-A selectors, the footprints of every kernel family
+#include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
 
 namespace {
 // the kernels this file launches itself; every other family is instantiated in its own translation unit (ce_tu_*.hip) and reached through the launchers of ce_types.h
@@ -98,6 +99,7 @@ struct ce_engine {
     DevBuf<double> wsdA;         // batch-major dA              [B][nnz_aug]
     DevBuf<double> gws;          // global residency fallback
     const double *retained_A = nullptr; int retained_B = 0;
+    int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
     DevBuf<int> d_idx_at, d_idx_ar, d_idx_b;       // k_fwd2: gather maps of the two register tiles of A and of b
@@ -302,6 +304,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     index_csr_split(tpl, *h, X);
     rc = plan_engine(tpl, h->T, h->nnz_p, read_plan_env(), h->plan);
     if (rc) return rc;
+    h->wave_variant = fwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+    h->wave_lds = h->wave_variant >= 0 ? fwd_wave_lds_bytes(h->wave_variant, tpl->n, tpl->m) : 0;
     h->T.f2_neumann = h->plan.f2_neumann; h->T.gen_blocked_f = h->plan.gen_blocked_f; h->T.gen_blocked_b = h->plan.gen_blocked_b;
     GatherMaps G;
     if (h->plan.fwd_mode == FWD_V2) build_gather_maps(tpl, *h, G);
@@ -486,6 +490,44 @@ int ce_solve_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, 
     }
     HIPCHK(hipGetLastError());
     if (fa_iters2) { h->order_pending_B = B; h->last_status = status; }          // (computed by flush_dispatch_order, off the critical path)
+    return CE_OK;
+}
+
+// k_fwd_wave: one instance per wave, for the small templates fwd_wave_variant serves (ce_lds_fwd_wave.h).  The arguments, layouts and retention of ce_solve; the
+// dispatch history is left alone (the kernel takes the instances in index order)
+int ce_wave_variant(ce_handle h) { return h ? h->wave_variant : -1; }
+int ce_wave_lds(ce_handle h) { return (h && h->wave_variant >= 0) ? (int)h->wave_lds : 0; }
+int ce_wave_occupancy(ce_handle h) {
+    if (!h || h->wave_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_fwd_wave(h->wave_variant, h->wave_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_solve_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                  const ce_settings *settings, double *x, double *y, double *s, int *iters, int *status, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals || !q_vals || !x || !y || !s || !iters || !status) { g_err = "null argument"; return CE_E_BADARG; }
+    if (h->wave_variant < 0) {
+        g_err = std::string("ce_solve_wave: ") + fwd_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_solve";
+        return CE_E_UNSUPPORTED;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    ce_settings S; if (settings) S = *settings; else ce_default_settings(&S);
+    if (S.acceleration_interval <= 0) S.acceleration_interval = 10;
+    const double *Abm = nullptr;
+    const bool transient = h->transient_solve;
+    if (transient && !(sA_k == 1 && sA_b == h->T.nnz_aug)) { g_err = "transient solve: A_vals must be batch-major (the layout workspace may hold the retained forward inputs)"; return CE_E_BADARG; }
+    int rc = to_batch_major(h, B, A_vals, sA_k, sA_b, st, &Abm);
+    if (rc) return rc;
+    if (!transient) { h->retained_A = Abm; h->retained_B = B; }
+    {
+        ProfScope ps(h, 0, st);
+        CeFwdArgs fa{};
+        fa.T = h->T; fa.S = S; fa.Abm = Abm; fa.q = q_vals; fa.sqk = sq_k; fa.sqb = sq_b;
+        fa.x = x; fa.y = y; fa.s = s; fa.iters = iters; fa.status = status; fa.resid = resid;
+        if (ce_launch_fwd_wave(h->wave_variant, B, h->wave_lds, st, fa)) { g_err = "internal: no wave kernel for the selected row"; return CE_E_BADARG; }
+    }
+    HIPCHK(hipGetLastError());
     return CE_OK;
 }
 

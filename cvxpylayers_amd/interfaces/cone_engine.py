@@ -41,6 +41,7 @@ class ConeEngine:
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
+        self.last_forward_kernel = None       # "k_fwd_wave" when the last solve() ran the one-instance-per-wave kernel (solve(wave=True)), None otherwise
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
@@ -125,11 +126,18 @@ class ConeEngine:
         _lib.check(_lib.lib().ce_transpose(self._h, K, B, A_eval.data_ptr(), out.data_ptr(), self._stream()), "ce_transpose")
         return out
 
-    def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None):
+    def wave_plan(self):
+        """(variant, lds) of the one-instance-per-wave forward kernel k_fwd_wave on this template: the row of csrc/ce_variants_wave.h that serves it (-1: not
+        served -- a P structure, a PSD / exponential / power cone, n > 32 or m > 64) and the launch's LDS bytes (0 when not served)."""
+        L = _lib.lib()
+        return int(L.ce_wave_variant(self._h)), int(L.ce_wave_lds(self._h))
+
+    def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None, wave: bool = False):
         """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
         warm = (x, y, s) of shapes (B, n), (B, m), (B, m): initial point (instances with non-finite entries start cold).
         path: None -- the dispatcher decides (per instance / shared A); "const_a" or "per_instance": the path a caller already knows (solve_transient: the
-        perturbed solves of a backward follow their forward's path without comparing values again)."""
+        perturbed solves of a backward follow their forward's path without comparing values again).
+        wave: run ce_solve_wave (k_fwd_wave, one instance per wave; per-instance A, wave_plan()[0] >= 0) instead of ce_solve; an engine it does not serve raises."""
         B = A_bm.shape[0]
         dev = self.device
         if B == 0:        # empty batch: nothing to launch (the C ABI refuses B <= 0)
@@ -146,12 +154,15 @@ class ConeEngine:
         # direct engine users (tests, probes): vjp() without q_eval may use the objective of the most recent solve() -- but only for the SAME value buffer
         # (the plugin always passes q_eval explicitly; a q paired with another call's A would silently change the full adjoint system: ADVICE round 5)
         self._last_q, self._last_q_key = q_eval.detach(), (A_bm.data_ptr(), B)
-        if P_bm is None and (path == "const_a" if path is not None else self._use_const_a(A_bm)):
+        self.last_forward_kernel = "k_fwd_wave" if wave else None
+        if wave and P_bm is not None:
+            raise RuntimeError("solve(wave=True): the wave kernel serves a linear objective")
+        if not wave and P_bm is None and (path == "const_a" if path is not None else self._use_const_a(A_bm)):
             from cvxpylayers_amd.interfaces.const_a import solve_const_a
             self.last_path = "const_a"
             return solve_const_a(self, A_bm, q_eval, settings, warm=warm)      # (notes itself whether its kernel honours the acceleration)
         self.last_path = "per_instance"
-        self._note_acceleration(settings, honoured=bool(_lib.lib().ce_acceleration_available(self._h)), path="size-generic forward kernels")
+        self._note_acceleration(settings, honoured=wave or bool(_lib.lib().ce_acceleration_available(self._h)), path="size-generic forward kernels")
         if warm is not None:       # the engine reads the initial point from the output buffers (ce_settings.warm_start)
             x, y, s = (t.detach().to(device=dev, dtype=torch.float64).clone().contiguous() for t in warm)
             settings.warm_start = 1
@@ -167,6 +178,11 @@ class ConeEngine:
             rc = _lib.lib().ce_solve_qp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
                                         q_eval.stride(1), P_bm.data_ptr(), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
                                         iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
+        elif wave:
+            rc = _lib.lib().ce_solve_wave(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
+                                          q_eval.stride(1), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                          iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
+            _lib.check(rc, "ce_solve_wave")
         else:
             rc = _lib.lib().ce_solve(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
                                      q_eval.stride(1), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
@@ -176,7 +192,7 @@ class ConeEngine:
 
     # what solve() records on the engine about "the most recent solve" (introspection, _recent_q, the one-time acceleration warning)
     # (_aa_warned is NOT among them: the once-per-engine acceleration warning stays said when a perturbed solve was the one to say it)
-    _SOLVE_TRACE = ("last_path", "last_acceleration", "last_const_a_kernel", "_last_q", "_last_q_key")
+    _SOLVE_TRACE = ("last_path", "last_forward_kernel", "last_acceleration", "last_const_a_kernel", "_last_q", "_last_q_key")
 
     def solve_transient(self, A_bm, q_eval, settings, warm=None, P_bm=None, path: str | None = None):
         """solve() that leaves no trace: the handle keeps the retained inputs and the dispatch history of the last ordinary solve (ce_set_transient_solve),

@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_mode, dims_to_solver_dict, forward_kernel, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -173,6 +173,7 @@ class _ConeLayer(torch.autograd.Function):
             q_eval = q_eval.unsqueeze(1)
         in_device = A_eval.device
         dev = in_device if in_device.type == "cuda" else ctx.default_device
+        fwd_kernel = forward_kernel({**ctx.options, **(solver_args or {})})          # (validated before the device is touched)
         if not torch.cuda.is_available():
             raise RuntimeError("MI355 solver needs a ROCm GPU; there is no CPU fallback (use solver='DIFFCP' on CPU)")
         eng = ctx.engine(dev)
@@ -212,6 +213,14 @@ class _ConeLayer(torch.autograd.Function):
                 P_bm = P_eval.detach().to(device=dev, dtype=torch.float64).t().contiguous()        # (B, nnz_p)
             # solver_args newton_first with a warm start: Newton steps from it, the termination test, and the forward kernels for the instances that miss it
             # (newton_first.py: one 4-byte host read, also under raise_on_error=False); everything below sees the final full-batch result
+            # solver_args forward_kernel="wave": one instance per wave where k_fwd_wave serves the template and the solve is per-instance; said once elsewhere
+            wave = False
+            if fwd_kernel == "wave":
+                wave = (P_bm is None and eng.wave_plan()[0] >= 0 and not (n_newton > 0 and warm is not None) and not eng._use_const_a(A_bm))
+                if not wave:
+                    _warn_once("forward_kernel_none", "MI355 solver: solver_args forward_kernel='wave' is ignored on this template or path: the wave kernel serves a linear "
+                                                      "objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a per-instance A, and not the remainder "
+                                                      "solve of newton_first; the ordinary kernel ran (info['forward']['kernel'] == 'workgroup')")
             nf_info = None
             if n_newton > 0 and warm is not None and batch_size > 0:
                 (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns)
@@ -219,7 +228,7 @@ class _ConeLayer(torch.autograd.Function):
                     _warn_once("newton_first_none", "MI355 solver: solver_args newton_first needs the search-free elimination, which this template or path does not have "
                                                     "(PSD cones, n > 108, a shared A); the ordinary warm-started solve ran (info['newton_first']['path'] == 'none')")
             else:
-                x, y, s, iters, status, resid = eng.solve(A_bm, q_dev, settings, warm=warm, P_bm=P_bm)
+                x, y, s, iters, status, resid = eng.solve(A_bm, q_dev, settings, warm=warm, P_bm=P_bm, **({"wave": True} if wave else {}))
                 if n_newton > 0:
                     nf_info = not_served(n_newton, batch_size)          # (no warm start: nothing to step from, said in info alone)
             path = adjoint_path(eng.last_path, P_bm is not None, merged_args)          # recorded per call: the backward of THIS node must not follow a later solve's path
@@ -251,6 +260,8 @@ class _ConeLayer(torch.autograd.Function):
             # info["adjoint"] is filled by backward(): "status" = the per-instance bit field of include/cone_engine.h ce_vjp (4: rank-deficient system, 8: gradients
             # are diffcp's LSQR element from the device-side re-solve); adjoint_report(info) counts them
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
+            if fwd_kernel == "wave":
+                info["forward"] = {"kernel": "k_fwd_wave" if wave else "workgroup"}
             if refine_info is not None:
                 info["refine"] = refine_info
             if nf_info is not None:

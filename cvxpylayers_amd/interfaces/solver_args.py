@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad", "forward_kernel"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -233,6 +233,20 @@ def psd_many_active(key: str, asked: bool, psd_ns_variant: int, has_psd: bool) -
         _warn_once(key + "_none", f"MI355 solver: solver_args {key} is ignored on this template: the search-free elimination does not serve it (a quadratic objective "
                                   "beside the PSD blocks, n > 108, or its footprint exceeds LDS)")
     return False
+
+
+def forward_kernel(merged_args: dict) -> str:
+    """Which kernel solves the forward problem of a PER-INSTANCE-A template:
+    absent / "workgroup" -> the ordinary kernels: one instance per workgroup of 256 or 512 threads (k_fwd2, k_forward_rt, the size-generic kernel);
+    "wave" -> k_fwd_wave (ce_solve_wave): one instance per wave, for small templates -- a linear objective, zero / nonnegative / second-order cones, n <= 32,
+    m <= 64 (ConeEngine.wave_plan()[0] >= 0).  The same algorithm and settings, so the same statuses, points within the solver's tolerance and iteration counts
+    within a check interval; cold solves, warm starts and raise_on_error=False alike.  info["forward"]["kernel"] tells which ran ("k_fwd_wave" / "workgroup").
+    Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger template, a shared A, the remainder solve of newton_first --
+    ignores the key with one notice and runs the ordinary kernel; LPGD's perturbed re-solves always run the ordinary kernel."""
+    mode = merged_args.get("forward_kernel", "workgroup")
+    if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
+        raise ValueError(f"MI355 solver: forward_kernel must be 'workgroup' or 'wave', got {mode!r}")
+    return mode
 
 
 def refine_steps(merged_args: dict) -> int:

@@ -12,6 +12,7 @@
  *   ce_solve    <- _build_diffcp_matrices + diffcp.solve_and_derivative_batch / solve_only_batch
  *                  (diffcp_if.py:46-70, 365-372): cuts (A,b,c) out of A_eval / q_eval, A = -A_cvx,
  *                  solves every instance, returns primal (B,n), dual (B,m) (+ slack, status).
+ *   ce_solve_wave <- the same call site, opt-in for small templates (one instance per wave; see its declaration)
  *   ce_vjp      <- _compute_gradients -> adj_batch(dxs, dys, dss=0)   (diffcp_if.py:73-96, 385-403):
  *                  returns d/dA_eval = [-dA.data, db[b_idx]] and d/dq_eval = [dc, 0].
  *   ce_destroy  <- (garbage collection of DIFFCP_ctx)
@@ -91,7 +92,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params, and ce_solve_wave, ce_wave_variant, ce_wave_lds and ce_wave_occupancy; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -123,6 +124,29 @@ int ce_solve(ce_handle h, int B,
              const ce_settings *settings,
              double *x, double *y, double *s, int *iters, int *status, double *resid,
              void *stream);
+
+/*
+ * The same solve, ONE INSTANCE PER WAVE, for small templates (k_fwd_wave; no reference call site: the reference calls SCS per instance whatever the size; additions
+ * under ABI 17).  ce_solve gives every instance a workgroup of 256 or 512 threads, whose barriers leave a template of a few tens of rows idle; here a 64-thread
+ * workgroup solves an instance, with no workgroup barrier, its vectors in registers and A-hat and the inverse of the reduced matrix in its own LDS.
+ *   served      : a linear objective (no P structure), zero / nonnegative / second-order cones of any dimensions, n <= 32, m <= 64, any sparsity pattern.
+ *   ce_solve_wave   : arguments, layouts, outputs, status codes, warm start and retention (ce_vjp with A_vals == NULL) of ce_solve; every ce_settings field is honoured
+ *                     (acceleration: one secant pair for any positive lookback).  The dispatch history of ce_set_dispatch_history is neither read nor written: the
+ *                     kernel takes the instances in index order.  CE_E_UNSUPPORTED on a handle it does not serve, before anything is enqueued and with nothing
+ *                     written; ce_last_error names the reason.
+ *   ce_wave_variant : the row of the kernel's instantiation list (csrc/ce_variants_wave.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_wave_lds     : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_wave_occupancy: resident workgroups (= instances) per CU of that row at that footprint, as the runtime's occupancy query reports it (0 when not served).
+ */
+int ce_solve_wave(ce_handle h, int B,
+                  const double *A_vals, long sA_k, long sA_b,
+                  const double *q_vals, long sq_k, long sq_b,
+                  const ce_settings *settings,
+                  double *x, double *y, double *s, int *iters, int *status, double *resid,
+                  void *stream);
+int ce_wave_variant(ce_handle h);
+int ce_wave_lds(ce_handle h);
+int ce_wave_occupancy(ce_handle h);
 
 /*
  * Backward (vector-Jacobian product), diffcp adjoint with ds = 0 (diffcp_if.py:84).
