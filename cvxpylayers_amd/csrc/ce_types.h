@@ -278,6 +278,9 @@ int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeF
 // ce_tu_fwd_wave.hip: k_fwd_wave, one instance per wave (row of CE_WAVE_VARIANTS, ce_variants_wave.h); the resident workgroups per CU of a row
 int ce_launch_fwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 hipError_t ce_occupancy_fwd_wave(int variant, size_t lds, int *blocks);
+// ce_tu_bwd_wave.hip: k_bwd_wave, the adjoint of one instance per wave (row of CE_BWD_WAVE_VARIANTS, ce_variants_bwd_wave.h; reads CeBwdArgs' dA_factors itself)
+int ce_launch_bwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
+hipError_t ce_occupancy_bwd_wave(int variant, size_t lds, int *blocks);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
 // search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement

@@ -36,6 +36,7 @@
 #include "ce_types.h"
 #include "ce_plan.h"           // the launch plan (host only): CePlan, plan_engine, the shared-A selectors, the footprints of every kernel family
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
+#include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
 
 namespace {
 // the kernels this file launches itself; every other family is instantiated in its own translation unit (ce_tu_*.hip) and reached through the launchers of ce_types.h
@@ -100,6 +101,8 @@ struct ce_engine {
     DevBuf<double> gws;          // global residency fallback
     const double *retained_A = nullptr; int retained_B = 0;
     int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
     DevBuf<int> d_idx_at, d_idx_ar, d_idx_b;       // k_fwd2: gather maps of the two register tiles of A and of b
@@ -306,6 +309,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     if (rc) return rc;
     h->wave_variant = fwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->wave_lds = h->wave_variant >= 0 ? fwd_wave_lds_bytes(h->wave_variant, tpl->n, tpl->m) : 0;
+    h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+    h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
     h->T.f2_neumann = h->plan.f2_neumann; h->T.gen_blocked_f = h->plan.gen_blocked_f; h->T.gen_blocked_b = h->plan.gen_blocked_b;
     GatherMaps G;
     if (h->plan.fwd_mode == FWD_V2) build_gather_maps(tpl, *h, G);
@@ -543,6 +548,27 @@ int ce_vjp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const
     return rc;
 }
 
+// k_bwd_wave: the adjoint of one instance per wave, for the small templates bwd_wave_variant serves (ce_lds_bwd_wave.h).  ce_vjp's / ce_vjp_params' arguments and
+// the whole of their body (ce_vjp_qp: layouts, retained A, the re-solve lists and the LSQR launch, the factor mode, k_expand_dA, k_param_grad) with the wave kernel
+// in the place of k_backward_ns; refused where the handle is not served or the re-solve is not armed.
+int ce_bwd_wave_variant(ce_handle h) { return h ? h->bwd_wave_variant : -1; }
+int ce_bwd_wave_lds(ce_handle h) { return (h && h->bwd_wave_variant >= 0) ? (int)h->bwd_wave_lds : 0; }
+int ce_bwd_wave_occupancy(ce_handle h) {
+    if (!h || h->bwd_wave_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_bwd_wave(h->bwd_wave_variant, h->bwd_wave_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_vjp_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream) {
+    if (!h) { g_err = "null argument"; return CE_E_BADARG; }
+    h->call_wave = "ce_vjp_wave";
+    const int rc = ce_vjp(h, B, A_vals, sA_k, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, sdA_k, sdA_b, dq_vals, sdq_k, sdq_b, adj_status, stream);
+    h->call_wave = nullptr;
+    return rc;
+}
+
 static int vjp_lsqr_launch(ce_handle h, int B, const double *A_vals0, long sA_b, int per_inst, const double *q_vals, long sq_k, long sq_b,
                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
                            double *dA_bm, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream,
@@ -584,6 +610,18 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     if (!h || B <= 0 || !x || !y || !s || !dx || !dy || (!dA_vals && !pg) || !dq_vals) { g_err = "null argument"; return CE_E_BADARG; }
     const CePlan &P = h->plan;
     if ((P_vals != nullptr) != P.qp_native || (P_vals && !dP_vals)) { g_err = "quadratic objective: P_vals / dP_vals must be given exactly when ce_qp_native(h) == 1"; return CE_E_BADARG; }
+    const bool wave = h->call_wave != nullptr;
+    if (wave) {          // (refused before anything is enqueued, nothing written)
+        if (h->bwd_wave_variant < 0) {
+            g_err = std::string(h->call_wave) + ": " + bwd_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use " + (pg ? "ce_vjp_params" : "ce_vjp");
+            return CE_E_UNSUPPORTED;
+        }
+        if (!(h->resolve && h->call_q && resolve_fits(h))) {
+            g_err = std::string(h->call_wave) + ": the LSQR re-solve of flagged instances is not armed for this call (q_vals == NULL, ce_set_adjoint_resolve(h, 0), or its "
+                    "vectors do not fit LDS), and the wave kernel's dropped-variable answer is never final; use " + (pg ? "ce_vjp_params" : "ce_vjp");
+            return CE_E_UNSUPPORTED;
+        }
+    }
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const DevT &T = h->T;
@@ -613,8 +651,8 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     // again by the layout pass; the adjoint stores r_y at the head of the instance's row of wsdA, where a re-solved instance's whole row lands as before.  The
     // expansion tells the two apart by bit 8 of adj_status, so a call without one keeps the layout pass (as does a template whose tile exceeds the kernel's LDS).
     ExpandPlan ex{};
-    const bool factors = pg ? true : (need_tr && do_fix && P.ns_variant >= 0 && adj_status && expand_dA_plan(T, B, &ex));
-    if (pg && !(do_fix && P.ns_variant >= 0 && adj_status && K >= T.m)) { g_err = "ce_vjp_params: internal, the factor mode is not available"; return CE_E_STATE; }
+    const bool factors = pg ? true : (need_tr && do_fix && (P.ns_variant >= 0 || wave) && adj_status && expand_dA_plan(T, B, &ex));
+    if (pg && !(do_fix && (P.ns_variant >= 0 || wave) && adj_status && K >= T.m)) { g_err = "ce_vjp_params: internal, the factor mode is not available"; return CE_E_STATE; }
     {
         ProfScope ps(h, 1, st);
         CeBwdArgs ba{};
@@ -624,7 +662,10 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         ba.p_tri = h->p_tri; ba.dP = dP_vals; ba.gA = gA; ba.gK = gK;
         int lrc;
         h->last_fast = -1;
-        if (do_fix && P.ns_variant >= 0) {
+        if (wave) {          // (do_fix holds: the entry refused otherwise)
+            ba.dA_factors = factors ? 1 : 0;
+            lrc = ce_launch_bwd_wave(h->bwd_wave_variant, B, h->bwd_wave_lds, st, ba);
+        } else if (do_fix && P.ns_variant >= 0) {
             ba.T.lda = T.n;
             ba.dA_factors = factors ? 1 : 0;
             lrc = ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, NsNoJvp{});
@@ -855,7 +896,7 @@ int ce_vjp_params(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b
                   int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
                   double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream) {
     if (!h || B <= 0 || !x || !y || !s || !dx || !dy || !g || !dq_vals || !adj_status) { g_err = "ce_vjp_params: null argument or B <= 0"; return CE_E_BADARG; }
-    int rc = pg_check(h, "ce_vjp_params", rows, map_ptr, map_code, map_k, map_val, q_vals);
+    int rc = pg_check(h, h->call_wave ? h->call_wave : "ce_vjp_params", rows, map_ptr, map_code, map_k, map_val, q_vals);
     if (rc) return rc;
     const DevT &T = h->T;
     if (T.nnz_aug < T.m) { g_err = "ce_vjp_params: a value row shorter than m cannot hold the factors (nnz_aug < m); call ce_vjp_many_params with K = 1"; return CE_E_UNSUPPORTED; }
@@ -863,6 +904,20 @@ int ce_vjp_params(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b
     h->pg = &ga; h->call_q = q_vals; h->call_sqk = sq_k; h->call_sqb = sq_b;
     rc = ce_vjp_qp(h, B, A_vals, sA_k, sA_b, nullptr, x, y, s, dx, dy, nullptr, 0, 0, dq_vals, sdq_k, sdq_b, nullptr, adj_status, stream);
     h->pg = nullptr; h->call_q = nullptr;
+    return rc;
+}
+int ce_vjp_params_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                       double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream) {
+    if (!h) { g_err = "ce_vjp_params_wave: null argument or B <= 0"; return CE_E_BADARG; }
+    if (h->bwd_wave_variant < 0) {          // (in front of ce_vjp_params' own checks: the refusal names this entry)
+        g_err = std::string("ce_vjp_params_wave: ") + bwd_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_vjp_params";
+        return CE_E_UNSUPPORTED;
+    }
+    h->call_wave = "ce_vjp_params_wave";
+    const int rc = ce_vjp_params(h, B, A_vals, sA_k, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, sdq_k, sdq_b, adj_status, stream);
+    h->call_wave = nullptr;
     return rc;
 }
 // K cotangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_vjp_many's body with k_backward_ns<..., TRI, MANY> on the

@@ -41,6 +41,7 @@ class ConeEngine:
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
+        self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), None otherwise
         self.last_forward_kernel = None       # "k_fwd_wave" when the last solve() ran the one-instance-per-wave kernel (solve(wave=True)), None otherwise
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
@@ -131,6 +132,12 @@ class ConeEngine:
         served -- a P structure, a PSD / exponential / power cone, n > 32 or m > 64) and the launch's LDS bytes (0 when not served)."""
         L = _lib.lib()
         return int(L.ce_wave_variant(self._h)), int(L.ce_wave_lds(self._h))
+
+    def bwd_wave_plan(self):
+        """(variant, lds) of the one-instance-per-wave adjoint kernel k_bwd_wave on this template: the row of csrc/ce_variants_bwd_wave.h that serves it (-1: not
+        served -- wave_plan's class) and the launch's LDS bytes (0 when not served)."""
+        L = _lib.lib()
+        return int(L.ce_bwd_wave_variant(self._h)), int(L.ce_bwd_wave_lds(self._h))
 
     def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None, wave: bool = False):
         """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
@@ -309,7 +316,8 @@ class ConeEngine:
             return bool(self.A_is_constant)
         return is_constant_A(A_bm, self.nnzA)
 
-    def vjp(self, A_bm, x, y, s, dx, dy, batch_minor_out: bool = False, P_bm=None, path: str | None = None, lsqr: tuple | None = None, q_eval=None):
+    def vjp(self, A_bm, x, y, s, dx, dy, batch_minor_out: bool = False, P_bm=None, path: str | None = None, lsqr: tuple | None = None, q_eval=None,
+            wave: bool = False):
         """Returns dA (nnz_aug, B), dq (n+1, B), adj_status (B,).  dA is a transposed view of a batch-major buffer (the
         engine-native layout, no extra pass) unless batch_minor_out: then it is (nnz_aug, B) contiguous -- the layout of a
         reference-style A_eval, so that autograd can accumulate it into the leaf without a strided copy (one engine layout pass).
@@ -317,14 +325,19 @@ class ConeEngine:
         after solve() -- the autograd node keeps it, so interleaved forward calls of one layer cannot redirect a pending backward.
         None (direct engine users with one solve in flight): the path of the most recent solve().
         lsqr: (atol, btol, iter_lim[, system]) of the shared-A LSQR adjoint (lsqr_rule); None = diffcp's 1e-8 / 1e-8 / 2 (n + m + 1) on the full system.  Ignored by the direct eliminations.
-        q_eval: the forward call's (n+1, B) objective values; the shared-A LSQR adjoint then solves diffcp's full (n + m + 1) system (const_a.vjp_const_a)."""
+        q_eval: the forward call's (n+1, B) objective values; the shared-A LSQR adjoint then solves diffcp's full (n + m + 1) system (const_a.vjp_const_a).
+        wave: run ce_vjp_wave (k_bwd_wave, one instance per wave; per-instance A, bwd_wave_plan()[0] >= 0, q_eval given) instead of ce_vjp; an engine it does
+        not serve, another path or a call without q_eval raises."""
         B = A_bm.shape[0]
         dev = self.device
+        self.last_adjoint_kernel = None
         if B == 0:
             return (torch.empty((self.nnz_aug, 0), dtype=torch.float64, device=dev), torch.empty((self.n + 1, 0), dtype=torch.float64, device=dev),
                     torch.empty((0,), dtype=torch.int32, device=dev))
         if path is None:
             path = self.last_path
+        if wave and (P_bm is not None or path != "per_instance"):
+            raise RuntimeError(f"vjp(wave=True): the wave adjoint serves the per-instance path with a linear objective (path {path!r})")
         if path == "const_a" and (self._launch_info["bwd_mode"] in (1, 2) or os.environ.get("CE_CONST_A") == "1"):
             from cvxpylayers_amd.interfaces.const_a import vjp_const_a      # shared A: batched LSQR with GEMMs over the batch
             if q_eval is None:          # direct engine users: the objective of the most recent solve() of this very value buffer, else the reduced system
@@ -369,10 +382,12 @@ class ConeEngine:
                                       dq.data_ptr(), B, 1, dP.data_ptr(), adj.data_ptr(), self._stream())
             _lib.check(rc, "ce_vjp_qp")
             return (dA if batch_minor_out else dA.t()), dq, adj, dP
-        rc = _lib.lib().ce_vjp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(),
-                               s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
-                               dq.data_ptr(), B, 1, adj.data_ptr(), self._stream())
-        _lib.check(rc, "ce_vjp")
+        entry = "ce_vjp_wave" if wave else "ce_vjp"
+        rc = getattr(_lib.lib(), entry)(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(),
+                                        s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
+                                        dq.data_ptr(), B, 1, adj.data_ptr(), self._stream())
+        _lib.check(rc, entry)
+        self.last_adjoint_kernel = "k_bwd_wave" if wave else None
         return (dA if batch_minor_out else dA.t()), dq, adj
 
     def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False,
@@ -517,12 +532,15 @@ class ConeEngine:
         _lib.check(_lib.lib().ce_param_grad_records(self._h, B, K, out.data_ptr(), self._stream()), "ce_param_grad_records")
         return out
 
-    def vjp_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None):
+    def vjp_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None, wave: bool = False):
         """One cotangent: dx (B, n), dy (B, m).  Returns g (B, maps.rows), dq (n + 1, B), adj (B,) from ce_vjp_params -- the single-cotangent kernel in its factor
         mode and k_param_grad behind it (K = 1 of the many-mode is the slower kernel for one cotangent).  A value row shorter than m cannot carry the factors:
-        that template takes vjp_many_params with K = 1."""
+        that template takes vjp_many_params with K = 1.  wave: ce_vjp_params_wave (k_bwd_wave in the place of the single-cotangent kernel; vjp's conditions)."""
         dev = self.device
         B = int(A_bm.shape[0])
+        self.last_adjoint_kernel = None
+        if wave and self.nnz_aug < self.m:
+            raise RuntimeError("vjp_params(wave=True): a value row shorter than m cannot hold the factors")
         if self.nnz_aug < self.m:
             g, dq, adj = self.vjp_many_params(A_bm, x, y, s, dx[None], None if dy is None else dy[None], maps, lsqr=lsqr, q_eval=q_eval)
             return g[0], dq[0].t(), adj[0]
@@ -535,10 +553,12 @@ class ConeEngine:
         A_c = A_bm if (A_bm.stride(1) == 1 and (B == 1 or A_bm.stride(0) == self.nnz_aug)) else A_bm.contiguous()
         xc, yc, sc_, dxc, dyc = (t.to(torch.float64).contiguous() for t in (x, y, s, dx, dy))
         qd, q_args = self._q_args(q_eval)
-        rc = _lib.lib().ce_vjp_params(self._h, B, A_c.data_ptr(), 1, self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dxc.data_ptr(), dyc.data_ptr(),
-                                      maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(), g.data_ptr(), dq.data_ptr(), B, 1, adj.data_ptr(),
-                                      self._stream())
-        _lib.check(rc, "ce_vjp_params")
+        entry = "ce_vjp_params_wave" if wave else "ce_vjp_params"
+        rc = getattr(_lib.lib(), entry)(self._h, B, A_c.data_ptr(), 1, self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dxc.data_ptr(), dyc.data_ptr(),
+                                        maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(), g.data_ptr(), dq.data_ptr(), B, 1, adj.data_ptr(),
+                                        self._stream())
+        _lib.check(rc, entry)
+        self.last_adjoint_kernel = "k_bwd_wave" if wave else None
         return g, dq, adj
 
     def _q_args(self, q_eval):

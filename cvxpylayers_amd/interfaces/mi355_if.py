@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_mode, dims_to_solver_dict, forward_kernel, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_kernel, adjoint_mode, dims_to_solver_dict, forward_kernel, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -158,6 +158,7 @@ class _Saved(NamedTuple):
     psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
     psd_adjoint: bool = False               # psd_many_active(psd_adjoint()) of this call: adjoint_many of a node with PSD blocks runs ce_vjp_psd_many (backward() ignores it)
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
+    adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave (every other route ignores it)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -174,6 +175,7 @@ class _ConeLayer(torch.autograd.Function):
         in_device = A_eval.device
         dev = in_device if in_device.type == "cuda" else ctx.default_device
         fwd_kernel = forward_kernel({**ctx.options, **(solver_args or {})})          # (validated before the device is touched)
+        adj_kernel = adjoint_kernel({**ctx.options, **(solver_args or {})})          # (likewise)
         if not torch.cuda.is_available():
             raise RuntimeError("MI355 solver needs a ROCm GPU; there is no CPU fallback (use solver='DIFFCP' on CPU)")
         eng = ctx.engine(dev)
@@ -262,6 +264,17 @@ class _ConeLayer(torch.autograd.Function):
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
             if fwd_kernel == "wave":
                 info["forward"] = {"kernel": "k_fwd_wave" if wave else "workgroup"}
+            # solver_args adjoint_kernel="wave": backward() / adjoint_params run k_bwd_wave where it serves the node -- the default adjoint mode, the per-instance
+            # path with q_eval saved, the search-free elimination enabled, a served template; said once elsewhere
+            adj_wave = False
+            if adj_kernel == "wave":
+                adj_wave = ("mode" not in merged_args and lpgd is None and P_bm is None and path == "per_instance" and os.environ.get("CE_BWD_NS") != "0"
+                            and eng.bwd_wave_plan()[0] >= 0 and eng.nnz_aug >= eng.m)          # (a value row shorter than m cannot hold the factors of vjp_params)
+                if not adj_wave:
+                    _warn_once("adjoint_kernel_none", "MI355 solver: solver_args adjoint_kernel='wave' is ignored on this template or path: the wave adjoint serves a linear "
+                                                      "objective, zero / nonnegative / second-order cones, n <= 32, m <= 64, nnz_aug >= m, a per-instance A and the default "
+                                                      "adjoint mode (no mode=, CE_BWD_NS not 0); the ordinary kernel runs (info['adjoint']['kernel'] == 'workgroup')")
+                info["adjoint"]["kernel"] = "k_bwd_wave" if adj_wave else "workgroup"
             if refine_info is not None:
                 info["refine"] = refine_info
             if nf_info is not None:
@@ -271,7 +284,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, adj_wave) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -382,7 +395,8 @@ class _ConeLayer(torch.autograd.Function):
                 dA, dq, adj, dP_bm = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, P_bm=saved.P_bm, path=saved.path, lsqr=saved.lsqr)
                 dP = dP_bm.t().to(in_device)
             else:
-                dA, dq, adj = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval)
+                dA, dq, adj = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval,
+                                      **({"wave": True} if saved.adj_wave else {}))
         # (masked instances: zero cotangents at a zero point give exactly zero dA / dq / dP rows from every adjoint kernel -- r = 0 --, no pass over the gradients needed)
         ctx.adj_status = adj
         if isinstance(ctx.info, dict) and isinstance(ctx.info.get("adjoint"), dict):
@@ -530,7 +544,7 @@ def adjoint_params(backward_data, dprimal, ddual, info, maps):
         dx = dprimal.to(**f64).contiguous() if dprimal is not None else eng.zeros_like_cached(saved.x)
         dy = ddual.to(**f64).contiguous() if ddual is not None else eng.zeros_like_cached(saved.y)
         x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
-        g, _dq, adj = eng.vjp_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval)
+        g, _dq, adj = eng.vjp_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, **({"wave": True} if saved.adj_wave else {}))
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
         eng.mailbox.note_adjoint_flags(adj, batch_size)

@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad", "forward_kernel"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad", "forward_kernel", "adjoint_kernel"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -246,6 +246,20 @@ def forward_kernel(merged_args: dict) -> str:
     mode = merged_args.get("forward_kernel", "workgroup")
     if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
         raise ValueError(f"MI355 solver: forward_kernel must be 'workgroup' or 'wave', got {mode!r}")
+    return mode
+
+
+def adjoint_kernel(merged_args: dict) -> str:
+    """Which kernel eliminates the single-cotangent adjoint system of a PER-INSTANCE-A template under the default adjoint mode:
+    absent / "workgroup" -> the ordinary kernels: one instance per workgroup of 256 threads (k_backward_ns with the LSQR re-solve behind it, or the pivoting kernels);
+    "wave" -> k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): one instance per wave, for small templates -- forward_kernel="wave"'s class
+    (ConeEngine.bwd_wave_plan()[0] >= 0).  The same system, rules, flags and LSQR re-solve of flagged instances; gradients agree to rounding, not bit for bit.
+    info["adjoint"]["kernel"] tells which runs ("k_bwd_wave" / "workgroup").  Independent of forward_kernel; composes with param_grad="factors".
+    Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger template, a shared A, any mode= key (LPGD included),
+    CE_BWD_NS=0 -- ignores the key with one notice and runs what it ran; layer.jacobian, forward-mode AD and the many-cotangent routes do not read it."""
+    mode = merged_args.get("adjoint_kernel", "workgroup")
+    if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
+        raise ValueError(f"MI355 solver: adjoint_kernel must be 'workgroup' or 'wave', got {mode!r}")
     return mode
 
 

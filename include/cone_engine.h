@@ -591,6 +591,33 @@ int ce_vjp_params(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b
                   int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
                   double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream);
 int ce_param_grad_variant(ce_handle h);
+/*
+ * The single-cotangent adjoint, ONE INSTANCE PER WAVE, for small templates (k_bwd_wave, csrc/ce_backward_wave.h; additions under ABI 17).  ce_vjp gives every
+ * instance a workgroup of 256 threads, 52.9 KB of LDS and barrier-separated phases sized for n = 50, m = 100; here a 64-thread workgroup eliminates an instance,
+ * with no workgroup barrier, the equality rows and the reduced Hessian in registers and A and R | B_1^-1 in its own LDS.  Same system, rules, flags and status
+ * bits as ce_vjp's search-free elimination; the results agree to rounding, not bit for bit.
+ *   served             : ce_solve_wave's class -- a linear objective, zero / nonnegative / second-order cones of any dimensions, n <= 32, m <= 64, any pattern.
+ *   ce_vjp_wave        : ce_vjp's arguments, layouts (batch-major or batch-minor A_vals / dA_vals, A_vals == NULL: the retained rows) and outputs.
+ *   ce_vjp_params_wave : ce_vjp_params' arguments and outputs.
+ *                        Both run the body of ce_vjp / ce_vjp_params with the wave kernel in the place of k_backward_ns: the instances the kernel flags (status bit
+ *                        4) are re-solved by the LSQR launch behind it exactly as there.  CE_E_UNSUPPORTED, before anything is enqueued and with nothing written,
+ *                        on a handle that is not served and on a call whose re-solve is not armed (q_vals == NULL, ce_set_adjoint_resolve(h, 0), or the LSQR
+ *                        vectors do not fit LDS): the kernel's dropped-variable answer on a flagged instance is never final.  ce_last_error names the entry and
+ *                        the reason.
+ *   ce_bwd_wave_variant : the row of the kernel's instantiation list (csrc/ce_variants_bwd_wave.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_bwd_wave_lds     : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_bwd_wave_occupancy: resident workgroups (= instances) per CU of that row at that footprint, as the runtime's occupancy query reports it (0 when not served).
+ */
+int ce_vjp_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream);
+int ce_vjp_params_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                       const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                       int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                       double *g, double *dq_vals, long sdq_k, long sdq_b, int *adj_status, void *stream);
+int ce_bwd_wave_variant(ce_handle h);
+int ce_bwd_wave_lds(ce_handle h);
+int ce_bwd_wave_occupancy(ce_handle h);
 /* Introspection (tests): the factor records the last ce_vjp_many_params call left in the engine's workspace, copied to out [K][B][m + 1 + n] on the stream: per pair
  * r_y[0 .. m), r_tau, r_x[0 .. n).  r_tau is 0 on the elimination path and LSQR's on a re-solved pair; g and dq do not determine it.  CE_E_STATE when no call of at
  * least this size has run. */
