@@ -20,7 +20,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_value", "ce_value_jvp", "ce_value_vjp", "ce_lpgd_perturb", "ce_lpgd_grad", "ce_set_transient_solve", "ce_check_solved",
            "ce_cones_create", "ce_cones_destroy", "ce_cones_rows", "ce_cones_state_len", "ce_cone_project", "ce_cone_dproject",
            "ce_solve_wave", "ce_wave_variant", "ce_wave_lds", "ce_wave_occupancy",
-           "ce_vjp_wave", "ce_vjp_params_wave", "ce_bwd_wave_variant", "ce_bwd_wave_lds", "ce_bwd_wave_occupancy"]
+           "ce_vjp_wave", "ce_vjp_params_wave", "ce_bwd_wave_variant", "ce_bwd_wave_lds", "ce_bwd_wave_occupancy",
+           "ce_vjp_many_wave", "ce_vjp_many_params_wave", "ce_bwd_wave_many_variant", "ce_bwd_wave_many_lds", "ce_bwd_wave_many_chunk", "ce_bwd_wave_many_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -104,6 +105,9 @@ def lib():
     L.ce_vjp_wave.argtypes = L.ce_vjp.argtypes
     L.ce_vjp_params_wave.argtypes = L.ce_vjp_params.argtypes
     L.ce_bwd_wave_variant.argtypes = [vp]; L.ce_bwd_wave_lds.argtypes = [vp]; L.ce_bwd_wave_occupancy.argtypes = [vp]
+    L.ce_vjp_many_wave.argtypes = L.ce_vjp_many.argtypes
+    L.ce_vjp_many_params_wave.argtypes = L.ce_vjp_many_params.argtypes
+    L.ce_bwd_wave_many_variant.argtypes = [vp]; L.ce_bwd_wave_many_lds.argtypes = [vp]; L.ce_bwd_wave_many_chunk.argtypes = [vp]; L.ce_bwd_wave_many_occupancy.argtypes = [vp]
     L.ce_vjp_tri_many_params.argtypes = L.ce_vjp_psd_many_params.argtypes = L.ce_vjp_psd_tri_many_params.argtypes = L.ce_vjp_many_params.argtypes
     L.ce_vjp_qp_many_params.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, dp, dp, dp, dp, dp, C.c_int, ip, ip, ip, dp, dp, dp, ip, vp]
     L.ce_param_grad_variant.argtypes = [vp]

@@ -58,6 +58,13 @@ struct NsMany {
     long sxk, syk, sAk, sqk, sak;
     double *rec = nullptr; long rpitch = 0, srk = 0;
 };
+// k_bwd_wave_many (ce_backward_wave_many.h; cone_engine.hip ce_vjp_many_wave, ce_vjp_many_params_wave): K cotangents of a small template, one wave per (instance,
+// chunk).  The strides and the record fields of NsMany, under a name of its own: the kernel is not a mode of k_backward_ns and is not launched by ce_launch_ns
+struct BwdWaveMany {
+    int K;
+    long sxk, syk, sAk, sqk, sak;
+    double *rec; long rpitch, srk;
+};
 // k_backward_ns<..., FWD = true, ..., MANY = true> (plain cones, P or not): K tangents on one factorisation of the instance (cone_engine.hip ce_jvp_many /
 // ce_jvp_qp_many).  Tangent k of instance i: its value row at tA + k * stAk + i * stAb, its q_eval row (n + 1 contiguous entries) at tq + k * stqk + i * stqb; a batch
 // stride of 0 is one row shared by every instance.  Outputs of tangent k lie sxk (dx) / syk (dy, ds) / sak (status -- CeBwdArgs' adj -- and iters) elements further
@@ -281,6 +288,10 @@ hipError_t ce_occupancy_fwd_wave(int variant, size_t lds, int *blocks);
 // ce_tu_bwd_wave.hip: k_bwd_wave, the adjoint of one instance per wave (row of CE_BWD_WAVE_VARIANTS, ce_variants_bwd_wave.h; reads CeBwdArgs' dA_factors itself)
 int ce_launch_bwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 hipError_t ce_occupancy_bwd_wave(int variant, size_t lds, int *blocks);
+// ce_tu_bwd_wave_many.hip: k_bwd_wave_many, K cotangents of one instance per wave and chunk (row of CE_BWD_WAVE_MANY_VARIANTS, ce_variants_bwd_wave_many.h): the grid
+// is B x ceil(w.K / KC) workgroups of 64 threads
+int ce_launch_bwd_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const BwdWaveMany &w);
+hipError_t ce_occupancy_bwd_wave_many(int variant, size_t lds, int *blocks);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
 // search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement

@@ -37,6 +37,7 @@
 #include "ce_plan.h"           // the launch plan (host only): CePlan, plan_engine, the shared-A selectors, the footprints of every kernel family
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
+#include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
 
 namespace {
 // the kernels this file launches itself; every other family is instantiated in its own translation unit (ce_tu_*.hip) and reached through the launchers of ce_types.h
@@ -102,6 +103,7 @@ struct ce_engine {
     const double *retained_A = nullptr; int retained_B = 0;
     int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
@@ -311,6 +313,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     h->wave_lds = h->wave_variant >= 0 ? fwd_wave_lds_bytes(h->wave_variant, tpl->n, tpl->m) : 0;
     h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
+    h->bwd_wave_many_variant = bwd_wave_many_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+    h->bwd_wave_many_lds = h->bwd_wave_many_variant >= 0 ? bwd_wave_many_lds_bytes(h->bwd_wave_many_variant, tpl->n, tpl->m) : 0;
     h->T.f2_neumann = h->plan.f2_neumann; h->T.gen_blocked_f = h->plan.gen_blocked_f; h->T.gen_blocked_b = h->plan.gen_blocked_b;
     GatherMaps G;
     if (h->plan.fwd_mode == FWD_V2) build_gather_maps(tpl, *h, G);
@@ -738,7 +742,9 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
 enum NsManyKind { NS_MANY_PLAIN = 0, NS_MANY_TRI = 1, NS_MANY_PSD = 2, NS_MANY_PSD_TRI = 3 };          // (NS_MANY_PSD_TRI: ce_vjp_psd_tri_many / ce_jvp_psd_tri_many -- on the row with both kinds' segments)
 static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                         const double *x, const double *y, const double *s, const double *dx, const double *dy,
-                        double *dA_vals, double *dq_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0) {
+                        double *dA_vals, double *dq_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0, bool wave = false) {
+    // wave (ce_vjp_many_wave, ce_vjp_many_params_wave; the plain kind, a served handle and an armed re-solve: the entries refuse otherwise): k_bwd_wave_many in the
+    // place of k_backward_ns<MANY>, the same strides, list and LSQR walk
     // rec (ce_vjp_many_params, the plain kind with an armed re-solve): both kernels store the pairs' factor records [K][B][rpitch] instead of dA rows; dA_vals is unused
     const CePlan &P = h->plan;
     const DevT &T = h->T;
@@ -770,7 +776,8 @@ static int vjp_many_run(ce_handle h, NsManyKind kind, const char *who, int B, in
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
     ba.adj = adj_status; ba.fix = fix.cur;
     h->last_fast = -1;
-    if (kind == NS_MANY_PSD_TRI ? ce_launch_ns(P.psd_tri_ns_variant, B, P.psd_tri_ns_lds, st, ba, NsVjpManyPsdTri{W})
+    if (wave ? ce_launch_bwd_wave_many(h->bwd_wave_many_variant, B, h->bwd_wave_many_lds, st, ba, BwdWaveMany{W.K, W.sxk, W.syk, W.sAk, W.sqk, W.sak, W.rec, W.rpitch, W.srk})
+        : kind == NS_MANY_PSD_TRI ? ce_launch_ns(P.psd_tri_ns_variant, B, P.psd_tri_ns_lds, st, ba, NsVjpManyPsdTri{W})
         : kind == NS_MANY_PSD ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsVjpManyPsd{W})
         : kind == NS_MANY_TRI ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsVjpTriMany{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W)) {
         g_err = "internal: no many-cotangent kernel for the planned variant"; return CE_E_BADARG;
@@ -834,7 +841,7 @@ static int pg_records_launch(ce_handle h, const std::string &who, int B, int K, 
 static int vjp_many_params_run(ce_handle h, NsManyKind kind, const char *who, int served, const char *refusal, int B, int K, const double *A_vals_bm, long sA_b,
                                const double *q_vals, long sq_k, long sq_b, const double *x, const double *y, const double *s, const double *dx, const double *dy,
                                int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
-                               double *g, double *dq_vals, int *adj_status, void *stream) {
+                               double *g, double *dq_vals, int *adj_status, void *stream, bool wave = false) {
     if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) { g_err = std::string(who) + ": null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
     int rc = pg_check(h, who, rows, map_ptr, map_code, map_k, map_val, q_vals, served, refusal);
     if (rc) return rc;
@@ -842,7 +849,7 @@ static int vjp_many_params_run(ce_handle h, NsManyKind kind, const char *who, in
     const long rpitch = (long)T.m + 1 + T.n;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(h->d_rec.reserve((size_t)K * B * rpitch));
-    rc = vjp_many_run(h, kind, who, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, nullptr, dq_vals, adj_status, stream, h->d_rec.get(), rpitch);
+    rc = vjp_many_run(h, kind, who, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, nullptr, dq_vals, adj_status, stream, h->d_rec.get(), rpitch, wave);
     if (rc) return rc;
     return pg_records_launch(h, who, B, K, x, y, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
 }
@@ -852,6 +859,53 @@ int ce_vjp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, long 
                        double *g, double *dq_vals, int *adj_status, void *stream) {
     return vjp_many_params_run(h, NS_MANY_PLAIN, "ce_vjp_many_params", -2, nullptr, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val,
                                g, dq_vals, adj_status, stream);
+}
+// k_bwd_wave_many: K cotangents of a small template, one wave per (instance, chunk of cotangents) (include/cone_engine.h).  ce_vjp_many's / ce_vjp_many_params'
+// arguments and the whole of their bodies (vjp_many_run: the strides, the re-solve list, ONE LSQR launch for all K cotangents of the listed instances; the records and
+// k_param_grad) with the wave kernel in the place of k_backward_ns<MANY>; refused where the handle is not served or the re-solve is not armed.
+int ce_bwd_wave_many_variant(ce_handle h) { return h ? h->bwd_wave_many_variant : -1; }
+int ce_bwd_wave_many_lds(ce_handle h) { return (h && h->bwd_wave_many_variant >= 0) ? (int)h->bwd_wave_many_lds : 0; }
+int ce_bwd_wave_many_chunk(ce_handle h) { return (h && h->bwd_wave_many_variant >= 0) ? bwd_wave_many_chunk(h->bwd_wave_many_variant) : 0; }
+int ce_bwd_wave_many_occupancy(ce_handle h) {
+    if (!h || h->bwd_wave_many_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_bwd_wave_many(h->bwd_wave_many_variant, h->bwd_wave_many_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+// (refused before anything is enqueued, nothing written; `alt`: the entry that serves the call instead)
+static int wave_many_check(ce_handle h, const char *who, int K, const double *q_vals, const char *alt) {
+    if (h->bwd_wave_many_variant < 0) {
+        g_err = std::string(who) + ": " + bwd_wave_many_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use " + alt;
+        return CE_E_UNSUPPORTED;
+    }
+    if (!(h->resolve && q_vals && resolve_fits(h))) {
+        g_err = std::string(who) + ": the LSQR re-solve of flagged instances is not armed for this call (q_vals == NULL, ce_set_adjoint_resolve(h, 0), or its "
+                "vectors do not fit LDS), and the wave kernel's dropped-variable answer is never final; use " + alt;
+        return CE_E_UNSUPPORTED;
+    }
+    if ((K + bwd_wave_many_chunk(h->bwd_wave_many_variant) - 1) / bwd_wave_many_chunk(h->bwd_wave_many_variant) > 65535) {
+        g_err = std::string(who) + ": K exceeds 65535 chunks of cotangents; use " + alt;
+        return CE_E_UNSUPPORTED;
+    }
+    return CE_OK;
+}
+int ce_vjp_many_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                     const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                     double *dA_vals, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dA_vals || !dq_vals) { g_err = "ce_vjp_many_wave: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    const int rc = wave_many_check(h, "ce_vjp_many_wave", K, q_vals, "ce_vjp_many");
+    if (rc) return rc;
+    return vjp_many_run(h, NS_MANY_PLAIN, "ce_vjp_many_wave", B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, x, y, s, dx, dy, dA_vals, dq_vals, adj_status, stream, nullptr, 0, true);
+}
+int ce_vjp_many_params_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                            const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                            int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                            double *g, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || K <= 0) { g_err = "ce_vjp_many_params_wave: null argument, B <= 0 or K <= 0"; return CE_E_BADARG; }
+    const int rc = wave_many_check(h, "ce_vjp_many_params_wave", K, q_vals, "ce_vjp_many_params");
+    if (rc) return rc;
+    return vjp_many_params_run(h, NS_MANY_PLAIN, "ce_vjp_many_params_wave", h->bwd_wave_many_variant, ": internal, the served row went away", B, K, A_vals_bm, sA_b,
+                               q_vals, sq_k, sq_b, x, y, s, dx, dy, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream, true);
 }
 // The same for the other many-cotangent kinds (include/cone_engine.h): each is served exactly where its kind's ce_vjp_*_many_variant >= 0 and refuses every other
 // handle -- a plain one included -- before anything is enqueued.  The records are the plain kind's: r_y stands in the original basis behind the triples' / blocks' rotation.

@@ -41,7 +41,7 @@ class ConeEngine:
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
-        self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), None otherwise
+        self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), "k_bwd_wave_many" when the last vjp_many() / vjp_many_params() ran its many-cotangent twin, None otherwise
         self.last_forward_kernel = None       # "k_fwd_wave" when the last solve() ran the one-instance-per-wave kernel (solve(wave=True)), None otherwise
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
@@ -138,6 +138,12 @@ class ConeEngine:
         served -- wave_plan's class) and the launch's LDS bytes (0 when not served)."""
         L = _lib.lib()
         return int(L.ce_bwd_wave_variant(self._h)), int(L.ce_bwd_wave_lds(self._h))
+
+    def bwd_wave_many_plan(self):
+        """(variant, lds, chunk) of the many-cotangent wave adjoint k_bwd_wave_many on this template: the row of csrc/ce_variants_bwd_wave_many.h that serves it
+        (-1: not served -- bwd_wave_plan()'s class), the launch's dynamic LDS in bytes and the cotangents one wave serves (0, 0 when not served)"""
+        L = _lib.lib()
+        return int(L.ce_bwd_wave_many_variant(self._h)), int(L.ce_bwd_wave_many_lds(self._h)), int(L.ce_bwd_wave_many_chunk(self._h))
 
     def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None, wave: bool = False):
         """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
@@ -391,7 +397,7 @@ class ConeEngine:
         return (dA if batch_minor_out else dA.t()), dq, adj
 
     def vjp_many(self, A_bm, x, y, s, dx, dy, path: str | None = None, lsqr: tuple | None = None, q_eval=None, P_bm=None, force_loop: bool = False,
-                 qp_many: bool = False, tri_many: bool = False, psd_many: bool = False):
+                 qp_many: bool = False, tri_many: bool = False, psd_many: bool = False, wave: bool = False):
         """K cotangents at one solution: dx (K, B, n), dy (K, B, m) or None (zero).  Returns dA (K, B, nnz_aug), dq (K, B, n+1), adj (K, B) -- and dP (K, B, nnz_p) when
         P_bm is given -- all batch-major.  For every k the result is what vjp returns for (dx[k], dy[k]).
         One ce_vjp_many call (each instance factored once, last_vjp_many_path == "many") under the rule that sends vjp to the search-free elimination: path
@@ -408,13 +414,20 @@ class ConeEngine:
         psd_many (opt-in, default False): on a template with PSD blocks (ce_vjp_psd_many_variant >= 0), under tri_many's conditions, one ce_vjp_psd_many call instead
         of the K ce_vjp calls of the pivoting kernel (last_vjp_kernel == "ce_vjp_psd_many"): each block is decomposed and its rows rotated once per instance.  The
         same caveat on flags (the stiff-row rule, carried over to PSD rows); in every other case the flag changes nothing.  On a template with PSD blocks AND
-        triples (ce_vjp_psd_tri_many_variant >= 0) the flag makes the one call ce_vjp_psd_tri_many (last_vjp_kernel names it)."""
+        triples (ce_vjp_psd_tri_many_variant >= 0) the flag makes the one call ce_vjp_psd_tri_many (last_vjp_kernel names it).
+        wave: the one call is ce_vjp_many_wave (k_bwd_wave_many: one wave per instance and chunk of bwd_wave_many_plan()[2] cotangents; last_vjp_kernel names the
+        entry, last_adjoint_kernel == "k_bwd_wave_many"); vjp(wave=True)'s conditions -- the per-instance path, a linear objective, q_eval given, a served engine --,
+        and a call outside them raises."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
         if path is None:
             path = self.last_path
-        many = (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
+        self.last_adjoint_kernel = None
+        if wave:
+            if P_bm is not None or path != "per_instance" or force_loop:
+                raise RuntimeError(f"vjp_many(wave=True): the wave adjoint serves the per-instance path with a linear objective in one call (path {path!r})")
+        many = wave or (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
         many_qp = (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
         many_tri = (not force_loop and tri_many and not many and path == "per_instance" and q_eval is not None and P_bm is None
                     and _lib.lib().ce_vjp_tri_many_variant(self._h) >= 0)
@@ -422,7 +435,7 @@ class ConeEngine:
                     and (_lib.lib().ce_vjp_psd_many_variant(self._h) >= 0 or _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0))
         mixed = many_psd and _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0          # (PSD blocks and triples: the mixed entry, the same arguments)
         self.last_vjp_many_path = "many" if (many or many_qp or many_tri or many_psd) else "loop"
-        self.last_vjp_kernel = ("ce_vjp_qp_many" if many_qp else ("ce_vjp_many" if many else ("ce_vjp_tri_many" if many_tri else
+        self.last_vjp_kernel = ("ce_vjp_qp_many" if many_qp else (("ce_vjp_many_wave" if wave else "ce_vjp_many") if many else ("ce_vjp_tri_many" if many_tri else
                                                                                              (("ce_vjp_psd_tri_many" if mixed else "ce_vjp_psd_many") if many_psd else None))))
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
@@ -456,10 +469,12 @@ class ConeEngine:
         dq = torch.empty((K, B, self.n + 1), **f64)
         adj = torch.empty((K, B), dtype=torch.int32, device=dev)
         fn, name = ((_lib.lib().ce_vjp_psd_tri_many, "ce_vjp_psd_tri_many") if mixed else (_lib.lib().ce_vjp_psd_many, "ce_vjp_psd_many") if many_psd else
-                    (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else (_lib.lib().ce_vjp_many, "ce_vjp_many"))
+                    (_lib.lib().ce_vjp_tri_many, "ce_vjp_tri_many") if many_tri else
+                    (_lib.lib().ce_vjp_many_wave, "ce_vjp_many_wave") if wave else (_lib.lib().ce_vjp_many, "ce_vjp_many"))
         rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
                 None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
         _lib.check(rc, name)
+        self.last_adjoint_kernel = "k_bwd_wave_many" if wave else None
         return dA, dq, adj
 
     @property
@@ -483,24 +498,27 @@ class ConeEngine:
         return maps.on(self.device)
 
     def vjp_many_params(self, A_bm, x, y, s, dx, dy, maps, lsqr: tuple | None = None, q_eval=None, out: torch.Tensor | None = None, P_bm=None,
-                        qp_many: bool = False, tri_many: bool = False, psd_many: bool = False):
+                        qp_many: bool = False, tri_many: bool = False, psd_many: bool = False, wave: bool = False):
         """The parameter gradients of K cotangents at one solution, with no dA in memory: dx (K, B, n), dy (K, B, m) or None (zero), maps a
         param_grad.ComposedMaps of this template.  Returns g (K, B, maps.rows) -- written into `out` when given (contiguous, that shape) --, dq (K, B, n + 1) and
         adj (K, B).  g[k, b] is what the transposed parameter maps make of vjp_many's dA[k, b] and dq[k, b] (and dP[k, b]): to the bit on a parameter with one map
         entry, within the terms' rounding elsewhere.  One C call (last_vjp_many_path == "many_params", last_vjp_kernel names the entry): ce_vjp_many_params, or under
         the keywords of vjp_many the entry of that kind -- qp_many with P_bm: ce_vjp_qp_many_params (maps may carry a P map; q_eval and lsqr are not read: no
         re-solve); tri_many: ce_vjp_tri_many_params; psd_many: ce_vjp_psd_many_params, on a template with triples beside the blocks ce_vjp_psd_tri_many_params.
+        wave: ce_vjp_many_params_wave (k_bwd_wave_many in the place of the many-cotangent kernel; last_adjoint_kernel == "k_bwd_wave_many"), alone of the keywords.
         The keyword SELECTS the entry: a template the entry does not serve raises _lib.EngineError with the library's reason and writes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
         if qp_many and P_bm is None:
             raise ValueError("ConeEngine.vjp_many_params: qp_many needs P_bm")
-        if sum(map(bool, (qp_many, tri_many, psd_many))) > 1 or (P_bm is not None and not qp_many):
-            raise ValueError("ConeEngine.vjp_many_params: at most one of qp_many / tri_many / psd_many, and P_bm with qp_many alone")
+        if sum(map(bool, (qp_many, tri_many, psd_many, wave))) > 1 or (P_bm is not None and not qp_many):
+            raise ValueError("ConeEngine.vjp_many_params: at most one of qp_many / tri_many / psd_many / wave, and P_bm with qp_many alone")
+        self.last_adjoint_kernel = None
         L = _lib.lib()
         name = ("ce_vjp_qp_many_params" if qp_many else "ce_vjp_tri_many_params" if tri_many else
-                ("ce_vjp_psd_tri_many_params" if L.ce_vjp_psd_tri_many_variant(self._h) >= 0 else "ce_vjp_psd_many_params") if psd_many else "ce_vjp_many_params")
+                ("ce_vjp_psd_tri_many_params" if L.ce_vjp_psd_tri_many_variant(self._h) >= 0 else "ce_vjp_psd_many_params") if psd_many else
+                "ce_vjp_many_params_wave" if wave else "ce_vjp_many_params")
         ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_many_params", need_q=not qp_many)
         g = out if out is not None else torch.empty((K, B, maps.rows), **f64)
         if tuple(g.shape) != (K, B, maps.rows) or not g.is_contiguous() or g.dtype != torch.float64:
@@ -524,6 +542,7 @@ class ConeEngine:
             rc = getattr(L, name)(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
                                   None if dy is None else dy.data_ptr(), *map_args)
         _lib.check(rc, name)
+        self.last_adjoint_kernel = "k_bwd_wave_many" if wave else None
         return g, dq, adj
 
     def param_grad_records(self, K: int, B: int) -> torch.Tensor:

@@ -158,7 +158,7 @@ class _Saved(NamedTuple):
     psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
     psd_adjoint: bool = False               # psd_many_active(psd_adjoint()) of this call: adjoint_many of a node with PSD blocks runs ce_vjp_psd_many (backward() ignores it)
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
-    adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave (every other route ignores it)
+    adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -440,12 +440,12 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
             dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
             x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
         out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm, qp_many=(saved.qp_adjoint == "search_free"),
-                           tri_many=(saved.tri_adjoint == "search_free"), psd_many=saved.psd_adjoint)
+                           tri_many=(saved.tri_adjoint == "search_free"), psd_many=saved.psd_adjoint, **({"wave": True} if saved.adj_wave else {}))
         dA, dq, adj = out[:3]
         dP = out[3] if saved.P_bm is not None else None
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
-            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many", "ce_vjp_psd_tri_many"):
+            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many", "ce_vjp_psd_tri_many", "ce_vjp_many_wave"):
                 info["adjoint"]["path"] = eng.last_vjp_kernel
         if K > 0 and batch_size > 0:
             any_k = adj[0].clone()
@@ -519,7 +519,7 @@ def adjoint_many_params(backward_data, dprimal, ddual, info, maps, out=None):
         dy = ddual.to(**f64).contiguous() if ddual is not None else None
         x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
         g, dq, adj = eng.vjp_many_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, out=out, P_bm=saved.P_bm if kind == "qp" else None,
-                                         qp_many=kind == "qp", tri_many=kind == "tri", psd_many=kind == "psd")
+                                         qp_many=kind == "qp", tri_many=kind == "tri", psd_many=kind == "psd", **({"wave": True} if (saved.adj_wave and kind == "plain") else {}))
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
             info["adjoint"]["path"] = eng.last_vjp_kernel
