@@ -292,6 +292,11 @@ hipError_t ce_occupancy_bwd_wave(int variant, size_t lds, int *blocks);
 // is B x ceil(w.K / KC) workgroups of 64 threads
 int ce_launch_bwd_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const BwdWaveMany &w);
 hipError_t ce_occupancy_bwd_wave_many(int variant, size_t lds, int *blocks);
+// ce_tu_newton_wave.hip: k_newton_wave, the forward derivative (NsJvp) and one Newton refinement step (NsRefine: a.T and a.Abm alone are read) of one instance per
+// wave (row of CE_NEWTON_WAVE_VARIANTS, ce_variants_newton_wave.h): the grid is B workgroups of 64 threads
+int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);
+int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);
+hipError_t ce_occupancy_newton_wave(int variant, int refine, size_t lds, int *blocks);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
 // search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement

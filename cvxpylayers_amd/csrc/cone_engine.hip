@@ -37,6 +37,7 @@
 #include "ce_plan.h"           // the launch plan (host only): CePlan, plan_engine, the shared-A selectors, the footprints of every kernel family
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
+#include "ce_lds_newton_wave.h"   // k_newton_wave (ce_jvp_wave, ce_refine_wave): the same for the one-wave forward derivative and refinement step
 #include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
 
 namespace {
@@ -104,6 +105,7 @@ struct ce_engine {
     int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
@@ -313,6 +315,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     h->wave_lds = h->wave_variant >= 0 ? fwd_wave_lds_bytes(h->wave_variant, tpl->n, tpl->m) : 0;
     h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
+    h->newton_wave_variant = newton_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+    h->newton_wave_lds = h->newton_wave_variant >= 0 ? newton_wave_lds_bytes(h->newton_wave_variant, tpl->n, tpl->m) : 0;
     h->bwd_wave_many_variant = bwd_wave_many_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_many_lds = h->bwd_wave_many_variant >= 0 ? bwd_wave_many_lds_bytes(h->bwd_wave_many_variant, tpl->n, tpl->m) : 0;
     h->T.f2_neumann = h->plan.f2_neumann; h->T.gen_blocked_f = h->plan.gen_blocked_f; h->T.gen_blocked_b = h->plan.gen_blocked_b;
@@ -1493,12 +1497,20 @@ static int qp_ns_check(ce_handle h, const char *who) {
 // re-solves the instances it listed as rank deficient -- the same re-solve list.  With P_vals (ce_jvp_qp: k_backward_ns<..., FWD, QP>) one launch and no re-solve list: no LSQR has a P term.
 static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
-                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false, bool psd_tri = false) {          // (psd_tri: ce_jvp_psd_tri -- PSD blocks and triples, the row with both kinds' segments)
+                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (psd_tri: ce_jvp_psd_tri -- PSD blocks and triples, the row with both kinds' segments; wave: ce_jvp_wave -- k_newton_wave in the place of k_backward_ns)
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_jvp_qp" : (psd_tri ? "ce_jvp_psd_tri" : (psd ? "ce_jvp_psd" : "ce_jvp"));
+    const std::string who = wave ? "ce_jvp_wave" : qp ? "ce_jvp_qp" : (psd_tri ? "ce_jvp_psd_tri" : (psd ? "ce_jvp_psd" : "ce_jvp"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     int rc = CE_OK;
+    if (wave) {          // (refused before anything is enqueued, nothing written)
+        if (h->newton_wave_variant < 0) { g_err = who + ": " + newton_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_jvp"; return CE_E_UNSUPPORTED; }
+        if (!(h->resolve && q_vals && resolve_fits(h))) {
+            g_err = who + ": the LSQR re-solve of flagged instances is not armed for this call (q_vals == NULL, ce_set_adjoint_resolve(h, 0), or its vectors do not fit "
+                    "LDS), and the wave kernel's dropped-variable answer is never final; use ce_jvp";
+            return CE_E_UNSUPPORTED;
+        }
+    } else
     if (qp) { rc = qp_ns_check(h, "ce_jvp_qp"); if (rc) return rc; }
     else if (psd_tri) {  // (the opt-in entry point of templates with PSD blocks and triples: ce_jvp and ce_jvp_psd keep refusing them)
         if (P.psd_tri_ns_variant < 0) { g_err = "ce_jvp_psd_tri: this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); use ce_jvp_lsqr"; return CE_E_UNSUPPORTED; }
@@ -1521,7 +1533,8 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     CeBwdArgs ba{};
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
-    const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
+    const int lrc = wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
+                  : qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
                   : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsdTri{W})
                   : psd ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsd{W})
                   : tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
@@ -1541,6 +1554,23 @@ int ce_jvp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double 
            double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream);
+}
+// k_newton_wave: the forward derivative and the refinement step of one instance per wave, for the small templates newton_wave_variant serves (ce_lds_newton_wave.h).
+// ce_jvp's / ce_refine's arguments and the whole of their body with the wave kernel in the place of k_backward_ns; refused where the handle is not served or (the
+// forward derivative) the re-solve is not armed.
+int ce_newton_wave_variant(ce_handle h) { return h ? h->newton_wave_variant : -1; }
+int ce_newton_wave_lds(ce_handle h) { return (h && h->newton_wave_variant >= 0) ? (int)h->newton_wave_lds : 0; }
+int ce_newton_wave_occupancy(ce_handle h, int refine) {
+    if (!h || h->newton_wave_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_newton_wave(h->newton_wave_variant, refine, h->newton_wave_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_jvp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "ce_jvp_wave: null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, nullptr, dx, dy, ds, jvp_status, lsqr_iters, atol, btol, conlim, iter_lim, stream, false, false, true);
 }
 int ce_jvp_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
                const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
@@ -1733,11 +1763,14 @@ int ce_vjp_qp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, lo
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
 static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
-                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false, bool psd_tri = false) {
+                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (wave: ce_refine_wave -- k_newton_wave<..., REF> in the place of k_backward_ns)
     const bool qp = P_vals != nullptr;
-    const std::string who = qp ? "ce_refine_qp" : (psd_tri ? "ce_refine_psd_tri" : (psd ? "ce_refine_psd" : "ce_refine"));
+    const std::string who = wave ? "ce_refine_wave" : qp ? "ce_refine_qp" : (psd_tri ? "ce_refine_psd_tri" : (psd ? "ce_refine_psd" : "ce_refine"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
+    if (wave) {          // (refused before anything is enqueued, nothing written)
+        if (h->newton_wave_variant < 0) { g_err = who + ": " + newton_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_refine"; return CE_E_UNSUPPORTED; }
+    } else
     if (qp) { const int rc = qp_ns_check(h, "ce_refine_qp"); if (rc) return rc; }
     else if (psd_tri) {  // (the opt-in entry point of templates with PSD blocks and triples: ce_refine and ce_refine_psd keep refusing them)
         if (P.psd_tri_ns_variant < 0) { g_err = "ce_refine_psd_tri: this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
@@ -1758,7 +1791,8 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
-        const int lrc = qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
+        const int lrc = wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
+                      : qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
                       : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsdTri{W})
                       : psd ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsd{W})
                       : tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefineTri{W}) : ce_launch_ns(variant, B, lds, st, ba, W);
@@ -1771,6 +1805,11 @@ int ce_refine(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
               const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine: null argument or negative step count"; return CE_E_BADARG; }
     return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream);
+}
+int ce_refine_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+                   const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals_bm || !q_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_wave: null argument or negative step count"; return CE_E_BADARG; }
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, status, steps, refine_status, steps_taken, resid, stream, false, false, true);
 }
 int ce_refine_psd(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
                   const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {

@@ -139,6 +139,12 @@ class ConeEngine:
         L = _lib.lib()
         return int(L.ce_bwd_wave_variant(self._h)), int(L.ce_bwd_wave_lds(self._h))
 
+    def newton_wave_plan(self):
+        """(variant, lds) of the one-instance-per-wave forward derivative / refinement kernel k_newton_wave on this template: the row of
+        csrc/ce_variants_newton_wave.h that serves it (-1: not served -- bwd_wave_plan()'s class) and the launch's LDS bytes (0 when not served)."""
+        L = _lib.lib()
+        return int(L.ce_newton_wave_variant(self._h)), int(L.ce_newton_wave_lds(self._h))
+
     def bwd_wave_many_plan(self):
         """(variant, lds, chunk) of the many-cotangent wave adjoint k_bwd_wave_many on this template: the row of csrc/ce_variants_bwd_wave_many.h that serves it
         (-1: not served -- bwd_wave_plan()'s class), the launch's dynamic LDS in bytes and the cotangents one wave serves (0, 0 when not served)"""
@@ -624,7 +630,7 @@ class ConeEngine:
         return out
 
     def jvp(self, A_bm, x, y, s, tA_bm, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "lsqr",
-            P_bm=None, tP_bm=None, psd_ns: bool = False):
+            P_bm=None, tP_bm=None, psd_ns: bool = False, wave: bool = False):
         """Forward-mode derivative of the solution map (diffcp's `derivative`): tangents tA_bm (B, nnz_aug) of the value rows and tq (n+1, B) of q_eval, either may be
         None (zero).  Returns dx (B, n), dy (B, m), ds (B, m), status (B,) -- 1: LSQR hit its iteration limit -- and sets last_lsqr_iters.
         One kernel per call, ce_jvp_lsqr, or ce_jvp_shared_a when `path` is "const_a" (only the b entries of tA_bm are read there: a shared A has no tangent).
@@ -636,7 +642,9 @@ class ConeEngine:
         with P inside and NO LSQR behind it (a flagged instance keeps the elimination's answer, status 4, 0 iterations); NotImplementedError under method="lsqr".
         psd_ns=True (with method="direct"): ce_jvp_psd in the place of ce_jvp -- the elimination with PSD blocks (psd_ns_plan()["psd_ns_variant"] >= 0), which
         ce_jvp refuses; the same fall to the LSQR call where the library has none for the template.  Without it a PSD template runs the LSQR call, as ever.
-        On a template with PSD blocks AND triples (psd_tri_ns_variant >= 0) the flag calls ce_jvp_psd_tri, the elimination with both kinds."""
+        On a template with PSD blocks AND triples (psd_tri_ns_variant >= 0) the flag calls ce_jvp_psd_tri, the elimination with both kinds.
+        wave=True (with method="direct", per-instance path): ce_jvp_wave in the place of ce_jvp -- k_newton_wave, one instance per wave (newton_wave_plan()[0] >= 0);
+        an engine or a call it does not serve raises, nothing falls back."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
@@ -665,6 +673,16 @@ class ConeEngine:
         def call(fn, A_t):
             return fn(self._h, B, A_t.data_ptr(), A_t.stride(0), *q_args, *point, *tangents, *(t.data_ptr() for t in outs),
                       float(atol), float(btol), float(conlim), int(lim), self._stream())
+        if wave:
+            if method != "direct" or shared or P_bm is not None or psd_ns:
+                raise NotImplementedError("ConeEngine.jvp: wave=True is the direct forward derivative on the per-instance path (ce_jvp_wave)")
+            rc = call(_lib.lib().ce_jvp_wave, A_c if A_c.stride(0) == self.nnz_aug else A_c.contiguous())
+            if rc in (-2, -3):
+                raise NotImplementedError(_lib.lib().ce_last_error().decode())
+            _lib.check(rc, "ce_jvp_wave")
+            self.last_jvp_kernel = "ce_jvp_wave"
+            self.last_lsqr_iters = its
+            return dx, dy, ds, st
         rc = -2
         if method == "direct" and not shared:
             direct, dname = (((_lib.lib().ce_jvp_psd_tri, "ce_jvp_psd_tri") if self.psd_tri_ns_variant >= 0 else (_lib.lib().ce_jvp_psd, "ce_jvp_psd")) if psd_ns
@@ -796,14 +814,16 @@ class ConeEngine:
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
-    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None, P_bm=None, psd_ns: bool = False):
+    def refine(self, A_bm, q_eval, x, y, s, steps: int, status=None, P_bm=None, psd_ns: bool = False, wave: bool = False):
         """`steps` safeguarded Newton steps on the KKT residual of (x, y, s) (include/cone_engine.h ce_refine): A_bm (B, nnz_aug), q_eval (n+1, B), x (B, n), y, s
         (B, m); status (B,) int32 or None: instances with a negative forward status are skipped.  Returns x, y, s, info -- contiguous fp64 tensors on this
         engine's device are refined IN PLACE and handed back, others are copied first.  info: "status" (bits 1 a step kept, 2 a step rejected, 4 flagged by the
         elimination, 16 skipped), "steps" (kept per instance), "resid_before" / "resid_after" (rho of the point that came in and of the one returned), "path"
         "ns" -- or "none", with the other entries None and the point untouched, where the library has no elimination for the template.  No host synchronisation.
         P_bm (B, nnz_p): the quadratic objective of a qp_native engine (ce_refine_qp: F_x = P x + A^T y^ + c).
-        psd_ns=True: ce_refine_psd in the place of ce_refine -- the elimination with PSD blocks, which ce_refine refuses (path "none" without the flag)."""
+        psd_ns=True: ce_refine_psd in the place of ce_refine -- the elimination with PSD blocks, which ce_refine refuses (path "none" without the flag).
+        wave=True: ce_refine_wave in the place of ce_refine -- k_newton_wave, one instance per wave (newton_wave_plan()[0] >= 0); info gains "kernel":
+        "k_newton_wave"; an engine it does not serve raises."""
         B = A_bm.shape[0]
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -817,6 +837,14 @@ class ConeEngine:
         rst = torch.empty((B,), dtype=torch.int32, device=dev); taken = torch.empty((B,), dtype=torch.int32, device=dev)
         resid = torch.empty((B, 2), **f64)
         tail = (x.data_ptr(), y.data_ptr(), s.data_ptr(), st_c.data_ptr() if st_c is not None else None, int(steps), rst.data_ptr(), taken.data_ptr(), resid.data_ptr(), self._stream())
+        if wave:
+            if P_bm is not None or psd_ns:
+                raise NotImplementedError("ConeEngine.refine: wave=True serves a linear objective and zero / nonnegative / second-order cones (ce_refine_wave)")
+            rc = _lib.lib().ce_refine_wave(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail)
+            if rc in (-2, -3):
+                raise NotImplementedError(_lib.lib().ce_last_error().decode())
+            _lib.check(rc, "ce_refine_wave")
+            return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns", "kernel": "k_newton_wave"}
         if P_bm is not None:
             P_c = P_bm.detach().to(**f64).contiguous()
             rc, name = _lib.lib().ce_refine_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp"

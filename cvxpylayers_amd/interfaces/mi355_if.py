@@ -28,7 +28,7 @@ from cvxpylayers_amd.interfaces.newton_first import newton_first_solve, not_serv
 from cvxpylayers_amd.interfaces.outcome_mailbox import OutcomeMailbox  # noqa: F401  (re-exported, like the names below)
 from cvxpylayers_amd.interfaces.quad_epigraph import QuadEpigraph
 from cvxpylayers_amd.interfaces.solver_args import (LSQR_ATOL, LSQR_BTOL, STATUS_NAMES, _KNOWN_ARGS, _WARNED, SolverError, _warn_once,  # noqa: F401
-                                                    adjoint_kernel, adjoint_mode, dims_to_solver_dict, forward_kernel, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
+                                                    adjoint_kernel, adjoint_mode, dims_to_solver_dict, forward_kernel, jvp_mode, lpgd_rule, lsqr_rule, make_settings, newton_first, newton_kernel, note_ignored_args, param_grad, psd_adjoint, psd_elimination, psd_elimination_active, psd_many_active, psd_tangents, qp_adjoint, refine_steps, tri_adjoint, tri_tangents, unpack_rule)
 
 
 class MI355_ctx:
@@ -158,6 +158,7 @@ class _Saved(NamedTuple):
     psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
     psd_adjoint: bool = False               # psd_many_active(psd_adjoint()) of this call: adjoint_many of a node with PSD blocks runs ce_vjp_psd_many (backward() ignores it)
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
+    nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave (every other route ignores it)
     adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
 
 
@@ -176,6 +177,7 @@ class _ConeLayer(torch.autograd.Function):
         dev = in_device if in_device.type == "cuda" else ctx.default_device
         fwd_kernel = forward_kernel({**ctx.options, **(solver_args or {})})          # (validated before the device is touched)
         adj_kernel = adjoint_kernel({**ctx.options, **(solver_args or {})})          # (likewise)
+        nw_kernel = newton_kernel({**ctx.options, **(solver_args or {})})            # (likewise)
         if not torch.cuda.is_available():
             raise RuntimeError("MI355 solver needs a ROCm GPU; there is no CPU fallback (use solver='DIFFCP' on CPU)")
         eng = ctx.engine(dev)
@@ -223,9 +225,18 @@ class _ConeLayer(torch.autograd.Function):
                     _warn_once("forward_kernel_none", "MI355 solver: solver_args forward_kernel='wave' is ignored on this template or path: the wave kernel serves a linear "
                                                       "objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a per-instance A, and not the remainder "
                                                       "solve of newton_first; the ordinary kernel ran (info['forward']['kernel'] == 'workgroup')")
+            # solver_args newton_kernel="wave": the Newton steps of refine_steps / newton_first and the direct forward derivative run k_newton_wave where it serves
+            # the node -- a per-instance A, a linear objective, the search-free elimination enabled, a served template; said once elsewhere
+            nw_wave = False
+            if nw_kernel == "wave":
+                nw_wave = (P_bm is None and os.environ.get("CE_BWD_NS") != "0" and eng.newton_wave_plan()[0] >= 0 and not eng._use_const_a(A_bm))
+                if not nw_wave:
+                    _warn_once("newton_kernel_none", "MI355 solver: solver_args newton_kernel='wave' is ignored on this template or path: the wave Newton kernel serves a "
+                                                     "linear objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a per-instance A (CE_BWD_NS not 0); "
+                                                     "the ordinary kernels run")
             nf_info = None
             if n_newton > 0 and warm is not None and batch_size > 0:
-                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns)
+                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if nw_wave else {}))
                 if nf_info["path"] == "none":
                     _warn_once("newton_first_none", "MI355 solver: solver_args newton_first needs the search-free elimination, which this template or path does not have "
                                                     "(PSD cones, n > 108, a shared A); the ordinary warm-started solve ran (info['newton_first']['path'] == 'none')")
@@ -240,7 +251,7 @@ class _ConeLayer(torch.autograd.Function):
             if n_refine > 0:
                 refine_info = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
                 if eng.last_path == "per_instance" and status.numel():
-                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm, psd_ns=psd_ns)
+                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if nw_wave else {}))
                 if refine_info["path"] == "none" and status.numel():
                     _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD "
                                               "cones, n > 108, a shared A); the solver's point is returned "
@@ -284,7 +295,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, adj_wave) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, nw_wave and path == "per_instance", adj_wave) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -361,12 +372,14 @@ class _ConeLayer(torch.autograd.Function):
                     tP_bm = (tP.unsqueeze(1) if originally_unbatched else tP).detach().to(device=eng.device, dtype=torch.float64).t().contiguous()
                 dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, method="direct", P_bm=saved.P_bm, tP_bm=tP_bm)
             else:
-                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode, psd_ns=saved.psd_ns)
+                nw = saved.nw_wave and saved.jvp_mode == "direct" and path == "per_instance" and saved.q_eval is not None and unpack_rule(saved.lsqr, eng.n, eng.m)[3] != "reduced"
+                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode, psd_ns=saved.psd_ns,
+                                        **({"wave": True} if nw else {}))
             if failed is not None:
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd", "ce_jvp_psd_tri") else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd", "ce_jvp_psd_tri", "ce_jvp_wave") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod

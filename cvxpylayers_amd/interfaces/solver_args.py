@@ -27,7 +27,7 @@ STATUS_NAMES = {1: "Solved", 2: "Solved/Inaccurate", -1: "Unbounded", -2: "Infea
 _KNOWN_ARGS = {"eps", "eps_abs", "eps_rel", "eps_infeas", "max_iters", "alpha", "rho_x", "scale", "normalize",
                "adaptive_scale", "acceleration_lookback", "acceleration_interval", "verbose", "mode", "solve_method",
                "n_jobs_forward", "n_jobs_backward", "warm_starts", "raise_on_error", "dispatch_history",
-               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad", "forward_kernel", "adjoint_kernel"}
+               "lsqr_atol", "lsqr_btol", "lsqr_iter_lim", "adjoint_system", "jvp_mode", "refine_steps", "lpgd_tau", "lpgd_rho", "newton_first", "qp_adjoint", "tri_adjoint", "tri_tangents", "psd_elimination", "psd_adjoint", "psd_tangents", "param_grad", "forward_kernel", "adjoint_kernel", "newton_kernel"}
 
 # Stopping rule of the LSQR adjoint (shared-A templates).  diffcp's adjoint (diffcp_if.py:86 -> adj_batch, mode="lsqr") runs LSQR with atol = btol = 1e-8 and an
 # iteration limit of 2 N on its N = n + m + 1 operator; the oracle restates exactly that (oracle/cone_oracle.c:85,712).  solver_args may override:
@@ -260,6 +260,21 @@ def adjoint_kernel(merged_args: dict) -> str:
     mode = merged_args.get("adjoint_kernel", "workgroup")
     if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
         raise ValueError(f"MI355 solver: adjoint_kernel must be 'workgroup' or 'wave', got {mode!r}")
+    return mode
+
+
+def newton_kernel(merged_args: dict) -> str:
+    """Which kernel solves the forward block of a PER-INSTANCE-A template -- the Newton steps of refine_steps and newton_first, and the forward derivative of
+    jvp_mode="direct":
+    absent / "workgroup" -> k_backward_ns<..., FWD> / <..., FWD, REF> (ce_jvp, ce_refine): one instance per workgroup of 256 threads;
+    "wave" -> k_newton_wave (ce_jvp_wave, ce_refine_wave): one instance per wave, for small templates -- adjoint_kernel="wave"'s class
+    (ConeEngine.newton_wave_plan()[0] >= 0).  The same system, rules, flags, safeguard and LSQR re-solve of flagged tangents; results agree to rounding, not bit for
+    bit.  info["refine"]["kernel"] and info["newton_first"]["refine"]["kernel"] are "k_newton_wave", info["jvp"]["kernel"] is "ce_jvp_wave" where it runs.
+    Independent of forward_kernel and adjoint_kernel.  Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger
+    template, a shared A, CE_BWD_NS=0 -- ignores the key with one notice and runs what it ran; jvp_mode="lsqr" and tangent_many do not read it."""
+    mode = merged_args.get("newton_kernel", "workgroup")
+    if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
+        raise ValueError(f"MI355 solver: newton_kernel must be 'workgroup' or 'wave', got {mode!r}")
     return mode
 
 

@@ -647,6 +647,31 @@ int ce_bwd_wave_many_variant(ce_handle h);
 int ce_bwd_wave_many_lds(ce_handle h);
 int ce_bwd_wave_many_chunk(ce_handle h);
 int ce_bwd_wave_many_occupancy(ce_handle h);
+/*
+ * The forward derivative and the Newton refinement step of a small template, ONE INSTANCE PER WAVE (k_newton_wave, csrc/ce_newton_wave.h; additions under ABI 17).
+ * ce_jvp and ce_refine run k_backward_ns<..., FWD> / <..., FWD, REF>: 256 threads and 52.9 KB of LDS per instance, three instances per CU.  Here a 64-thread
+ * workgroup solves the forward block with ce_vjp_wave's elimination (the same H and B) between a prologue and an epilogue of its own.  Same system, rules, flags,
+ * status bits and safeguard; the results agree with ce_jvp's / ce_refine's to rounding, not bit for bit, and an instance's result does not depend on its position.
+ *   served            : exactly ce_vjp_wave's class (ce_newton_wave_variant >= 0 where ce_bwd_wave_variant >= 0).
+ *   ce_jvp_wave       : ce_jvp's arguments and outputs.  It runs ce_jvp's body with the wave kernel in the place of k_backward_ns: the instances the kernel flags
+ *                       (status bit 4, or 2) are re-solved by the LSQR launch behind it exactly as there (status 4 | 8).  CE_E_UNSUPPORTED, before anything is
+ *                       enqueued and with nothing written, on a handle that is not served and on a call whose re-solve is not armed (q_vals == NULL,
+ *                       ce_set_adjoint_resolve(h, 0), or the LSQR vectors do not fit LDS); ce_last_error names the entry and the reason.
+ *   ce_refine_wave    : ce_refine's arguments, record and contract; `steps` launches, one complete safeguarded step each.  CE_E_UNSUPPORTED with nothing written
+ *                       on a handle that is not served.
+ *   ce_newton_wave_variant  : the row of the kernel's instantiation list (csrc/ce_variants_newton_wave.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_newton_wave_lds      : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_newton_wave_occupancy: resident workgroups (= instances) per CU of that row at that footprint (refine != 0: of the refinement step's instantiation), as
+ *                             the runtime's occupancy query reports it (0 when not served).
+ */
+int ce_jvp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream);
+int ce_refine_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, double *x, double *y, double *s,
+                   const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream);
+int ce_newton_wave_variant(ce_handle h);
+int ce_newton_wave_lds(ce_handle h);
+int ce_newton_wave_occupancy(ce_handle h, int refine);
 /* Introspection (tests): the factor records the last ce_vjp_many_params call left in the engine's workspace, copied to out [K][B][m + 1 + n] on the stream: per pair
  * r_y[0 .. m), r_tau, r_x[0 .. n).  r_tau is 0 on the elimination path and LSQR's on a re-solved pair; g and dq do not determine it.  CE_E_STATE when no call of at
  * least this size has run. */
