@@ -22,7 +22,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_solve_wave", "ce_wave_variant", "ce_wave_lds", "ce_wave_occupancy",
            "ce_vjp_wave", "ce_vjp_params_wave", "ce_bwd_wave_variant", "ce_bwd_wave_lds", "ce_bwd_wave_occupancy",
            "ce_vjp_many_wave", "ce_vjp_many_params_wave", "ce_bwd_wave_many_variant", "ce_bwd_wave_many_lds", "ce_bwd_wave_many_chunk", "ce_bwd_wave_many_occupancy",
-           "ce_jvp_wave", "ce_refine_wave", "ce_newton_wave_variant", "ce_newton_wave_lds", "ce_newton_wave_occupancy"]
+           "ce_jvp_wave", "ce_refine_wave", "ce_newton_wave_variant", "ce_newton_wave_lds", "ce_newton_wave_occupancy",
+           "ce_jvp_many_wave", "ce_jvp_wave_many_variant", "ce_jvp_wave_many_lds", "ce_jvp_wave_many_chunk", "ce_jvp_wave_many_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -117,6 +118,8 @@ def lib():
     L.ce_param_grad_variant.argtypes = [vp]
     L.ce_param_grad_records.argtypes = [vp, C.c_int, C.c_int, dp, vp]
     L.ce_jvp_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, lg, lg, dp, dp, dp, dp, lg, lg, dp, lg, lg, dp, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, C.c_int, vp]
+    L.ce_jvp_many_wave.argtypes = L.ce_jvp_many.argtypes
+    L.ce_jvp_wave_many_variant.argtypes = [vp]; L.ce_jvp_wave_many_lds.argtypes = [vp]; L.ce_jvp_wave_many_chunk.argtypes = [vp]; L.ce_jvp_wave_many_occupancy.argtypes = [vp]
     L.ce_jvp_qp_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, dp, dp, dp, dp, lg, lg, dp, lg, lg, dp, lg, lg, dp, dp, dp, ip, ip, vp]
     L.ce_jvp_many_variant.argtypes = [vp]
     L.ce_jvp_tri_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, lg, lg, dp, dp, dp, dp, lg, lg, dp, lg, lg, dp, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, C.c_int, vp]

@@ -297,6 +297,10 @@ hipError_t ce_occupancy_bwd_wave_many(int variant, size_t lds, int *blocks);
 int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);
 int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);
 hipError_t ce_occupancy_newton_wave(int variant, int refine, size_t lds, int *blocks);
+// ce_tu_jvp_wave_many.hip: k_jvp_wave_many, K tangents of one instance per wave and chunk (row of CE_JVP_WAVE_MANY_VARIANTS, ce_variants_jvp_wave_many.h): the grid
+// is B x ceil(w.K / KC) workgroups of 64 threads; NsJvpMany as k_backward_ns<FWD, MANY> takes it (its structure arrays are not read)
+int ce_launch_jvp_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpMany &w);
+hipError_t ce_occupancy_jvp_wave_many(int variant, size_t lds, int *blocks);
 int ce_launch_bwd_rt_plain(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 // k_backward_ns (ce_tu_ns.hip: the linear-objective modes in one object, the two with P in another), one launcher per mode, selected by the mode's argument struct:
 // search-free null-space adjoint (plain cones); the same elimination for the forward derivative (a.dx, a.dy, a.dA, a.dq unused) and for one Newton refinement

@@ -38,6 +38,7 @@
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
 #include "ce_lds_newton_wave.h"   // k_newton_wave (ce_jvp_wave, ce_refine_wave): the same for the one-wave forward derivative and refinement step
+#include "ce_lds_jvp_wave_many.h"   // k_jvp_wave_many (ce_jvp_many_wave): the same for the many-tangent twin of the forward derivative
 #include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
 
 namespace {
@@ -106,6 +107,7 @@ struct ce_engine {
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int jvp_wave_many_variant = -1; size_t jvp_wave_many_lds = 0;      // k_jvp_wave_many (ce_jvp_many_wave): row of CE_JVP_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
@@ -317,6 +319,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
     h->newton_wave_variant = newton_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->newton_wave_lds = h->newton_wave_variant >= 0 ? newton_wave_lds_bytes(h->newton_wave_variant, tpl->n, tpl->m) : 0;
+    h->jvp_wave_many_variant = jvp_wave_many_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+    h->jvp_wave_many_lds = h->jvp_wave_many_variant >= 0 ? jvp_wave_many_lds_bytes(h->jvp_wave_many_variant, tpl->n, tpl->m) : 0;
     h->bwd_wave_many_variant = bwd_wave_many_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_many_lds = h->bwd_wave_many_variant >= 0 ? bwd_wave_many_lds_bytes(h->bwd_wave_many_variant, tpl->n, tpl->m) : 0;
     h->T.f2_neumann = h->plan.f2_neumann; h->T.gen_blocked_f = h->plan.gen_blocked_f; h->T.gen_blocked_b = h->plan.gen_blocked_b;
@@ -1597,13 +1601,23 @@ int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
 static int jvp_many_ns(ce_handle h, NsManyKind kind, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                        const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
                        const double *tP_vals, long stP_k, long stP_b, double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters,
-                       double atol, double btol, double conlim, int iter_lim, void *stream) {
+                       double atol, double btol, double conlim, int iter_lim, void *stream, bool wave = false) {          // (wave: ce_jvp_many_wave -- k_jvp_wave_many in the place of k_backward_ns<FWD, MANY>, the plain kind)
     const bool qp = P_vals != nullptr, tri = kind == NS_MANY_TRI, psd = kind == NS_MANY_PSD, psd_tri = kind == NS_MANY_PSD_TRI;
-    const std::string who = qp ? "ce_jvp_qp_many" : (psd_tri ? "ce_jvp_psd_tri_many" : (psd ? "ce_jvp_psd_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many")));
+    const std::string who = wave ? "ce_jvp_many_wave" : qp ? "ce_jvp_qp_many" : (psd_tri ? "ce_jvp_psd_tri_many" : (psd ? "ce_jvp_psd_many" : (tri ? "ce_jvp_tri_many" : "ce_jvp_many")));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
+    if (wave) {          // (refused before anything is enqueued, nothing written)
+        if (h->jvp_wave_many_variant < 0) { g_err = who + ": " + newton_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_jvp_many"; return CE_E_UNSUPPORTED; }
+        if (!(h->resolve && q_vals && resolve_fits(h))) {
+            g_err = who + ": the LSQR re-solve of flagged instances is not armed for this call (q_vals == NULL, ce_set_adjoint_resolve(h, 0), or its vectors do not fit "
+                    "LDS), and the wave kernel's dropped-variable answer is never final; use ce_jvp_many";
+            return CE_E_UNSUPPORTED;
+        }
+        const int kc = jvp_wave_many_chunk(h->jvp_wave_many_variant);
+        if ((K + kc - 1) / kc > 65535) { g_err = who + ": K exceeds 65535 chunks of tangents; use ce_jvp_many"; return CE_E_UNSUPPORTED; }
+    } else
     if (qp) { const int rc = qp_ns_check(h, "ce_jvp_qp_many"); if (rc) return rc; }
-    if ((qp ? ce_jvp_qp_many_variant(h) : psd_tri ? ce_jvp_psd_tri_many_variant(h) : (psd ? ce_jvp_psd_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h)))) < 0) {
+    if (!wave && (qp ? ce_jvp_qp_many_variant(h) : psd_tri ? ce_jvp_psd_tri_many_variant(h) : (psd ? ce_jvp_psd_many_variant(h) : (tri ? ce_jvp_tri_many_variant(h) : ce_jvp_many_variant(h)))) < 0) {
         g_err = who + (qp ? ": this template has no many-tangent elimination with a quadratic objective; call ce_jvp_qp once per tangent"
                        : psd_tri ? ": this template has no search-free elimination with PSD blocks and triples (it lacks a PSD block or an exponential / power cone, has a quadratic objective, n > 108, its footprint exceeds LDS, or CE_BWD_NS=0); call ce_jvp_lsqr once per tangent"
                        : psd ? ": this template has no search-free elimination with PSD blocks (no PSD block, triples or a quadratic objective beside them, n > 108, its "
@@ -1630,7 +1644,8 @@ static int jvp_many_ns(ce_handle h, NsManyKind kind, int B, int K, const double 
     const long sxk = (long)((size_t)B * n), syk = (long)((size_t)B * m), sak = B;
     const NsJvpMany W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), K, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b,
                       dx, dy, ds, sxk, syk, sak, lsqr_iters};
-    const int lrc = qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
+    const int lrc = wave ? ce_launch_jvp_wave_many(h->jvp_wave_many_variant, B, h->jvp_wave_many_lds, st, ba, W)
+                       : qp ? ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, NsJvpQpMany{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}, stP_k, stP_b})
                        : psd_tri ? ce_launch_ns(P.psd_tri_ns_variant, B, P.psd_tri_ns_lds, st, ba, NsJvpManyPsdTri{W})
                        : psd ? ce_launch_ns(P.psd_ns_variant, B, P.psd_ns_lds, st, ba, NsJvpManyPsd{W})
                        : tri ? ce_launch_ns(P.tri_ns_variant, B, P.tri_ns_lds, st, ba, NsJvpManyTri{W}) : ce_launch_ns(P.ns_variant, B, P.ns_lds, st, ba, W);
@@ -1657,6 +1672,27 @@ int ce_jvp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, c
     if (h->plan.qp_native) { g_err = "ce_jvp_many: this template runs a quadratic objective inside the kernels; use ce_jvp_qp_many"; return CE_E_UNSUPPORTED; }
     return jvp_many_ns(h, NS_MANY_PLAIN, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
                        atol, btol, conlim, iter_lim, stream);
+}
+// k_jvp_wave_many: K tangents of a small template, one wave per (instance, chunk of tangents) (include/cone_engine.h).  ce_jvp_many's arguments and the whole of its
+// body (jvp_many_ns: the strides, the re-solve list, ONE LSQR launch for all K tangents of the listed instances) with the wave kernel in the place of
+// k_backward_ns<FWD, MANY>; refused where the handle is not served or the re-solve is not armed.
+int ce_jvp_wave_many_variant(ce_handle h) { return h ? h->jvp_wave_many_variant : -1; }
+int ce_jvp_wave_many_lds(ce_handle h) { return (h && h->jvp_wave_many_variant >= 0) ? (int)h->jvp_wave_many_lds : 0; }
+int ce_jvp_wave_many_chunk(ce_handle h) { return (h && h->jvp_wave_many_variant >= 0) ? jvp_wave_many_chunk(h->jvp_wave_many_variant) : 0; }
+int ce_jvp_wave_many_occupancy(ce_handle h) {
+    if (!h || h->jvp_wave_many_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_jvp_wave_many(h->jvp_wave_many_variant, h->jvp_wave_many_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_jvp_many_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                     const double *x, const double *y, const double *s, const double *tA_vals, long stA_k, long stA_b, const double *tq_vals, long stq_k, long stq_b,
+                     double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !x || !y || !s || !dx || !dy || !jvp_status || stA_b < 0 || stq_b < 0) {
+        g_err = "ce_jvp_many_wave: null argument, B <= 0, K <= 0 or a negative batch stride"; return CE_E_BADARG;
+    }
+    return jvp_many_ns(h, NS_MANY_PLAIN, B, K, A_vals_bm, sA_b, q_vals, sq_k, sq_b, nullptr, x, y, s, tA_vals, stA_k, stA_b, tq_vals, stq_k, stq_b, nullptr, 0, 0, dx, dy, ds, jvp_status, lsqr_iters,
+                       atol, btol, conlim, iter_lim, stream, true);
 }
 // K tangents at one solution of a template with exponential / power triples (include/cone_engine.h): ce_jvp_many's body with k_backward_ns<..., FWD, ..., TRI, MANY> on
 // the triples' variant and footprint; the re-solve behind it is the same one launch.  Refusals come before any device call.

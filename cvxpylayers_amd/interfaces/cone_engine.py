@@ -46,7 +46,7 @@ class ConeEngine:
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
-        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_psd" / "ce_jvp_lsqr" / "ce_jvp_shared_a"
+        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_psd" / "ce_jvp_lsqr" / "ce_jvp_shared_a" / "ce_jvp_wave"; after jvp_many's one call its entry ("ce_jvp_many", "ce_jvp_many_wave", ...)
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -150,6 +150,12 @@ class ConeEngine:
         (-1: not served -- bwd_wave_plan()'s class), the launch's dynamic LDS in bytes and the cotangents one wave serves (0, 0 when not served)"""
         L = _lib.lib()
         return int(L.ce_bwd_wave_many_variant(self._h)), int(L.ce_bwd_wave_many_lds(self._h)), int(L.ce_bwd_wave_many_chunk(self._h))
+
+    def jvp_wave_many_plan(self):
+        """(variant, lds, chunk) of the many-tangent wave forward derivative k_jvp_wave_many on this template: the row of csrc/ce_variants_jvp_wave_many.h that serves
+        it (-1: not served -- newton_wave_plan()'s class), the launch's dynamic LDS in bytes and the tangents one wave serves (0, 0 when not served)"""
+        L = _lib.lib()
+        return int(L.ce_jvp_wave_many_variant(self._h)), int(L.ce_jvp_wave_many_lds(self._h)), int(L.ce_jvp_wave_many_chunk(self._h))
 
     def solve(self, A_bm: torch.Tensor, q_eval: torch.Tensor, settings, warm=None, P_bm=None, path: str | None = None, wave: bool = False):
         """A_bm (B, nnz_aug) contiguous, q_eval (n+1, B) any strides.  Returns x, y, s, iters, status, resid.
@@ -700,7 +706,7 @@ class ConeEngine:
         return dx, dy, ds, st
 
     def jvp_many(self, A_bm, x, y, s, tA, tq, path: str | None = None, lsqr: tuple | None = None, q_eval=None, conlim: float = 1e8, method: str = "direct",
-                 P_bm=None, tP=None, force_loop: bool = False, tri_many: bool = False, psd_many: bool = False):
+                 P_bm=None, tP=None, force_loop: bool = False, tri_many: bool = False, psd_many: bool = False, wave: bool = False):
         """K tangents at one solution.  tA (K, B, nnz_aug), tq (K, B, n+1), tP (K, B, nnz_p) -- or (K, .) for a tangent every instance shares (batch stride 0: a
         parameter-space basis vector pushed through the parameter maps); at most two of the three may be None (zero).  Returns dx (K, B, n), dy (K, B, m),
         ds (K, B, m), status (K, B) and sets last_lsqr_iters (K, B): for every k what jvp(method=method) returns for the k-th tangent.
@@ -715,7 +721,10 @@ class ConeEngine:
         (last_jvp_kernel == "ce_jvp_psd_many") instead of the K calls of the loop, which are ce_jvp_lsqr calls on such a template: each block is decomposed, its rows
         rotated and each instance factored once for all K tangents.  With force_loop the flag selects the loop's kernel instead: K ce_jvp_psd calls, the elimination
         this mode repeats K times less -- its comparator.  In every other case the flag changes nothing.  On a template with PSD blocks AND triples
-        (ce_jvp_psd_tri_many_variant >= 0) the one call is ce_jvp_psd_tri_many and the loop under force_loop is K ce_jvp_psd_tri calls."""
+        (ce_jvp_psd_tri_many_variant >= 0) the one call is ce_jvp_psd_tri_many and the loop under force_loop is K ce_jvp_psd_tri calls.
+        wave (with method="direct", no P_bm, any path but "const_a"): the one call is ce_jvp_many_wave (k_jvp_wave_many: one wave per instance and chunk of
+        jvp_wave_many_plan()[2] tangents; last_jvp_kernel names the entry); an engine it does not serve (jvp_wave_many_plan()[0] < 0) or a call outside these
+        conditions raises NotImplementedError, nothing falls back.  With force_loop the flag goes through to the K jvp(wave=True) calls: the comparator."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp_many: method must be 'lsqr' or 'direct', got {method!r}")
         given = [t for t in (tA, tq, tP) if t is not None]
@@ -731,7 +740,9 @@ class ConeEngine:
         if path is None:
             path = self.last_path
         L = _lib.lib()
-        many = not force_loop and method == "direct" and (L.ce_jvp_qp_many_variant(self._h) >= 0 if P_bm is not None else (path != "const_a" and L.ce_jvp_many_variant(self._h) >= 0))
+        if wave and (method != "direct" or P_bm is not None or path == "const_a"):
+            raise NotImplementedError("ConeEngine.jvp_many: wave=True is the direct forward derivative with a linear objective off the shared-A path (ce_jvp_many_wave)")
+        many = not force_loop and method == "direct" and (L.ce_jvp_qp_many_variant(self._h) >= 0 if P_bm is not None else (path != "const_a" and (wave or L.ce_jvp_many_variant(self._h) >= 0)))
         many_tri = (not force_loop and tri_many and not many and method == "direct" and P_bm is None and path != "const_a"
                     and L.ce_jvp_tri_many_variant(self._h) >= 0)
         psd_ok = (psd_many and not many and not many_tri and method == "direct" and P_bm is None and path != "const_a"
@@ -752,7 +763,7 @@ class ConeEngine:
             for k in range(K):
                 tqk = of(tq, k)
                 outs.append(self.jvp(A_bm, x, y, s, of(tA, k), None if tqk is None else tqk.t(), path=path, lsqr=lsqr, q_eval=q_eval, conlim=conlim, method=method,
-                                     P_bm=P_bm, tP_bm=of(tP, k), psd_ns=psd_ok))
+                                     P_bm=P_bm, tP_bm=of(tP, k), psd_ns=psd_ok, **({"wave": True} if wave else {})))
                 its.append(self.last_lsqr_iters)
             self.last_lsqr_iters = torch.stack(its)
             return tuple(torch.stack([o[i] for o in outs]) for i in range(4))
@@ -776,9 +787,11 @@ class ConeEngine:
                 q_eval = None
             qd, q_args = self._q_args(q_eval)
             fn, name = ((L.ce_jvp_psd_tri_many, "ce_jvp_psd_tri_many") if mixed else (L.ce_jvp_psd_many, "ce_jvp_psd_many") if many_psd else
-                        (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many, "ce_jvp_many"))
+                        (L.ce_jvp_tri_many, "ce_jvp_tri_many") if many_tri else (L.ce_jvp_many_wave, "ce_jvp_many_wave") if wave else (L.ce_jvp_many, "ce_jvp_many"))
             rc = fn(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(),
                     *strides(tA, self.nnz_aug), *strides(tq, self.n + 1), *outp, float(atol), float(btol), float(conlim), int(lim), self._stream())
+            if wave and rc in (-2, -3):
+                raise NotImplementedError(L.ce_last_error().decode())
         _lib.check(rc, name)
         self.last_jvp_kernel = name
         self.last_lsqr_iters = its

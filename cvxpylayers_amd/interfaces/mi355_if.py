@@ -158,7 +158,7 @@ class _Saved(NamedTuple):
     psd_ns: bool = False                    # psd_elimination_active() of this call: jvp_mode="direct" runs ce_jvp_psd on this node
     psd_adjoint: bool = False               # psd_many_active(psd_adjoint()) of this call: adjoint_many of a node with PSD blocks runs ce_vjp_psd_many (backward() ignores it)
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
-    nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave (every other route ignores it)
+    nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave, tangent_many ce_jvp_many_wave (every other route ignores it)
     adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
 
 
@@ -594,11 +594,12 @@ def tangent_many(backward_data, tP, tq, tA, info=None, method=None, sym_perm=Non
         if qp:
             dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, method="direct", P_bm=saved.P_bm, tP=tP)
         else:
+            nw = saved.nw_wave and method == "direct" and path == "per_instance" and saved.q_eval is not None and unpack_rule(saved.lsqr, eng.n, eng.m)[3] != "reduced"
             dx, dy, _, st = eng.jvp_many(saved.A_bm, x, y, s, tA, tq, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=method, tri_many=(saved.tri_tangents == "many"),
-                                         psd_many=saved.psd_tangents)
+                                         psd_many=saved.psd_tangents, **({"wave": True} if nw else {}))
         if isinstance(info, dict):
             info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel,
-                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many", "ce_jvp_psd_many", "ce_jvp_psd_tri", "ce_jvp_psd_tri_many") else "lsqr"}
+                           "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_many", "ce_jvp_qp_many", "ce_jvp_tri_many", "ce_jvp_psd_many", "ce_jvp_psd_tri", "ce_jvp_psd_tri_many", "ce_jvp_many_wave") else "lsqr"}
     return dx, dy, failed
 
 
