@@ -285,6 +285,10 @@ int ce_launch_fwd_generic(int mode, int B, size_t lds, hipStream_t st, const CeF
 // ce_tu_fwd_wave.hip: k_fwd_wave, one instance per wave (row of CE_WAVE_VARIANTS, ce_variants_wave.h); the resident workgroups per CU of a row
 int ce_launch_fwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a);
 hipError_t ce_occupancy_fwd_wave(int variant, size_t lds, int *blocks);
+// ce_tu_fwd_wave_qp.hip: k_fwd_wave_qp, one QP instance per wave (row of CE_FWD_WAVE_QP_VARIANTS, ce_variants_fwd_wave_qp.h): a.P, a.nnz_p and the (row, column)
+// of every entry of the P structure (p_tri: one triangle is stored and an off-diagonal entry stands for both)
+int ce_launch_fwd_wave_qp(int variant, int B, size_t lds, hipStream_t st, const CeFwdArgs &a, const int *prow, const int *pcol, int p_tri);
+hipError_t ce_occupancy_fwd_wave_qp(int variant, size_t lds, int *blocks);
 // ce_tu_bwd_wave.hip: k_bwd_wave, the adjoint of one instance per wave (row of CE_BWD_WAVE_VARIANTS, ce_variants_bwd_wave.h; reads CeBwdArgs' dA_factors itself)
 int ce_launch_bwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 hipError_t ce_occupancy_bwd_wave(int variant, size_t lds, int *blocks);

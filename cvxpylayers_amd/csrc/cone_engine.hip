@@ -36,6 +36,7 @@
 #include "ce_types.h"
 #include "ce_plan.h"           // the launch plan (host only): CePlan, plan_engine, the shared-A selectors, the footprints of every kernel family
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
+#include "ce_lds_fwd_wave_qp.h"   // k_fwd_wave_qp (ce_solve_qp_wave): the same for the one-wave forward kernel of a quadratic objective
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
 #include "ce_lds_newton_wave.h"   // k_newton_wave (ce_jvp_wave, ce_refine_wave): the same for the one-wave forward derivative and refinement step
 #include "ce_lds_jvp_wave_many.h"   // k_jvp_wave_many (ce_jvp_many_wave): the same for the many-tangent twin of the forward derivative
@@ -104,6 +105,7 @@ struct ce_engine {
     DevBuf<double> gws;          // global residency fallback
     const double *retained_A = nullptr; int retained_B = 0;
     int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int wave_qp_variant = -1; size_t wave_qp_lds = 0;      // k_fwd_wave_qp (ce_solve_qp_wave): row of CE_FWD_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
@@ -315,6 +317,10 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     if (rc) return rc;
     h->wave_variant = fwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->wave_lds = h->wave_variant >= 0 ? fwd_wave_lds_bytes(h->wave_variant, tpl->n, tpl->m) : 0;
+    if (h->plan.qp_native) {      // (the P structure's (row, column) arrays are uploaded on such a handle: upload_engine)
+        h->wave_qp_variant = fwd_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+        h->wave_qp_lds = h->wave_qp_variant >= 0 ? fwd_wave_qp_lds_bytes(h->wave_qp_variant, tpl->n, tpl->m) : 0;
+    }
     h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
     h->newton_wave_variant = newton_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
@@ -543,6 +549,49 @@ int ce_solve_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b
         fa.T = h->T; fa.S = S; fa.Abm = Abm; fa.q = q_vals; fa.sqk = sq_k; fa.sqb = sq_b;
         fa.x = x; fa.y = y; fa.s = s; fa.iters = iters; fa.status = status; fa.resid = resid;
         if (ce_launch_fwd_wave(h->wave_variant, B, h->wave_lds, st, fa)) { g_err = "internal: no wave kernel for the selected row"; return CE_E_BADARG; }
+    }
+    HIPCHK(hipGetLastError());
+    return CE_OK;
+}
+
+// k_fwd_wave_qp: one QP instance per wave, for the small templates fwd_wave_qp_variant serves (ce_lds_fwd_wave_qp.h).  The arguments, layouts, retention and
+// transient-solve rule of ce_solve_qp; the dispatch history is left alone (the kernel takes the instances in index order)
+int ce_wave_qp_variant(ce_handle h) { return h ? h->wave_qp_variant : -1; }
+int ce_wave_qp_lds(ce_handle h) { return (h && h->wave_qp_variant >= 0) ? (int)h->wave_qp_lds : 0; }
+int ce_wave_qp_occupancy(ce_handle h) {
+    if (!h || h->wave_qp_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_fwd_wave_qp(h->wave_qp_variant, h->wave_qp_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_solve_qp_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *q_vals, long sq_k, long sq_b,
+                     const double *P_vals, const ce_settings *settings, double *x, double *y, double *s, int *iters, int *status, double *resid, void *stream) {
+    if (!h || B <= 0 || !A_vals || !q_vals || !x || !y || !s || !iters || !status) { g_err = "null argument"; return CE_E_BADARG; }
+    if (h->wave_qp_variant < 0) {
+        const bool lin = h->nnz_p <= 0;
+        const bool in_class = fwd_wave_qp_variant(h->T.n, h->T.m, h->T.z, h->T.l, h->T.nq, h->q.data(), h->T.ns, h->T.nep, h->T.np, h->nnz_p) >= 0;
+        g_err = std::string("ce_solve_qp_wave: ") + (in_class ? "the template does not run P inside the kernels (ce_qp_native == 0)"
+                                                              : fwd_wave_qp_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p)) +
+                "; use " + (lin ? "ce_solve" : "ce_solve_qp");
+        return CE_E_UNSUPPORTED;
+    }
+    if (!P_vals) { g_err = "ce_solve_qp_wave: template created with a P structure: P_vals is required"; return CE_E_BADARG; }
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    ce_settings S; if (settings) S = *settings; else ce_default_settings(&S);
+    if (S.acceleration_interval <= 0) S.acceleration_interval = 10;
+    const double *Abm = nullptr;
+    const bool transient = h->transient_solve;
+    if (transient && !(sA_k == 1 && sA_b == h->T.nnz_aug)) { g_err = "transient solve: A_vals must be batch-major (the layout workspace may hold the retained forward inputs)"; return CE_E_BADARG; }
+    int rc = to_batch_major(h, B, A_vals, sA_k, sA_b, st, &Abm);
+    if (rc) return rc;
+    if (!transient) { h->retained_A = Abm; h->retained_B = B; }
+    {
+        ProfScope ps(h, 0, st);
+        CeFwdArgs fa{};
+        fa.T = h->T; fa.S = S; fa.Abm = Abm; fa.q = q_vals; fa.sqk = sq_k; fa.sqb = sq_b; fa.P = P_vals; fa.nnz_p = h->nnz_p;
+        fa.x = x; fa.y = y; fa.s = s; fa.iters = iters; fa.status = status; fa.resid = resid;
+        if (ce_launch_fwd_wave_qp(h->wave_qp_variant, B, h->wave_qp_lds, st, fa, h->d_prow.get(), h->d_pcol.get(), h->p_tri)) { g_err = "internal: no QP wave kernel for the selected row"; return CE_E_BADARG; }
     }
     HIPCHK(hipGetLastError());
     return CE_OK;

@@ -133,6 +133,13 @@ class ConeEngine:
         L = _lib.lib()
         return int(L.ce_wave_variant(self._h)), int(L.ce_wave_lds(self._h))
 
+    def wave_qp_plan(self):
+        """(variant, lds) of the one-instance-per-wave forward kernel of a quadratic objective, k_fwd_wave_qp, on this template: the row of
+        csrc/ce_variants_fwd_wave_qp.h that serves it (-1: not served -- no P structure or one the kernels do not run natively, a PSD / exponential / power
+        cone, n > 32 or m > 64) and the launch's LDS bytes (0 when not served)."""
+        L = _lib.lib()
+        return int(L.ce_wave_qp_variant(self._h)), int(L.ce_wave_qp_lds(self._h))
+
     def bwd_wave_plan(self):
         """(variant, lds) of the one-instance-per-wave adjoint kernel k_bwd_wave on this template: the row of csrc/ce_variants_bwd_wave.h that serves it (-1: not
         served -- wave_plan's class) and the launch's LDS bytes (0 when not served)."""
@@ -162,7 +169,8 @@ class ConeEngine:
         warm = (x, y, s) of shapes (B, n), (B, m), (B, m): initial point (instances with non-finite entries start cold).
         path: None -- the dispatcher decides (per instance / shared A); "const_a" or "per_instance": the path a caller already knows (solve_transient: the
         perturbed solves of a backward follow their forward's path without comparing values again).
-        wave: run ce_solve_wave (k_fwd_wave, one instance per wave; per-instance A, wave_plan()[0] >= 0) instead of ce_solve; an engine it does not serve raises."""
+        wave: run ce_solve_wave (k_fwd_wave, one instance per wave; per-instance A, wave_plan()[0] >= 0) instead of ce_solve -- with P_bm, ce_solve_qp_wave
+        (k_fwd_wave_qp; wave_qp_plan()[0] >= 0) instead of ce_solve_qp; an engine the entry does not serve raises."""
         B = A_bm.shape[0]
         dev = self.device
         if B == 0:        # empty batch: nothing to launch (the C ABI refuses B <= 0)
@@ -179,9 +187,7 @@ class ConeEngine:
         # direct engine users (tests, probes): vjp() without q_eval may use the objective of the most recent solve() -- but only for the SAME value buffer
         # (the plugin always passes q_eval explicitly; a q paired with another call's A would silently change the full adjoint system: ADVICE round 5)
         self._last_q, self._last_q_key = q_eval.detach(), (A_bm.data_ptr(), B)
-        self.last_forward_kernel = "k_fwd_wave" if wave else None
-        if wave and P_bm is not None:
-            raise RuntimeError("solve(wave=True): the wave kernel serves a linear objective")
+        self.last_forward_kernel = ("k_fwd_wave_qp" if P_bm is not None else "k_fwd_wave") if wave else None
         if not wave and P_bm is None and (path == "const_a" if path is not None else self._use_const_a(A_bm)):
             from cvxpylayers_amd.interfaces.const_a import solve_const_a
             self.last_path = "const_a"
@@ -199,7 +205,12 @@ class ConeEngine:
         iters = torch.empty((B,), dtype=torch.int32, device=dev)
         status = torch.empty((B,), dtype=torch.int32, device=dev)
         resid = torch.empty((B, 3), dtype=torch.float64, device=dev)
-        if P_bm is not None:
+        if P_bm is not None and wave:
+            rc = _lib.lib().ce_solve_qp_wave(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
+                                             q_eval.stride(1), P_bm.data_ptr(), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
+                                             iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())
+            _lib.check(rc, "ce_solve_qp_wave")
+        elif P_bm is not None:
             rc = _lib.lib().ce_solve_qp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, q_eval.data_ptr(), q_eval.stride(0),
                                         q_eval.stride(1), P_bm.data_ptr(), C.byref(settings), x.data_ptr(), y.data_ptr(), s.data_ptr(),
                                         iters.data_ptr(), status.data_ptr(), resid.data_ptr(), self._stream())

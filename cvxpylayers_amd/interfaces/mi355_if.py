@@ -218,13 +218,18 @@ class _ConeLayer(torch.autograd.Function):
             # solver_args newton_first with a warm start: Newton steps from it, the termination test, and the forward kernels for the instances that miss it
             # (newton_first.py: one 4-byte host read, also under raise_on_error=False); everything below sees the final full-batch result
             # solver_args forward_kernel="wave": one instance per wave where k_fwd_wave serves the template and the solve is per-instance; said once elsewhere
+            # (a node with P_bm is always solved per instance: k_fwd_wave_qp where it serves the template)
             wave = False
             if fwd_kernel == "wave":
-                wave = (P_bm is None and eng.wave_plan()[0] >= 0 and not (n_newton > 0 and warm is not None) and not eng._use_const_a(A_bm))
+                if P_bm is not None:
+                    wave = eng.wave_qp_plan()[0] >= 0 and not (n_newton > 0 and warm is not None)
+                else:
+                    wave = (eng.wave_plan()[0] >= 0 and not (n_newton > 0 and warm is not None) and not eng._use_const_a(A_bm))
                 if not wave:
-                    _warn_once("forward_kernel_none", "MI355 solver: solver_args forward_kernel='wave' is ignored on this template or path: the wave kernel serves a linear "
-                                                      "objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a per-instance A, and not the remainder "
-                                                      "solve of newton_first; the ordinary kernel ran (info['forward']['kernel'] == 'workgroup')")
+                    _warn_once("forward_kernel_none", "MI355 solver: solver_args forward_kernel='wave' is ignored on this template or path: the wave kernels serve a linear "
+                                                      "or (run inside the kernels) quadratic objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a "
+                                                      "per-instance A, and not the remainder solve of newton_first; the ordinary kernel ran "
+                                                      "(info['forward']['kernel'] == 'workgroup')")
             # solver_args newton_kernel="wave": the Newton steps of refine_steps / newton_first and the direct forward derivative run k_newton_wave where it serves
             # the node -- a per-instance A, a linear objective, the search-free elimination enabled, a served template; said once elsewhere
             nw_wave = False
@@ -274,7 +279,7 @@ class _ConeLayer(torch.autograd.Function):
             # are diffcp's LSQR element from the device-side re-solve); adjoint_report(info) counts them
             info = dict(iters=iters, status=status, resid=resid, acceleration=eng.last_acceleration, adjoint={"status": None, "path": path})
             if fwd_kernel == "wave":
-                info["forward"] = {"kernel": "k_fwd_wave" if wave else "workgroup"}
+                info["forward"] = {"kernel": ("k_fwd_wave_qp" if P_bm is not None else "k_fwd_wave") if wave else "workgroup"}
             # solver_args adjoint_kernel="wave": backward() / adjoint_params run k_bwd_wave where it serves the node -- the default adjoint mode, the per-instance
             # path with q_eval saved, the search-free elimination enabled, a served template; said once elsewhere
             adj_wave = False

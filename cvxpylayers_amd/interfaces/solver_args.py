@@ -239,10 +239,12 @@ def forward_kernel(merged_args: dict) -> str:
     """Which kernel solves the forward problem of a PER-INSTANCE-A template:
     absent / "workgroup" -> the ordinary kernels: one instance per workgroup of 256 or 512 threads (k_fwd2, k_forward_rt, the size-generic kernel);
     "wave" -> k_fwd_wave (ce_solve_wave): one instance per wave, for small templates -- a linear objective, zero / nonnegative / second-order cones, n <= 32,
-    m <= 64 (ConeEngine.wave_plan()[0] >= 0).  The same algorithm and settings, so the same statuses, points within the solver's tolerance and iteration counts
-    within a check interval; cold solves, warm starts and raise_on_error=False alike.  info["forward"]["kernel"] tells which ran ("k_fwd_wave" / "workgroup").
-    Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger template, a shared A, the remainder solve of newton_first --
-    ignores the key with one notice and runs the ordinary kernel; LPGD's perturbed re-solves always run the ordinary kernel."""
+    m <= 64 (ConeEngine.wave_plan()[0] >= 0) -- and, on a node whose quadratic objective runs inside the kernels, k_fwd_wave_qp (ce_solve_qp_wave): the same
+    class with a P structure (ConeEngine.wave_qp_plan()[0] >= 0).  The same algorithm and settings, so the same statuses, points within the solver's tolerance
+    and iteration counts within a check interval; cold solves, warm starts and raise_on_error=False alike.  info["forward"]["kernel"] tells which ran
+    ("k_fwd_wave" / "k_fwd_wave_qp" / "workgroup").  Every other template or path -- a PSD / exponential / power cone, a larger template, a shared A, the
+    remainder solve of newton_first -- ignores the key with one notice and runs the ordinary kernel; LPGD's perturbed re-solves, refine_steps, the adjoint,
+    forward-mode AD and jacobian of a QP node always run their ordinary kernels."""
     mode = merged_args.get("forward_kernel", "workgroup")
     if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
         raise ValueError(f"MI355 solver: forward_kernel must be 'workgroup' or 'wave', got {mode!r}")

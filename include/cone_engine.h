@@ -92,7 +92,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params, and ce_solve_wave, ce_wave_variant, ce_wave_lds and ce_wave_occupancy, and ce_vjp_many_wave, ce_vjp_many_params_wave, ce_bwd_wave_many_variant, ce_bwd_wave_many_lds, ce_bwd_wave_many_chunk and ce_bwd_wave_many_occupancy, and ce_jvp_many_wave, ce_jvp_wave_many_variant, ce_jvp_wave_many_lds, ce_jvp_wave_many_chunk and ce_jvp_wave_many_occupancy; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params, and ce_solve_wave, ce_wave_variant, ce_wave_lds and ce_wave_occupancy, and ce_vjp_many_wave, ce_vjp_many_params_wave, ce_bwd_wave_many_variant, ce_bwd_wave_many_lds, ce_bwd_wave_many_chunk and ce_bwd_wave_many_occupancy, and ce_jvp_many_wave, ce_jvp_wave_many_variant, ce_jvp_wave_many_lds, ce_jvp_wave_many_chunk and ce_jvp_wave_many_occupancy, and ce_solve_qp_wave, ce_wave_qp_variant, ce_wave_qp_lds and ce_wave_qp_occupancy; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -147,6 +147,33 @@ int ce_solve_wave(ce_handle h, int B,
 int ce_wave_variant(ce_handle h);
 int ce_wave_lds(ce_handle h);
 int ce_wave_occupancy(ce_handle h);
+
+/*
+ * ce_solve_qp, ONE INSTANCE PER WAVE, for small quadratic programs (k_fwd_wave_qp; no reference call site; additions under ABI 17).  ce_solve_wave's kernel with
+ * SCS 3's QP embedding: P-hat = E P E is a third dense matrix in the wave's LDS, the reduced matrix is rho_x I + P-hat + A-hat^T R_y^-1 A-hat, tau-tilde is the
+ * positive root of the embedding's quadratic, and P x enters the dual residual, the gap and the scales of the termination test.
+ *   served           : a P structure on a handle that runs P inside the kernels (ce_qp_native == 1), zero / nonnegative / second-order cones of any dimensions,
+ *                      n <= 32, m <= 64, any sparsity pattern of A and P.
+ *   ce_solve_qp_wave : arguments, layouts (P_vals [B][nnz_p] in the structure's order; a one-triangle structure stands for both triangles), outputs, status codes
+ *                      (-4: the reduced matrix is not positive definite, i.e. P is not positive semidefinite -- that instance's x, y, s are NaN), warm start,
+ *                      retention (ce_vjp_qp with A_vals == NULL) and transient-solve rule of ce_solve_qp; every ce_settings field is honoured (acceleration: one
+ *                      secant pair for any positive lookback).  The dispatch history is neither read nor written.  CE_E_UNSUPPORTED on a handle it does not serve
+ *                      (a linear objective, other cones, sizes), before anything is enqueued and with nothing written; ce_last_error names the reason.
+ *                      CE_E_BADARG on a NULL P_vals.
+ *   ce_wave_qp_variant : the row of the kernel's instantiation list (csrc/ce_variants_fwd_wave_qp.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_wave_qp_lds     : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_wave_qp_occupancy: resident workgroups (= instances) per CU of that row at that footprint, as the runtime's occupancy query reports it (0 when not served).
+ */
+int ce_solve_qp_wave(ce_handle h, int B,
+                     const double *A_vals, long sA_k, long sA_b,
+                     const double *q_vals, long sq_k, long sq_b,
+                     const double *P_vals,
+                     const ce_settings *settings,
+                     double *x, double *y, double *s, int *iters, int *status, double *resid,
+                     void *stream);
+int ce_wave_qp_variant(ce_handle h);
+int ce_wave_qp_lds(ce_handle h);
+int ce_wave_qp_occupancy(ce_handle h);
 
 /*
  * Backward (vector-Jacobian product), diffcp adjoint with ds = 0 (diffcp_if.py:84).
