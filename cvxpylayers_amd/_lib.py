@@ -24,7 +24,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_vjp_many_wave", "ce_vjp_many_params_wave", "ce_bwd_wave_many_variant", "ce_bwd_wave_many_lds", "ce_bwd_wave_many_chunk", "ce_bwd_wave_many_occupancy",
            "ce_jvp_wave", "ce_refine_wave", "ce_newton_wave_variant", "ce_newton_wave_lds", "ce_newton_wave_occupancy",
            "ce_jvp_many_wave", "ce_jvp_wave_many_variant", "ce_jvp_wave_many_lds", "ce_jvp_wave_many_chunk", "ce_jvp_wave_many_occupancy",
-           "ce_solve_qp_wave", "ce_wave_qp_variant", "ce_wave_qp_lds", "ce_wave_qp_occupancy"]
+           "ce_solve_qp_wave", "ce_wave_qp_variant", "ce_wave_qp_lds", "ce_wave_qp_occupancy",
+           "ce_vjp_qp_wave", "ce_bwd_wave_qp_variant", "ce_bwd_wave_qp_lds", "ce_bwd_wave_qp_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -148,6 +149,8 @@ def lib():
     L.ce_solve_qp_wave.argtypes = L.ce_solve_qp.argtypes
     L.ce_wave_qp_variant.argtypes = [vp]; L.ce_wave_qp_lds.argtypes = [vp]; L.ce_wave_qp_occupancy.argtypes = [vp]
     L.ce_vjp_qp.argtypes = [vp, C.c_int, dp, lg, lg, dp, dp, dp, dp, dp, dp, dp, lg, lg, dp, lg, lg, dp, ip, vp]
+    L.ce_vjp_qp_wave.argtypes = list(L.ce_vjp_qp.argtypes)
+    L.ce_bwd_wave_qp_variant.argtypes = [vp]; L.ce_bwd_wave_qp_lds.argtypes = [vp]; L.ce_bwd_wave_qp_occupancy.argtypes = [vp]
     L.ce_value.argtypes = [vp, C.c_int, dp, lg, lg, dp, lg, lg, dp, ip, ip, C.c_int, dp, dp, dp, dp, vp]
     L.ce_value_jvp.argtypes = [vp, C.c_int, dp, lg, dp, lg, lg, dp, ip, ip, C.c_int, dp, dp, dp, vp]
     L.ce_value_vjp.argtypes = [vp, C.c_int, dp, dp, dp, vp, dp, lg, lg, dp, lg, lg, dp, ip, ip, C.c_int, vp]

@@ -292,6 +292,10 @@ hipError_t ce_occupancy_fwd_wave_qp(int variant, size_t lds, int *blocks);
 // ce_tu_bwd_wave.hip: k_bwd_wave, the adjoint of one instance per wave (row of CE_BWD_WAVE_VARIANTS, ce_variants_bwd_wave.h; reads CeBwdArgs' dA_factors itself)
 int ce_launch_bwd_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
 hipError_t ce_occupancy_bwd_wave(int variant, size_t lds, int *blocks);
+// ce_tu_bwd_wave_qp.hip: k_bwd_wave_qp, the adjoint of one QP instance per wave (row of CE_BWD_WAVE_QP_VARIANTS, ce_variants_bwd_wave_qp.h; reads CeBwdArgs' P,
+// nnz_p, prow, pcol, p_tri and dP; neither fix nor dA_factors)
+int ce_launch_bwd_wave_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a);
+hipError_t ce_occupancy_bwd_wave_qp(int variant, size_t lds, int *blocks);
 // ce_tu_bwd_wave_many.hip: k_bwd_wave_many, K cotangents of one instance per wave and chunk (row of CE_BWD_WAVE_MANY_VARIANTS, ce_variants_bwd_wave_many.h): the grid
 // is B x ceil(w.K / KC) workgroups of 64 threads
 int ce_launch_bwd_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const BwdWaveMany &w);

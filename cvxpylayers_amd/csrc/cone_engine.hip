@@ -38,6 +38,7 @@
 #include "ce_lds_fwd_wave.h"   // k_fwd_wave (ce_solve_wave): served class, row and footprint -- beside the plan, not a field of it
 #include "ce_lds_fwd_wave_qp.h"   // k_fwd_wave_qp (ce_solve_qp_wave): the same for the one-wave forward kernel of a quadratic objective
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
+#include "ce_lds_bwd_wave_qp.h"   // k_bwd_wave_qp (ce_vjp_qp_wave): the same for the one-wave adjoint of a quadratic objective
 #include "ce_lds_newton_wave.h"   // k_newton_wave (ce_jvp_wave, ce_refine_wave): the same for the one-wave forward derivative and refinement step
 #include "ce_lds_jvp_wave_many.h"   // k_jvp_wave_many (ce_jvp_many_wave): the same for the many-tangent twin of the forward derivative
 #include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
@@ -107,9 +108,11 @@ struct ce_engine {
     int wave_variant = -1; size_t wave_lds = 0;      // k_fwd_wave (ce_solve_wave): row of CE_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int wave_qp_variant = -1; size_t wave_qp_lds = 0;      // k_fwd_wave_qp (ce_solve_qp_wave): row of CE_FWD_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int bwd_wave_qp_variant = -1; size_t bwd_wave_qp_lds = 0;      // k_bwd_wave_qp (ce_vjp_qp_wave): row of CE_BWD_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int jvp_wave_many_variant = -1; size_t jvp_wave_many_lds = 0;      // k_jvp_wave_many (ce_jvp_many_wave): row of CE_JVP_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    bool call_wave_qp = false;      // (ce_vjp_qp_wave -> ce_vjp_qp: the call in flight runs k_bwd_wave_qp in the place of k_backward_rt)
     const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
     bool transient_solve = false;          // ce_set_transient_solve: ce_solve / ce_solve_qp leave retained_A and the dispatch history as they found them
     uintptr_t summary_host_checked = 0; char *summary_host_dev = nullptr;      // ce_status_summary: the last 64-byte line of host memory examined and its device alias (null: not mapped)
@@ -320,6 +323,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
     if (h->plan.qp_native) {      // (the P structure's (row, column) arrays are uploaded on such a handle: upload_engine)
         h->wave_qp_variant = fwd_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
         h->wave_qp_lds = h->wave_qp_variant >= 0 ? fwd_wave_qp_lds_bytes(h->wave_qp_variant, tpl->n, tpl->m) : 0;
+        h->bwd_wave_qp_variant = bwd_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+        h->bwd_wave_qp_lds = h->bwd_wave_qp_variant >= 0 ? bwd_wave_qp_lds_bytes(h->bwd_wave_qp_variant, tpl->n, tpl->m) : 0;
     }
     h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
@@ -723,7 +728,9 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
         ba.p_tri = h->p_tri; ba.dP = dP_vals; ba.gA = gA; ba.gK = gK;
         int lrc;
         h->last_fast = -1;
-        if (wave) {          // (do_fix holds: the entry refused otherwise)
+        if (h->call_wave_qp) {          // (ce_vjp_qp_wave: a served handle and P_vals, the entry refused otherwise; no list, no factor mode)
+            lrc = ce_launch_bwd_wave_qp(h->bwd_wave_qp_variant, B, h->bwd_wave_qp_lds, st, ba);
+        } else if (wave) {          // (do_fix holds: the entry refused otherwise)
             ba.dA_factors = factors ? 1 : 0;
             lrc = ce_launch_bwd_wave(h->bwd_wave_variant, B, h->bwd_wave_lds, st, ba);
         } else if (do_fix && P.ns_variant >= 0) {
@@ -789,6 +796,36 @@ int ce_vjp_qp(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, co
     }
     HIPCHK(hipGetLastError());
     return flush_dispatch_order(h, st, nullptr, nullptr);
+}
+
+// k_bwd_wave_qp: the adjoint of one QP instance per wave, for the small templates bwd_wave_qp_variant serves on a handle that runs P inside the kernels
+// (ce_lds_bwd_wave_qp.h).  ce_vjp_qp's arguments and the whole of its body (layouts, retained A, the layout pass of a batch-minor dA) with the wave kernel where
+// the P branch launches k_backward_rt; refused, before anything is enqueued, where the handle is not served.
+int ce_bwd_wave_qp_variant(ce_handle h) { return h ? h->bwd_wave_qp_variant : -1; }
+int ce_bwd_wave_qp_lds(ce_handle h) { return (h && h->bwd_wave_qp_variant >= 0) ? (int)h->bwd_wave_qp_lds : 0; }
+int ce_bwd_wave_qp_occupancy(ce_handle h) {
+    if (!h || h->bwd_wave_qp_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_bwd_wave_qp(h->bwd_wave_qp_variant, h->bwd_wave_qp_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_vjp_qp_wave(ce_handle h, int B, const double *A_vals, long sA_k, long sA_b, const double *P_vals,
+                   const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                   double *dA_vals, long sdA_k, long sdA_b, double *dq_vals, long sdq_k, long sdq_b, double *dP_vals, int *adj_status, void *stream) {
+    if (!h) { g_err = "ce_vjp_qp_wave: null argument"; return CE_E_BADARG; }
+    if (h->bwd_wave_qp_variant < 0) {
+        const bool lin = h->nnz_p <= 0;
+        const bool in_class = bwd_wave_qp_variant(h->T.n, h->T.m, h->T.z, h->T.l, h->T.nq, h->q.data(), h->T.ns, h->T.nep, h->T.np, h->nnz_p) >= 0;
+        g_err = std::string("ce_vjp_qp_wave: ") + (in_class ? "the template does not run P inside the kernels (ce_qp_native == 0)"
+                                                            : bwd_wave_qp_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p)) +
+                "; use " + (lin ? "ce_vjp" : "ce_vjp_qp");
+        return CE_E_UNSUPPORTED;
+    }
+    if (!P_vals || !dP_vals) { g_err = "ce_vjp_qp_wave: template created with a P structure: P_vals and dP_vals are required"; return CE_E_BADARG; }
+    h->call_wave_qp = true;
+    const int rc = ce_vjp_qp(h, B, A_vals, sA_k, sA_b, P_vals, x, y, s, dx, dy, dA_vals, sdA_k, sdA_b, dq_vals, sdq_k, sdq_b, dP_vals, adj_status, stream);
+    h->call_wave_qp = false;
+    return rc;
 }
 
 // K cotangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., MANY> factors every instance once and writes all K answers; the instances

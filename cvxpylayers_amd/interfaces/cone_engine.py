@@ -41,7 +41,7 @@ class ConeEngine:
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
         self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
-        self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), "k_bwd_wave_many" when the last vjp_many() / vjp_many_params() ran its many-cotangent twin, None otherwise
+        self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), "k_bwd_wave_qp" when that vjp() had P_bm, "k_bwd_wave_many" when the last vjp_many() / vjp_many_params() ran its many-cotangent twin, None otherwise
         self.last_forward_kernel = None       # "k_fwd_wave" when the last solve() ran the one-instance-per-wave kernel (solve(wave=True)), None otherwise
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
@@ -151,6 +151,12 @@ class ConeEngine:
         csrc/ce_variants_newton_wave.h that serves it (-1: not served -- bwd_wave_plan()'s class) and the launch's LDS bytes (0 when not served)."""
         L = _lib.lib()
         return int(L.ce_newton_wave_variant(self._h)), int(L.ce_newton_wave_lds(self._h))
+
+    def bwd_wave_qp_plan(self):
+        """(variant, lds) of the one-instance-per-wave adjoint kernel of a quadratic objective, k_bwd_wave_qp, on this template: the row of
+        csrc/ce_variants_bwd_wave_qp.h that serves it (-1: not served -- wave_qp_plan()'s class) and the launch's dynamic LDS in bytes (0 when not served)"""
+        L = _lib.lib()
+        return int(L.ce_bwd_wave_qp_variant(self._h)), int(L.ce_bwd_wave_qp_lds(self._h))
 
     def bwd_wave_many_plan(self):
         """(variant, lds, chunk) of the many-cotangent wave adjoint k_bwd_wave_many on this template: the row of csrc/ce_variants_bwd_wave_many.h that serves it
@@ -356,7 +362,8 @@ class ConeEngine:
         lsqr: (atol, btol, iter_lim[, system]) of the shared-A LSQR adjoint (lsqr_rule); None = diffcp's 1e-8 / 1e-8 / 2 (n + m + 1) on the full system.  Ignored by the direct eliminations.
         q_eval: the forward call's (n+1, B) objective values; the shared-A LSQR adjoint then solves diffcp's full (n + m + 1) system (const_a.vjp_const_a).
         wave: run ce_vjp_wave (k_bwd_wave, one instance per wave; per-instance A, bwd_wave_plan()[0] >= 0, q_eval given) instead of ce_vjp; an engine it does
-        not serve, another path or a call without q_eval raises."""
+        not serve, another path or a call without q_eval raises.  With P_bm: ce_vjp_qp_wave (k_bwd_wave_qp; bwd_wave_qp_plan()[0] >= 0) instead of ce_vjp_qp --
+        the search-free elimination, so a rank-deficient instance keeps the dropped-variable answer with status 4 where ce_vjp_qp returns its own basic solution."""
         B = A_bm.shape[0]
         dev = self.device
         self.last_adjoint_kernel = None
@@ -365,8 +372,8 @@ class ConeEngine:
                     torch.empty((0,), dtype=torch.int32, device=dev))
         if path is None:
             path = self.last_path
-        if wave and (P_bm is not None or path != "per_instance"):
-            raise RuntimeError(f"vjp(wave=True): the wave adjoint serves the per-instance path with a linear objective (path {path!r})")
+        if wave and path != "per_instance":
+            raise RuntimeError(f"vjp(wave=True): the wave adjoint serves the per-instance path (path {path!r})")
         if path == "const_a" and (self._launch_info["bwd_mode"] in (1, 2) or os.environ.get("CE_CONST_A") == "1"):
             from cvxpylayers_amd.interfaces.const_a import vjp_const_a      # shared A: batched LSQR with GEMMs over the batch
             if q_eval is None:          # direct engine users: the objective of the most recent solve() of this very value buffer, else the reduced system
@@ -406,10 +413,12 @@ class ConeEngine:
             sk, sb = 1, self.nnz_aug
         if P_bm is not None:      # quadratic objective: also dP (B, nnz_p) batch-major
             dP = torch.empty((B, self.nnz_p), dtype=torch.float64, device=dev)
-            rc = _lib.lib().ce_vjp_qp(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, P_bm.data_ptr(), x.data_ptr(), y.data_ptr(),
-                                      s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
-                                      dq.data_ptr(), B, 1, dP.data_ptr(), adj.data_ptr(), self._stream())
-            _lib.check(rc, "ce_vjp_qp")
+            entry = "ce_vjp_qp_wave" if wave else "ce_vjp_qp"
+            rc = getattr(_lib.lib(), entry)(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, P_bm.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                            s.data_ptr(), dx.data_ptr(), dy.data_ptr(), dA.data_ptr(), sk, sb,
+                                            dq.data_ptr(), B, 1, dP.data_ptr(), adj.data_ptr(), self._stream())
+            _lib.check(rc, entry)
+            self.last_adjoint_kernel = "k_bwd_wave_qp" if wave else None
             return (dA if batch_minor_out else dA.t()), dq, adj, dP
         entry = "ce_vjp_wave" if wave else "ce_vjp"
         rc = getattr(_lib.lib(), entry)(self._h, B, A_bm.data_ptr(), 1, self.nnz_aug, *q_args, x.data_ptr(), y.data_ptr(),

@@ -160,6 +160,7 @@ class _Saved(NamedTuple):
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
     nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave, tangent_many ce_jvp_many_wave (every other route ignores it)
     adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
+    adj_wave_qp: bool = False               # adjoint_kernel() == "wave" on a served node with P_bm: backward() runs k_bwd_wave_qp (every other route ignores it: adj_wave stays False on such a node)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -282,15 +283,20 @@ class _ConeLayer(torch.autograd.Function):
                 info["forward"] = {"kernel": ("k_fwd_wave_qp" if P_bm is not None else "k_fwd_wave") if wave else "workgroup"}
             # solver_args adjoint_kernel="wave": backward() / adjoint_params run k_bwd_wave where it serves the node -- the default adjoint mode, the per-instance
             # path with q_eval saved, the search-free elimination enabled, a served template; said once elsewhere
-            adj_wave = False
+            # A node with P_bm: backward() alone runs k_bwd_wave_qp, under the same conditions on a template bwd_wave_qp_plan serves.
+            adj_wave = adj_wave_qp = False
             if adj_kernel == "wave":
-                adj_wave = ("mode" not in merged_args and lpgd is None and P_bm is None and path == "per_instance" and os.environ.get("CE_BWD_NS") != "0"
-                            and eng.bwd_wave_plan()[0] >= 0 and eng.nnz_aug >= eng.m)          # (a value row shorter than m cannot hold the factors of vjp_params)
-                if not adj_wave:
-                    _warn_once("adjoint_kernel_none", "MI355 solver: solver_args adjoint_kernel='wave' is ignored on this template or path: the wave adjoint serves a linear "
-                                                      "objective, zero / nonnegative / second-order cones, n <= 32, m <= 64, nnz_aug >= m, a per-instance A and the default "
-                                                      "adjoint mode (no mode=, CE_BWD_NS not 0); the ordinary kernel runs (info['adjoint']['kernel'] == 'workgroup')")
-                info["adjoint"]["kernel"] = "k_bwd_wave" if adj_wave else "workgroup"
+                wave_ok = "mode" not in merged_args and lpgd is None and path == "per_instance" and os.environ.get("CE_BWD_NS") != "0"
+                if P_bm is not None:
+                    adj_wave_qp = wave_ok and eng.bwd_wave_qp_plan()[0] >= 0
+                else:
+                    adj_wave = wave_ok and eng.bwd_wave_plan()[0] >= 0 and eng.nnz_aug >= eng.m          # (a value row shorter than m cannot hold the factors of vjp_params)
+                if not (adj_wave or adj_wave_qp):
+                    _warn_once("adjoint_kernel_none", "MI355 solver: solver_args adjoint_kernel='wave' is ignored on this template or path: the wave adjoints serve a linear "
+                                                      "objective (nnz_aug >= m) or a quadratic one inside the kernels, zero / nonnegative / second-order cones, n <= 32, "
+                                                      "m <= 64, a per-instance A and the default adjoint mode (no mode=, CE_BWD_NS not 0); the ordinary kernel runs "
+                                                      "(info['adjoint']['kernel'] == 'workgroup')")
+                info["adjoint"]["kernel"] = "k_bwd_wave" if adj_wave else ("k_bwd_wave_qp" if adj_wave_qp else "workgroup")
             if refine_info is not None:
                 info["refine"] = refine_info
             if nf_info is not None:
@@ -300,7 +306,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, nw_wave and path == "per_instance", adj_wave) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, nw_wave and path == "per_instance", adj_wave, adj_wave_qp) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -410,7 +416,8 @@ class _ConeLayer(torch.autograd.Function):
                                                                failed=failed, batch_minor_out=saved.batch_minor_in)
                 dP = dP_bm.t().to(in_device) if dP_bm is not None else None
             elif saved.P_bm is not None:
-                dA, dq, adj, dP_bm = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, P_bm=saved.P_bm, path=saved.path, lsqr=saved.lsqr)
+                dA, dq, adj, dP_bm = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, P_bm=saved.P_bm, path=saved.path, lsqr=saved.lsqr,
+                                             **({"wave": True} if saved.adj_wave_qp else {}))
                 dP = dP_bm.t().to(in_device)
             else:
                 dA, dq, adj = eng.vjp(saved.A_bm, x, y, s, dx, dy, batch_minor_out=saved.batch_minor_in, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval,

@@ -256,8 +256,12 @@ def adjoint_kernel(merged_args: dict) -> str:
     absent / "workgroup" -> the ordinary kernels: one instance per workgroup of 256 threads (k_backward_ns with the LSQR re-solve behind it, or the pivoting kernels);
     "wave" -> k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): one instance per wave, for small templates -- forward_kernel="wave"'s class
     (ConeEngine.bwd_wave_plan()[0] >= 0).  The same system, rules, flags and LSQR re-solve of flagged instances; gradients agree to rounding, not bit for bit.
-    info["adjoint"]["kernel"] tells which runs ("k_bwd_wave" / "workgroup").  Independent of forward_kernel; composes with param_grad="factors".
-    Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger template, a shared A, any mode= key (LPGD included),
+    On a node whose quadratic objective runs inside the kernels, k_bwd_wave_qp (ce_vjp_qp_wave; ConeEngine.bwd_wave_qp_plan()[0] >= 0) in the place of the
+    pivoting kernel of ce_vjp_qp: the search-free elimination with P, so a rank-deficient instance keeps the dropped-variable answer with status 4 where
+    ce_vjp_qp returns its own basic solution (the difference qp_adjoint="search_free" documents; no LSQR has a P term).
+    info["adjoint"]["kernel"] tells which runs ("k_bwd_wave" / "k_bwd_wave_qp" / "workgroup").  Independent of forward_kernel; composes with param_grad="factors"
+    on a linear objective.
+    Every other template or path -- a quadratic objective outside the kernels, a PSD / exponential / power cone, a larger template, a shared A, any mode= key (LPGD included),
     CE_BWD_NS=0 -- ignores the key with one notice and runs what it ran; layer.jacobian, forward-mode AD and the many-cotangent routes do not read it."""
     mode = merged_args.get("adjoint_kernel", "workgroup")
     if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
