@@ -25,7 +25,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_jvp_wave", "ce_refine_wave", "ce_newton_wave_variant", "ce_newton_wave_lds", "ce_newton_wave_occupancy",
            "ce_jvp_many_wave", "ce_jvp_wave_many_variant", "ce_jvp_wave_many_lds", "ce_jvp_wave_many_chunk", "ce_jvp_wave_many_occupancy",
            "ce_solve_qp_wave", "ce_wave_qp_variant", "ce_wave_qp_lds", "ce_wave_qp_occupancy",
-           "ce_vjp_qp_wave", "ce_bwd_wave_qp_variant", "ce_bwd_wave_qp_lds", "ce_bwd_wave_qp_occupancy"]
+           "ce_vjp_qp_wave", "ce_bwd_wave_qp_variant", "ce_bwd_wave_qp_lds", "ce_bwd_wave_qp_occupancy",
+           "ce_jvp_qp_wave", "ce_refine_qp_wave", "ce_newton_wave_qp_variant", "ce_newton_wave_qp_lds", "ce_newton_wave_qp_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -115,6 +116,9 @@ def lib():
     L.ce_jvp_wave.argtypes = L.ce_jvp.argtypes
     L.ce_refine_wave.argtypes = L.ce_refine.argtypes
     L.ce_newton_wave_variant.argtypes = [vp]; L.ce_newton_wave_lds.argtypes = [vp]; L.ce_newton_wave_occupancy.argtypes = [vp, C.c_int]
+    L.ce_jvp_qp_wave.argtypes = list(L.ce_jvp_qp.argtypes)
+    L.ce_refine_qp_wave.argtypes = list(L.ce_refine_qp.argtypes)
+    L.ce_newton_wave_qp_variant.argtypes = [vp]; L.ce_newton_wave_qp_lds.argtypes = [vp]; L.ce_newton_wave_qp_occupancy.argtypes = [vp, C.c_int]
     L.ce_vjp_tri_many_params.argtypes = L.ce_vjp_psd_many_params.argtypes = L.ce_vjp_psd_tri_many_params.argtypes = L.ce_vjp_many_params.argtypes
     L.ce_vjp_qp_many_params.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, dp, dp, dp, dp, dp, C.c_int, ip, ip, ip, dp, dp, dp, ip, vp]
     L.ce_param_grad_variant.argtypes = [vp]

@@ -96,6 +96,13 @@ struct NsQp {
     const int *pmap;         // [n][n]     entry of the structure at (i, j), -1: structural zero; a one-triangle structure maps (i, j) and (j, i) to one entry
     int nnz_p;
 };
+// k_newton_wave_qp: the quadratic objective of the instance as the wave kernels read it -- through the structure's (row, column) arrays, not the dense entry map
+struct NwQp {
+    const double *P;         // [B][nnz_p] values of P in the template's structure order
+    const double *tP;        // [B][nnz_p] their tangent (the forward derivative only; NULL: zero)
+    const int *prow, *pcol;  // [nnz_p]    (row, column) of every entry of the structure
+    int nnz_p, p_tri;        // p_tri: one triangle is stored and an off-diagonal entry stands for both
+};
 struct NsJvpQp : NsJvp { NsQp Q; };
 struct NsRefineQp : NsRefine { NsQp Q; };
 struct NsJvpQpMany : NsJvpMany { NsQp Q; long stPk, stPb; };          // Q.tP: tangent k of instance i's P row at Q.tP + k * stPk + i * stPb
@@ -305,6 +312,11 @@ hipError_t ce_occupancy_bwd_wave_many(int variant, size_t lds, int *blocks);
 int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);
 int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w);
 hipError_t ce_occupancy_newton_wave(int variant, int refine, size_t lds, int *blocks);
+// ce_tu_newton_wave_qp.hip: k_newton_wave_qp, the same two modes with a quadratic objective inside (row of CE_NEWTON_WAVE_QP_VARIANTS,
+// ce_variants_newton_wave_qp.h); a.adj is the forward derivative's status, a.fix is not read (no re-solve list behind a P launch)
+int ce_launch_newton_wave_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w, const NwQp &q);
+int ce_launch_newton_wave_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsRefine &w, const NwQp &q);
+hipError_t ce_occupancy_newton_wave_qp(int variant, int refine, size_t lds, int *blocks);
 // ce_tu_jvp_wave_many.hip: k_jvp_wave_many, K tangents of one instance per wave and chunk (row of CE_JVP_WAVE_MANY_VARIANTS, ce_variants_jvp_wave_many.h): the grid
 // is B x ceil(w.K / KC) workgroups of 64 threads; NsJvpMany as k_backward_ns<FWD, MANY> takes it (its structure arrays are not read)
 int ce_launch_jvp_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvpMany &w);

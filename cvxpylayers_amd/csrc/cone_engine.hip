@@ -40,6 +40,7 @@
 #include "ce_lds_bwd_wave.h"   // k_bwd_wave (ce_vjp_wave, ce_vjp_params_wave): the same for the one-wave adjoint
 #include "ce_lds_bwd_wave_qp.h"   // k_bwd_wave_qp (ce_vjp_qp_wave): the same for the one-wave adjoint of a quadratic objective
 #include "ce_lds_newton_wave.h"   // k_newton_wave (ce_jvp_wave, ce_refine_wave): the same for the one-wave forward derivative and refinement step
+#include "ce_lds_newton_wave_qp.h"   // k_newton_wave_qp (ce_jvp_qp_wave, ce_refine_qp_wave): the same for the one-wave forward derivative and refinement step of a quadratic objective
 #include "ce_lds_jvp_wave_many.h"   // k_jvp_wave_many (ce_jvp_many_wave): the same for the many-tangent twin of the forward derivative
 #include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
 
@@ -111,6 +112,7 @@ struct ce_engine {
     int bwd_wave_qp_variant = -1; size_t bwd_wave_qp_lds = 0;      // k_bwd_wave_qp (ce_vjp_qp_wave): row of CE_BWD_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int newton_wave_qp_variant = -1; size_t newton_wave_qp_lds = 0;      // k_newton_wave_qp (ce_jvp_qp_wave, ce_refine_qp_wave): row of CE_NEWTON_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int jvp_wave_many_variant = -1; size_t jvp_wave_many_lds = 0;      // k_jvp_wave_many (ce_jvp_many_wave): row of CE_JVP_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
     bool call_wave_qp = false;      // (ce_vjp_qp_wave -> ce_vjp_qp: the call in flight runs k_bwd_wave_qp in the place of k_backward_rt)
     const char *call_wave = nullptr;      // (ce_vjp_wave / ce_vjp_params_wave -> ce_vjp_qp: the entry whose call in flight runs k_bwd_wave in the place of k_backward_ns)
@@ -325,6 +327,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
         h->wave_qp_lds = h->wave_qp_variant >= 0 ? fwd_wave_qp_lds_bytes(h->wave_qp_variant, tpl->n, tpl->m) : 0;
         h->bwd_wave_qp_variant = bwd_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
         h->bwd_wave_qp_lds = h->bwd_wave_qp_variant >= 0 ? bwd_wave_qp_lds_bytes(h->bwd_wave_qp_variant, tpl->n, tpl->m) : 0;
+        h->newton_wave_qp_variant = newton_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+        h->newton_wave_qp_lds = h->newton_wave_qp_variant >= 0 ? newton_wave_qp_lds_bytes(h->newton_wave_qp_variant, tpl->n, tpl->m) : 0;
     }
     h->bwd_wave_variant = bwd_wave_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
     h->bwd_wave_lds = h->bwd_wave_variant >= 0 ? bwd_wave_lds_bytes(h->bwd_wave_variant, tpl->n, tpl->m) : 0;
@@ -1583,16 +1587,26 @@ static int qp_ns_check(ce_handle h, const char *who) {
     if (h->plan.qp_ns_variant < 0) { g_err = std::string(who) + ": this template has no search-free elimination with a quadratic objective (n > 108, its footprint exceeds LDS, or CE_BWD_NS=0)"; return CE_E_UNSUPPORTED; }
     return CE_OK;
 }
+// ce_jvp_qp_wave / ce_refine_qp_wave (`who`) on a handle k_newton_wave_qp does not serve: the reason, and the entry to use instead (`use`, the linear objective's: `use_lin`)
+static int newton_wave_qp_refuse(ce_handle h, const std::string &who, const char *use, const char *use_lin) {
+    const bool in_class = newton_wave_qp_variant(h->T.n, h->T.m, h->T.z, h->T.l, h->T.nq, h->q.data(), h->T.ns, h->T.nep, h->T.np, h->nnz_p) >= 0;
+    g_err = who + ": " + (in_class ? "the template does not run P inside the kernels (ce_qp_native == 0)"
+                                   : newton_wave_qp_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p)) + "; use " + (h->nnz_p <= 0 ? use_lin : use);
+    return CE_E_UNSUPPORTED;
+}
 // The forward derivative as ce_vjp_qp runs the adjoint: the search-free elimination (k_backward_ns<..., FWD>), then the fixed grid of LSQR workgroups that
 // re-solves the instances it listed as rank deficient -- the same re-solve list.  With P_vals (ce_jvp_qp: k_backward_ns<..., FWD, QP>) one launch and no re-solve list: no LSQR has a P term.
 static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals,
                   const double *x, const double *y, const double *s, const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
-                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (psd_tri: ce_jvp_psd_tri -- PSD blocks and triples, the row with both kinds' segments; wave: ce_jvp_wave -- k_newton_wave in the place of k_backward_ns)
+                  double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, double atol, double btol, double conlim, int iter_lim, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (psd_tri: ce_jvp_psd_tri -- PSD blocks and triples, the row with both kinds' segments; wave: ce_jvp_wave -- k_newton_wave in the place of k_backward_ns; with P_vals: ce_jvp_qp_wave -- k_newton_wave_qp)
     const bool qp = P_vals != nullptr;
-    const std::string who = wave ? "ce_jvp_wave" : qp ? "ce_jvp_qp" : (psd_tri ? "ce_jvp_psd_tri" : (psd ? "ce_jvp_psd" : "ce_jvp"));
+    const std::string who = wave ? (qp ? "ce_jvp_qp_wave" : "ce_jvp_wave") : qp ? "ce_jvp_qp" : (psd_tri ? "ce_jvp_psd_tri" : (psd ? "ce_jvp_psd" : "ce_jvp"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     int rc = CE_OK;
+    if (wave && qp) {          // (refused before anything is enqueued, nothing written; no re-solve to arm: the dropped-variable answer stands, as ce_jvp_qp's)
+        if (h->newton_wave_qp_variant < 0) return newton_wave_qp_refuse(h, who, "ce_jvp_qp", "ce_jvp");
+    } else
     if (wave) {          // (refused before anything is enqueued, nothing written)
         if (h->newton_wave_variant < 0) { g_err = who + ": " + newton_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_jvp"; return CE_E_UNSUPPORTED; }
         if (!(h->resolve && q_vals && resolve_fits(h))) {
@@ -1623,7 +1637,8 @@ static int jvp_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const 
     CeBwdArgs ba{};
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.adj = jvp_status; ba.fix = fix.cur;
     const NsJvp W{h->d_csc_ptr.get(), h->d_csr_ptr.get(), h->d_csr_col.get(), h->d_csr_src.get(), h->d_bpos.get(), tA_vals_bm, tq_vals, stq_k, stq_b, dx, dy, ds, lsqr_iters};
-    const int lrc = wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
+    const int lrc = (wave && qp) ? ce_launch_newton_wave_qp(h->newton_wave_qp_variant, B, h->newton_wave_qp_lds, st, ba, W, NwQp{P_vals, tP_vals, h->d_prow.get(), h->d_pcol.get(), h->nnz_p, h->p_tri ? 1 : 0})
+                  : wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
                   : qp ? ce_launch_ns(variant, B, lds, st, ba, NsJvpQp{W, NsQp{P_vals, tP_vals, h->d_pmap.get(), h->nnz_p}})
                   : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsdTri{W})
                   : psd ? ce_launch_ns(variant, B, lds, st, ba, NsJvpPsd{W})
@@ -1679,6 +1694,25 @@ int ce_jvp_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const doub
               double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "null argument"; return CE_E_BADARG; }
     return jvp_ns(h, B, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, tP_vals, dx, dy, ds, jvp_status, lsqr_iters, 0.0, 0.0, 0.0, 0, stream);
+}
+// k_newton_wave_qp: the forward derivative and the refinement step of one QP instance per wave, for the small templates newton_wave_qp_variant serves on a handle
+// that runs P inside the kernels (ce_lds_newton_wave_qp.h).  ce_jvp_qp's / ce_refine_qp's arguments and the whole of their body with the wave kernel in the place
+// of k_backward_ns<..., QP>; refused, before anything is enqueued, where the handle is not served.  No host synchronisation.
+int ce_newton_wave_qp_variant(ce_handle h) { return h ? h->newton_wave_qp_variant : -1; }
+int ce_newton_wave_qp_lds(ce_handle h) { return (h && h->newton_wave_qp_variant >= 0) ? (int)h->newton_wave_qp_lds : 0; }
+int ce_newton_wave_qp_occupancy(ce_handle h, int refine) {
+    if (!h || h->newton_wave_qp_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_newton_wave_qp(h->newton_wave_qp_variant, refine, h->newton_wave_qp_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+int ce_jvp_qp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                   const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream) {
+    if (!h) { g_err = "ce_jvp_qp_wave: null argument"; return CE_E_BADARG; }
+    if (h->newton_wave_qp_variant < 0) return newton_wave_qp_refuse(h, "ce_jvp_qp_wave", "ce_jvp_qp", "ce_jvp");
+    if (B <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dy || !jvp_status) { g_err = "ce_jvp_qp_wave: null argument"; return CE_E_BADARG; }
+    return jvp_ns(h, B, A_vals_bm, sA_b, nullptr, 0, 0, P_vals, x, y, s, tA_vals_bm, stA_b, tq_vals, stq_k, stq_b, tP_vals, dx, dy, ds, jvp_status, lsqr_iters, 0.0, 0.0, 0.0, 0, stream, false, false, true);
 }
 // K tangents at one solution (include/cone_engine.h).  One launch of k_backward_ns<..., FWD, ..., MANY> factors every instance once and writes all K answers; plain kind:
 // the instances it lists as rank deficient are listed ONCE, and ONE launch of the LSQR kernel walks the K x list (tangent, instance) pairs (SaWalkMany; the list parity
@@ -1885,11 +1919,14 @@ int ce_vjp_qp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, lo
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record
 // (refine_status, steps_taken, resid) carries an instance's state from launch to launch on the device.  No re-solve list: a flagged instance keeps its point.
 static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
-                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (wave: ce_refine_wave -- k_newton_wave<..., REF> in the place of k_backward_ns)
+                     const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream, bool psd = false, bool psd_tri = false, bool wave = false) {          // (wave: ce_refine_wave -- k_newton_wave<..., REF> in the place of k_backward_ns; with P_vals: ce_refine_qp_wave -- k_newton_wave_qp<..., REF>)
     const bool qp = P_vals != nullptr;
-    const std::string who = wave ? "ce_refine_wave" : qp ? "ce_refine_qp" : (psd_tri ? "ce_refine_psd_tri" : (psd ? "ce_refine_psd" : "ce_refine"));
+    const std::string who = wave ? (qp ? "ce_refine_qp_wave" : "ce_refine_wave") : qp ? "ce_refine_qp" : (psd_tri ? "ce_refine_psd_tri" : (psd ? "ce_refine_psd" : "ce_refine"));
     const CePlan &P = h->plan;
     const DevT &T = h->T;
+    if (wave && qp) {          // (refused before anything is enqueued, nothing written)
+        if (h->newton_wave_qp_variant < 0) return newton_wave_qp_refuse(h, who, "ce_refine_qp", "ce_refine");
+    } else
     if (wave) {          // (refused before anything is enqueued, nothing written)
         if (h->newton_wave_variant < 0) { g_err = who + ": " + newton_wave_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p) + "; use ce_refine"; return CE_E_UNSUPPORTED; }
     } else
@@ -1913,7 +1950,8 @@ static int refine_ns(ce_handle h, int B, const double *A_vals_bm, long sA_b, con
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm;
     for (int k = 0; k < steps; k++) {
         const NsRefine W{h->d_bpos.get(), q_vals, sq_k, sq_b, x, y, s, status, refine_status, steps_taken, resid, k == 0 ? 1 : 0};
-        const int lrc = wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
+        const int lrc = (wave && qp) ? ce_launch_newton_wave_qp(h->newton_wave_qp_variant, B, h->newton_wave_qp_lds, st, ba, W, NwQp{P_vals, nullptr, h->d_prow.get(), h->d_pcol.get(), h->nnz_p, h->p_tri ? 1 : 0})
+                      : wave ? ce_launch_newton_wave(h->newton_wave_variant, B, h->newton_wave_lds, st, ba, W)
                       : qp ? ce_launch_ns(variant, B, lds, st, ba, NsRefineQp{W, NsQp{P_vals, nullptr, h->d_pmap.get(), h->nnz_p}})
                       : psd_tri ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsdTri{W})
                       : psd ? ce_launch_ns(variant, B, lds, st, ba, NsRefinePsd{W})
@@ -1947,6 +1985,13 @@ int ce_refine_qp(ce_handle h, int B, const double *A_vals_bm, long sA_b, const d
                  const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
     if (!h || B <= 0 || !A_vals_bm || !q_vals || !P_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_qp: null argument or negative step count"; return CE_E_BADARG; }
     return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, P_vals, x, y, s, status, steps, refine_status, steps_taken, resid, stream);
+}
+int ce_refine_qp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
+                      const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream) {
+    if (!h) { g_err = "ce_refine_qp_wave: null argument or negative step count"; return CE_E_BADARG; }
+    if (h->newton_wave_qp_variant < 0) return newton_wave_qp_refuse(h, "ce_refine_qp_wave", "ce_refine_qp", "ce_refine");
+    if (B <= 0 || !A_vals_bm || !q_vals || !P_vals || !x || !y || !s || !refine_status || !steps_taken || !resid || steps < 0) { g_err = "ce_refine_qp_wave: null argument or negative step count"; return CE_E_BADARG; }
+    return refine_ns(h, B, A_vals_bm, sA_b, q_vals, sq_k, sq_b, P_vals, x, y, s, status, steps, refine_status, steps_taken, resid, stream, false, false, true);
 }
 int ce_ca_triples(ce_handle h, int B, int lp, double *U, double *roots, const int *active, void *stream) {
     if (!h || B <= 0 || !U || !roots || !active) { g_err = "null argument"; return CE_E_BADARG; }

@@ -46,7 +46,7 @@ class ConeEngine:
         self.last_acceleration = False        # Anderson acceleration ran
         self.last_const_a_kernel = None       # "k_sa_fwd" / "batch GEMM"
         self.last_lsqr_iters = None           # (B,) int32 iteration counts of the last one-kernel LSQR adjoint / forward derivative
-        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_psd" / "ce_jvp_lsqr" / "ce_jvp_shared_a" / "ce_jvp_wave"; after jvp_many's one call its entry ("ce_jvp_many", "ce_jvp_many_wave", ...)
+        self.last_jvp_kernel = None           # "ce_jvp" / "ce_jvp_qp" / "ce_jvp_psd" / "ce_jvp_lsqr" / "ce_jvp_shared_a" / "ce_jvp_wave" / "ce_jvp_qp_wave"; after jvp_many's one call its entry ("ce_jvp_many", "ce_jvp_many_wave", ...)
         self.dispatch_history = False         # (the library's default; set_dispatch_history)
         self._last_solution = None            # (x, y, s) of the last forward of the layer: warm_start=True
         self._last_q, self._last_q_key = None, None          # objective of the last solve() and the value buffer it belongs to (_recent_q)
@@ -151,6 +151,12 @@ class ConeEngine:
         csrc/ce_variants_newton_wave.h that serves it (-1: not served -- bwd_wave_plan()'s class) and the launch's LDS bytes (0 when not served)."""
         L = _lib.lib()
         return int(L.ce_newton_wave_variant(self._h)), int(L.ce_newton_wave_lds(self._h))
+
+    def newton_wave_qp_plan(self):
+        """(variant, lds) of the one-instance-per-wave forward derivative / refinement kernel of a quadratic objective, k_newton_wave_qp, on this template: the
+        row of csrc/ce_variants_newton_wave_qp.h that serves it (-1: not served -- bwd_wave_qp_plan()'s class) and the launch's LDS bytes (0 when not served)."""
+        L = _lib.lib()
+        return int(L.ce_newton_wave_qp_variant(self._h)), int(L.ce_newton_wave_qp_lds(self._h))
 
     def bwd_wave_qp_plan(self):
         """(variant, lds) of the one-instance-per-wave adjoint kernel of a quadratic objective, k_bwd_wave_qp, on this template: the row of
@@ -670,7 +676,8 @@ class ConeEngine:
         ce_jvp refuses; the same fall to the LSQR call where the library has none for the template.  Without it a PSD template runs the LSQR call, as ever.
         On a template with PSD blocks AND triples (psd_tri_ns_variant >= 0) the flag calls ce_jvp_psd_tri, the elimination with both kinds.
         wave=True (with method="direct", per-instance path): ce_jvp_wave in the place of ce_jvp -- k_newton_wave, one instance per wave (newton_wave_plan()[0] >= 0);
-        an engine or a call it does not serve raises, nothing falls back."""
+        with P_bm, ce_jvp_qp_wave in the place of ce_jvp_qp -- k_newton_wave_qp (newton_wave_qp_plan()[0] >= 0).  An engine or a call it does not serve raises,
+        nothing falls back."""
         if method not in ("lsqr", "direct"):
             raise ValueError(f"ConeEngine.jvp: method must be 'lsqr' or 'direct', got {method!r}")
         B = A_bm.shape[0]
@@ -684,7 +691,9 @@ class ConeEngine:
             if method != "direct":
                 raise NotImplementedError("ConeEngine.jvp: a quadratic objective inside the kernels has no LSQR forward derivative; use method='direct' "
                                           "(or the epigraph form, CE_QP_EPIGRAPH=1)")
-            return self._jvp_qp(A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm)
+            if wave and (path != "per_instance" or psd_ns):
+                raise NotImplementedError("ConeEngine.jvp: wave=True is the direct forward derivative on the per-instance path (ce_jvp_qp_wave)")
+            return self._jvp_qp(A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm, wave=wave)
         atol, btol, lim, system, _ = unpack_rule(lsqr, self.n, self.m)
         if q_eval is None and system != "reduced":
             q_eval = self._recent_q(A_bm)
@@ -830,20 +839,21 @@ class ConeEngine:
         tangents = (tA_c.data_ptr() if tA_c is not None else None, self.nnz_aug, *tq_args)
         return point, tangents, outs, (xc, yc, sc_, tA_c, tqd)
 
-    def _jvp_qp(self, A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm):
-        """ce_jvp_qp (include/cone_engine.h): one launch of the search-free elimination with P inside"""
+    def _jvp_qp(self, A_bm, P_bm, x, y, s, tA_bm, tq, tP_bm, wave: bool = False):
+        """ce_jvp_qp (include/cone_engine.h): one launch of the search-free elimination with P inside; wave: ce_jvp_qp_wave, k_newton_wave_qp in its place"""
+        entry = "ce_jvp_qp_wave" if wave else "ce_jvp_qp"
         B = A_bm.shape[0]
         f64 = dict(dtype=torch.float64, device=self.device)
         A_c, P_c = (t.detach().to(**f64).contiguous() for t in (A_bm, P_bm))
         tP_c = tP_bm.detach().to(**f64).contiguous() if tP_bm is not None else None
         point, tangents, outs, keep = self._jvp_buffers(B, x, y, s, tA_bm, tq)
         dx, dy, ds, st, its = outs
-        rc = _lib.lib().ce_jvp_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), *point, *tangents, tP_c.data_ptr() if tP_c is not None else None,
-                                  *(t.data_ptr() for t in outs), self._stream())
+        rc = getattr(_lib.lib(), entry)(self._h, B, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), *point, *tangents, tP_c.data_ptr() if tP_c is not None else None,
+                                        *(t.data_ptr() for t in outs), self._stream())
         if rc == -2:
             raise NotImplementedError(_lib.lib().ce_last_error().decode())
-        _lib.check(rc, "ce_jvp_qp")
-        self.last_jvp_kernel = "ce_jvp_qp"
+        _lib.check(rc, entry)
+        self.last_jvp_kernel = entry
         self.last_lsqr_iters = its
         return dx, dy, ds, st
 
@@ -856,7 +866,8 @@ class ConeEngine:
         P_bm (B, nnz_p): the quadratic objective of a qp_native engine (ce_refine_qp: F_x = P x + A^T y^ + c).
         psd_ns=True: ce_refine_psd in the place of ce_refine -- the elimination with PSD blocks, which ce_refine refuses (path "none" without the flag).
         wave=True: ce_refine_wave in the place of ce_refine -- k_newton_wave, one instance per wave (newton_wave_plan()[0] >= 0); info gains "kernel":
-        "k_newton_wave"; an engine it does not serve raises."""
+        "k_newton_wave"; with P_bm, ce_refine_qp_wave in the place of ce_refine_qp -- k_newton_wave_qp (newton_wave_qp_plan()[0] >= 0), "kernel":
+        "k_newton_wave_qp".  An engine it does not serve raises."""
         B = A_bm.shape[0]
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -871,13 +882,17 @@ class ConeEngine:
         resid = torch.empty((B, 2), **f64)
         tail = (x.data_ptr(), y.data_ptr(), s.data_ptr(), st_c.data_ptr() if st_c is not None else None, int(steps), rst.data_ptr(), taken.data_ptr(), resid.data_ptr(), self._stream())
         if wave:
-            if P_bm is not None or psd_ns:
-                raise NotImplementedError("ConeEngine.refine: wave=True serves a linear objective and zero / nonnegative / second-order cones (ce_refine_wave)")
-            rc = _lib.lib().ce_refine_wave(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail)
+            if psd_ns:
+                raise NotImplementedError("ConeEngine.refine: wave=True serves zero / nonnegative / second-order cones (ce_refine_wave, ce_refine_qp_wave)")
+            if P_bm is not None:
+                P_c = P_bm.detach().to(**f64).contiguous()
+                rc, name, kernel = _lib.lib().ce_refine_qp_wave(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp_wave", "k_newton_wave_qp"
+            else:
+                rc, name, kernel = _lib.lib().ce_refine_wave(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, *tail), "ce_refine_wave", "k_newton_wave"
             if rc in (-2, -3):
                 raise NotImplementedError(_lib.lib().ce_last_error().decode())
-            _lib.check(rc, "ce_refine_wave")
-            return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns", "kernel": "k_newton_wave"}
+            _lib.check(rc, name)
+            return x, y, s, {"status": rst, "steps": taken, "resid_before": resid[:, 0], "resid_after": resid[:, 1], "path": "ns", "kernel": kernel}
         if P_bm is not None:
             P_c = P_bm.detach().to(**f64).contiguous()
             rc, name = _lib.lib().ce_refine_qp(self._h, B, A_c.data_ptr(), self.nnz_aug, *q_args, P_c.data_ptr(), *tail), "ce_refine_qp"

@@ -160,6 +160,7 @@ class _Saved(NamedTuple):
     psd_tangents: bool = False              # psd_many_active(psd_tangents()) of this call: tangent_many of a node with PSD blocks runs ce_jvp_psd_many (one-tangent forward-mode AD ignores it)
     nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave, tangent_many ce_jvp_many_wave (every other route ignores it)
     adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
+    nw_wave_qp: bool = False                # newton_kernel() == "wave" on a served node with P_bm: forward-mode AD with jvp_mode="direct" runs ce_jvp_qp_wave (every other route ignores it: nw_wave stays False on such a node, tangent_many / jacobian keep ce_jvp_qp_many)
     adj_wave_qp: bool = False               # adjoint_kernel() == "wave" on a served node with P_bm: backward() runs k_bwd_wave_qp (every other route ignores it: adj_wave stays False on such a node)
 
 
@@ -232,17 +233,21 @@ class _ConeLayer(torch.autograd.Function):
                                                       "per-instance A, and not the remainder solve of newton_first; the ordinary kernel ran "
                                                       "(info['forward']['kernel'] == 'workgroup')")
             # solver_args newton_kernel="wave": the Newton steps of refine_steps / newton_first and the direct forward derivative run k_newton_wave where it serves
-            # the node -- a per-instance A, a linear objective, the search-free elimination enabled, a served template; said once elsewhere
-            nw_wave = False
+            # the node -- a per-instance A, a linear objective, the search-free elimination enabled, a served template; said once elsewhere.
+            # A node with P_bm: the same steps and the direct forward derivative run k_newton_wave_qp on a template newton_wave_qp_plan serves.
+            nw_wave = nw_wave_qp = False
             if nw_kernel == "wave":
-                nw_wave = (P_bm is None and os.environ.get("CE_BWD_NS") != "0" and eng.newton_wave_plan()[0] >= 0 and not eng._use_const_a(A_bm))
-                if not nw_wave:
-                    _warn_once("newton_kernel_none", "MI355 solver: solver_args newton_kernel='wave' is ignored on this template or path: the wave Newton kernel serves a "
-                                                     "linear objective, zero / nonnegative / second-order cones, n <= 32, m <= 64 and a per-instance A (CE_BWD_NS not 0); "
-                                                     "the ordinary kernels run")
+                if P_bm is not None:
+                    nw_wave_qp = os.environ.get("CE_BWD_NS") != "0" and eng.newton_wave_qp_plan()[0] >= 0
+                else:
+                    nw_wave = (os.environ.get("CE_BWD_NS") != "0" and eng.newton_wave_plan()[0] >= 0 and not eng._use_const_a(A_bm))
+                if not (nw_wave or nw_wave_qp):
+                    _warn_once("newton_kernel_none", "MI355 solver: solver_args newton_kernel='wave' is ignored on this template or path: the wave Newton kernels serve a "
+                                                     "linear objective or a quadratic one inside the kernels, zero / nonnegative / second-order cones, n <= 32, m <= 64 "
+                                                     "and a per-instance A (CE_BWD_NS not 0); the ordinary kernels run")
             nf_info = None
             if n_newton > 0 and warm is not None and batch_size > 0:
-                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if nw_wave else {}))
+                (x, y, s, iters, status, resid), nf_info = newton_first_solve(eng, A_bm, q_dev, settings, warm, n_newton, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if (nw_wave or nw_wave_qp) else {}))
                 if nf_info["path"] == "none":
                     _warn_once("newton_first_none", "MI355 solver: solver_args newton_first needs the search-free elimination, which this template or path does not have "
                                                     "(PSD cones, n > 108, a shared A); the ordinary warm-started solve ran (info['newton_first']['path'] == 'none')")
@@ -257,7 +262,7 @@ class _ConeLayer(torch.autograd.Function):
             if n_refine > 0:
                 refine_info = {"status": None, "steps": None, "resid_before": None, "resid_after": None, "path": "none"}
                 if eng.last_path == "per_instance" and status.numel():
-                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if nw_wave else {}))
+                    x, y, s, refine_info = eng.refine(A_bm, q_dev, x, y, s, n_refine, status=status, P_bm=P_bm, psd_ns=psd_ns, **({"wave": True} if (nw_wave or nw_wave_qp) else {}))
                 if refine_info["path"] == "none" and status.numel():
                     _warn_once("refine_none", "MI355 solver: solver_args refine_steps needs the search-free elimination, which this template or path does not have (PSD "
                                               "cones, n > 108, a shared A); the solver's point is returned "
@@ -306,7 +311,7 @@ class _ConeLayer(torch.autograd.Function):
             if lpgd is not None:
                 info["adjoint"].update(path=lpgd[0], tau=lpgd[1], rho=lpgd[2], lpgd_iters=None)
             saved = _Saved(eng, A_bm, x.detach(), y.detach(), s, batch_minor_in, P_bm, path, None, lsqr, q_dev if (P_bm is None or lpgd is not None) else None, fwd_mode,
-                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, nw_wave and path == "per_instance", adj_wave, adj_wave_qp) if needs_grad else None
+                           _lib.CeSettings.from_buffer_copy(settings) if lpgd is not None else None, lpgd, eng.last_path, qp_adj, tri_adj, tri_tan, psd_ns, psd_adj, psd_tan, nw_wave and path == "per_instance", adj_wave, nw_wave_qp and path == "per_instance", adj_wave_qp) if needs_grad else None
             if status.numel() and not raise_on:
                 # raise_on_error=False: the caller has waived the reference's "raise from forward()" contract, so NOTHING forces a host round trip here.  Failed
                 # instances are masked ON THE DEVICE (two small elementwise launches, unconditionally), the outcome summary lands in pinned memory behind the
@@ -381,7 +386,8 @@ class _ConeLayer(torch.autograd.Function):
                 tP_bm = None
                 if tP is not None:
                     tP_bm = (tP.unsqueeze(1) if originally_unbatched else tP).detach().to(device=eng.device, dtype=torch.float64).t().contiguous()
-                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, method="direct", P_bm=saved.P_bm, tP_bm=tP_bm)
+                nw_qp = saved.nw_wave_qp and saved.jvp_mode == "direct" and path == "per_instance"
+                dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, method="direct", P_bm=saved.P_bm, tP_bm=tP_bm, **({"wave": True, "path": path} if nw_qp else {}))
             else:
                 nw = saved.nw_wave and saved.jvp_mode == "direct" and path == "per_instance" and saved.q_eval is not None and unpack_rule(saved.lsqr, eng.n, eng.m)[3] != "reduced"
                 dx, dy, _, st = eng.jvp(saved.A_bm, x, y, s, tA_bm, tq_dev, path=path, lsqr=saved.lsqr, q_eval=saved.q_eval, method=saved.jvp_mode, psd_ns=saved.psd_ns,
@@ -390,7 +396,7 @@ class _ConeLayer(torch.autograd.Function):
                 nanv = float("nan")
                 dx = torch.where(failed[:, None], nanv, dx); dy = torch.where(failed[:, None], nanv, dy)
         if isinstance(ctx.info, dict):
-            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd", "ce_jvp_psd_tri", "ce_jvp_wave") else "lsqr"}
+            ctx.info["jvp"] = {"status": st, "iters": eng.last_lsqr_iters, "kernel": eng.last_jvp_kernel, "path": "direct" if eng.last_jvp_kernel in ("ce_jvp", "ce_jvp_qp", "ce_jvp_psd", "ce_jvp_psd_tri", "ce_jvp_wave", "ce_jvp_qp_wave") else "lsqr"}
         return dx.to(in_device), dy.to(in_device), None, None
 
     @staticmethod

@@ -38,7 +38,7 @@ def _read_int(eng: ConeEngine, dev_int: torch.Tensor) -> int:
 
 def newton_first_solve(eng: ConeEngine, A_bm, q_eval, settings, warm, steps: int, P_bm=None, psd_ns: bool = False, wave: bool = False):
     """The forward solve of a warm-started call with newton_first = steps > 0.  A_bm (B, nnz_aug) contiguous, q_eval (n+1, B), warm = (x, y, s), P_bm (B, nnz_p)
-    or None, settings the call's ce_settings, psd_ns: the steps run ce_refine_psd (a template with PSD blocks under solver_args psd_elimination), wave: they run ce_refine_wave (solver_args newton_kernel='wave' on a served template).  Returns (x, y, s, iters, status, resid), info -- what ConeEngine.solve returns for the whole batch, and
+    or None, settings the call's ce_settings, psd_ns: the steps run ce_refine_psd (a template with PSD blocks under solver_args psd_elimination), wave: they run ce_refine_wave -- with P_bm ce_refine_qp_wave -- (solver_args newton_kernel='wave' on a served template).  Returns (x, y, s, iters, status, resid), info -- what ConeEngine.solve returns for the whole batch, and
     info["newton_first"].  Where the feature is not served (a shared A, no elimination for the template) the ordinary warm-started solve runs and info's path is
     "none".  Leaves on the engine what a full-batch per-instance solve() leaves (last_path, last_acceleration, the remembered objective)."""
     B = A_bm.shape[0]

@@ -276,8 +276,12 @@ def newton_kernel(merged_args: dict) -> str:
     "wave" -> k_newton_wave (ce_jvp_wave, ce_refine_wave): one instance per wave, for small templates -- adjoint_kernel="wave"'s class
     (ConeEngine.newton_wave_plan()[0] >= 0).  The same system, rules, flags, safeguard and LSQR re-solve of flagged tangents; results agree to rounding, not bit for
     bit.  info["refine"]["kernel"] and info["newton_first"]["refine"]["kernel"] are "k_newton_wave", info["jvp"]["kernel"] is "ce_jvp_wave" where it runs.
-    Independent of forward_kernel and adjoint_kernel.  Every other template or path -- a quadratic objective, a PSD / exponential / power cone, a larger
-    template, a shared A, CE_BWD_NS=0 -- ignores the key with one notice and runs what it ran; jvp_mode="lsqr" and tangent_many do not read it."""
+    On a node whose quadratic objective runs inside the kernels, k_newton_wave_qp (ce_jvp_qp_wave, ce_refine_qp_wave; ConeEngine.newton_wave_qp_plan()[0] >= 0)
+    in the place of k_backward_ns<..., FWD[, REF], QP> (ce_jvp_qp, ce_refine_qp): the same elimination with P inside, status 0 or 4, no LSQR behind it;
+    info["refine"]["kernel"] and info["newton_first"]["refine"]["kernel"] are "k_newton_wave_qp", info["jvp"]["kernel"] is "ce_jvp_qp_wave" there
+    (tangent_many / jacobian of such a node keep ce_jvp_qp_many).
+    Independent of forward_kernel and adjoint_kernel.  Every other template or path -- a quadratic objective outside the kernels, a PSD / exponential / power
+    cone, a larger template, a shared A, CE_BWD_NS=0 -- ignores the key with one notice and runs what it ran; jvp_mode="lsqr" does not read it."""
     mode = merged_args.get("newton_kernel", "workgroup")
     if not isinstance(mode, str) or mode not in ("workgroup", "wave"):
         raise ValueError(f"MI355 solver: newton_kernel must be 'workgroup' or 'wave', got {mode!r}")

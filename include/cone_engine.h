@@ -92,7 +92,7 @@ void ce_default_settings(ce_settings *s);
  * library short structs.  Bindings must check  ce_abi_version() == CE_ABI_VERSION  and  ce_struct_size(which) == sizeof(their
  * struct)  (which: 0 ce_template, 1 ce_settings) once at load time and refuse to continue otherwise (cvxpylayers_amd/_lib.py
  * does; tests/test_cabi.py checks the stub printed in INTEGRATION.md the same way).  CE_ABI_VERSION is bumped whenever a struct
- * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params, and ce_solve_wave, ce_wave_variant, ce_wave_lds and ce_wave_occupancy, and ce_vjp_many_wave, ce_vjp_many_params_wave, ce_bwd_wave_many_variant, ce_bwd_wave_many_lds, ce_bwd_wave_many_chunk and ce_bwd_wave_many_occupancy, and ce_jvp_many_wave, ce_jvp_wave_many_variant, ce_jvp_wave_many_lds, ce_jvp_wave_many_chunk and ce_jvp_wave_many_occupancy, and ce_solve_qp_wave, ce_wave_qp_variant, ce_wave_qp_lds and ce_wave_qp_occupancy, and ce_vjp_qp_wave, ce_bwd_wave_qp_variant, ce_bwd_wave_qp_lds and ce_bwd_wave_qp_occupancy; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
+ * layout, an entry point's signature or the meaning of an argument changes (additions that leave every existing call as it was keep the number: ce_tri_ns_variant and entry 17 of ce_get_plan, then ce_value / ce_value_jvp / ce_value_vjp, then ce_cones_create / ce_cones_destroy / ce_cones_rows / ce_cones_state_len / ce_cone_project / ce_cone_dproject, came under 17, as did ce_lpgd_perturb, ce_lpgd_grad and ce_set_transient_solve, and ce_vjp_many and ce_vjp_many_variant, and ce_jvp_many, ce_jvp_qp_many, ce_jvp_many_variant and ce_jvp_qp_many_variant, and ce_vjp_qp_many and ce_vjp_qp_many_variant, and ce_vjp_tri_many and ce_vjp_tri_many_variant, and ce_jvp_tri_many and ce_jvp_tri_many_variant, and ce_jvp_psd, ce_refine_psd, ce_psd_ns_variant and ce_psd_ns_lds, and ce_vjp_psd_many, ce_jvp_psd_many, ce_vjp_psd_many_variant and ce_jvp_psd_many_variant, and ce_jvp_psd_tri, ce_refine_psd_tri, ce_vjp_psd_tri_many, ce_jvp_psd_tri_many, ce_psd_tri_ns_variant, ce_psd_tri_ns_lds, ce_vjp_psd_tri_many_variant and ce_jvp_psd_tri_many_variant, and ce_vjp_many_params, ce_vjp_params, ce_param_grad_variant and ce_param_grad_records, and ce_vjp_qp_many_params, ce_vjp_tri_many_params, ce_vjp_psd_many_params and ce_vjp_psd_tri_many_params, and ce_solve_wave, ce_wave_variant, ce_wave_lds and ce_wave_occupancy, and ce_vjp_many_wave, ce_vjp_many_params_wave, ce_bwd_wave_many_variant, ce_bwd_wave_many_lds, ce_bwd_wave_many_chunk and ce_bwd_wave_many_occupancy, and ce_jvp_many_wave, ce_jvp_wave_many_variant, ce_jvp_wave_many_lds, ce_jvp_wave_many_chunk and ce_jvp_wave_many_occupancy, and ce_solve_qp_wave, ce_wave_qp_variant, ce_wave_qp_lds and ce_wave_qp_occupancy, and ce_vjp_qp_wave, ce_bwd_wave_qp_variant, ce_bwd_wave_qp_lds and ce_bwd_wave_qp_occupancy, and ce_jvp_qp_wave, ce_refine_qp_wave, ce_newton_wave_qp_variant, ce_newton_wave_qp_lds and ce_newton_wave_qp_occupancy; 16: ce_get_plan appends last_sa_fwd, last_sa_lsqr; 15: ce_refine added; 14: ce_jvp added; 13: ce_jvp_lsqr / ce_jvp_shared_a added; 12: ce_get_plan added; 11: ce_vjp re-solves rank-deficient instances by LSQR when q_vals is given, adj_status is a bit field, ce_set_adjoint_resolve added; 10: ce_vjp_lsqr added; 9: ce_vjp_shared_a takes sA_b and q_vals -- the adjoint system gains diffcp's tau row and column --, its iter_lim default is diffcp's 2 (n + m + 1); 8: ce_set_dispatch_history added, ce_status_summary writes a fourth "ready" int; 7: ce_status_summary added; 6: ce_default_settings = SCS defaults incl. acceleration_lookback 10, ce_acceleration_available). */
 #define CE_ABI_VERSION 17
 int ce_abi_version(void);
 int ce_struct_size(int which);
@@ -721,6 +721,32 @@ int ce_refine_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const
 int ce_newton_wave_variant(ce_handle h);
 int ce_newton_wave_lds(ce_handle h);
 int ce_newton_wave_occupancy(ce_handle h, int refine);
+/*
+ * ce_jvp_qp and ce_refine_qp, ONE INSTANCE PER WAVE, for small quadratic programs (k_newton_wave_qp, csrc/ce_newton_wave_qp.h; additions under ABI 17).
+ * ce_jvp_wave's / ce_refine_wave's kernel with P inside the way ce_vjp_qp_wave adds it: a third dense matrix in the wave's LDS goes through the null-space
+ * transform on both sides, Z^T P Z and -(Z^T P x_p) start the reduced Hessian and its right-hand side, (P d_x)[piv] joins the multipliers' right-hand side;
+ * g_x = tq - tA^T y + tP x (refinement: F_x = P x + A^T y^ + c).  Same system, rules, flags, status bits and safeguard as ce_jvp_qp / ce_refine_qp; the results
+ * agree to rounding, not bit for bit, and an instance's result does not depend on its position.  No host synchronisation.
+ *   served                     : ce_vjp_qp_wave's class -- ce_qp_native(h) == 1, zero / nonnegative / second-order cones of any dimensions, n <= 32, m <= 64.
+ *   ce_jvp_qp_wave             : ce_jvp_qp's arguments and outputs (each of tA_vals_bm, tq_vals, tP_vals may be NULL: zero).  jvp_status: 0, or 4 (more active rows
+ *                                than variables: zero outputs; a dropped equality row or variable: the dropped-variable answer, finite); bit 8 is never set and
+ *                                lsqr_iters is 0 -- no LSQR has a P term.
+ *   ce_refine_qp_wave          : ce_refine_qp's arguments, record and contract; `steps` launches, one complete safeguarded step each.
+ *                                Both return CE_E_UNSUPPORTED, before anything is enqueued and with nothing written, on a handle that is not served (a linear
+ *                                objective is named as such); ce_last_error names the entry and the reason.
+ *   ce_newton_wave_qp_variant  : the row of the kernel's instantiation list (csrc/ce_variants_newton_wave_qp.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_newton_wave_qp_lds      : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_newton_wave_qp_occupancy: resident workgroups (= instances) per CU of that row at that footprint (refine != 0: of the refinement step's instantiation), as
+ *                                the runtime's occupancy query reports it (0 when not served).
+ */
+int ce_jvp_qp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                   const double *tA_vals_bm, long stA_b, const double *tq_vals, long stq_k, long stq_b, const double *tP_vals,
+                   double *dx, double *dy, double *ds, int *jvp_status, int *lsqr_iters, void *stream);
+int ce_refine_qp_wave(ce_handle h, int B, const double *A_vals_bm, long sA_b, const double *q_vals, long sq_k, long sq_b, const double *P_vals, double *x, double *y, double *s,
+                      const int *status, int steps, int *refine_status, int *steps_taken, double *resid, void *stream);
+int ce_newton_wave_qp_variant(ce_handle h);
+int ce_newton_wave_qp_lds(ce_handle h);
+int ce_newton_wave_qp_occupancy(ce_handle h, int refine);
 /*
  * K tangents at one solution of a small template, ONE WAVE PER (INSTANCE, CHUNK OF TANGENTS) (k_jvp_wave_many, csrc/ce_jvp_wave_many.h; additions under ABI 17).
  * ce_jvp_wave's elimination keeps one right-hand side in the lane behind the n columns; here the lanes n .. n + KC - 1 carry KC tangents through the same row
