@@ -26,7 +26,8 @@ SYMBOLS = ["ce_abi_version", "ce_struct_size", "ce_acceleration_available", "ce_
            "ce_jvp_many_wave", "ce_jvp_wave_many_variant", "ce_jvp_wave_many_lds", "ce_jvp_wave_many_chunk", "ce_jvp_wave_many_occupancy",
            "ce_solve_qp_wave", "ce_wave_qp_variant", "ce_wave_qp_lds", "ce_wave_qp_occupancy",
            "ce_vjp_qp_wave", "ce_bwd_wave_qp_variant", "ce_bwd_wave_qp_lds", "ce_bwd_wave_qp_occupancy",
-           "ce_jvp_qp_wave", "ce_refine_qp_wave", "ce_newton_wave_qp_variant", "ce_newton_wave_qp_lds", "ce_newton_wave_qp_occupancy"]
+           "ce_jvp_qp_wave", "ce_refine_qp_wave", "ce_newton_wave_qp_variant", "ce_newton_wave_qp_lds", "ce_newton_wave_qp_occupancy",
+           "ce_vjp_qp_many_wave", "ce_vjp_qp_many_params_wave", "ce_bwd_wave_many_qp_variant", "ce_bwd_wave_many_qp_lds", "ce_bwd_wave_many_qp_chunk", "ce_bwd_wave_many_qp_occupancy"]
 
 
 class CeTemplate(C.Structure):
@@ -133,6 +134,9 @@ def lib():
     L.ce_jvp_qp_many_variant.argtypes = [vp]
     L.ce_vjp_qp_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, vp]
     L.ce_vjp_qp_many_variant.argtypes = [vp]
+    L.ce_vjp_qp_many_wave.argtypes = L.ce_vjp_qp_many.argtypes
+    L.ce_vjp_qp_many_params_wave.argtypes = L.ce_vjp_qp_many_params.argtypes
+    L.ce_bwd_wave_many_qp_variant.argtypes = [vp]; L.ce_bwd_wave_many_qp_lds.argtypes = [vp]; L.ce_bwd_wave_many_qp_chunk.argtypes = [vp]; L.ce_bwd_wave_many_qp_occupancy.argtypes = [vp]
     L.ce_vjp_tri_many.argtypes = [vp, C.c_int, C.c_int, dp, lg, dp, lg, lg, dp, dp, dp, dp, dp, dp, dp, ip, vp]
     L.ce_vjp_tri_many_variant.argtypes = [vp]
     L.ce_vjp_psd_many.argtypes = L.ce_vjp_many.argtypes

@@ -65,6 +65,16 @@ struct BwdWaveMany {
     long sxk, syk, sAk, sqk, sak;
     double *rec; long rpitch, srk;
 };
+// k_bwd_wave_many_qp (ce_backward_wave_many_qp.h; cone_engine.hip ce_vjp_qp_many_wave, ce_vjp_qp_many_params_wave): the same for a template with a quadratic
+// objective inside the kernels.  BwdWaveMany's strides and record fields, then what NsVjpQpMany carries of P: the instances' rows, entry k of the structure at
+// (prow[k], pcol[k]) (p_tri: one triangle is stored and an off-diagonal entry stands for both), dP [K][B][nnz_p] with cotangent k sPk elements further
+struct BwdWaveManyQp {
+    int K;
+    long sxk, syk, sAk, sqk, sak;
+    double *rec; long rpitch, srk;
+    const double *P; const int *prow, *pcol; int nnz_p, p_tri;
+    double *dP; long sPk;
+};
 // k_backward_ns<..., FWD = true, ..., MANY = true> (plain cones, P or not): K tangents on one factorisation of the instance (cone_engine.hip ce_jvp_many /
 // ce_jvp_qp_many).  Tangent k of instance i: its value row at tA + k * stAk + i * stAb, its q_eval row (n + 1 contiguous entries) at tq + k * stqk + i * stqb; a batch
 // stride of 0 is one row shared by every instance.  Outputs of tangent k lie sxk (dx) / syk (dy, ds) / sak (status -- CeBwdArgs' adj -- and iters) elements further
@@ -307,6 +317,10 @@ hipError_t ce_occupancy_bwd_wave_qp(int variant, size_t lds, int *blocks);
 // is B x ceil(w.K / KC) workgroups of 64 threads
 int ce_launch_bwd_wave_many(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const BwdWaveMany &w);
 hipError_t ce_occupancy_bwd_wave_many(int variant, size_t lds, int *blocks);
+// ce_tu_bwd_wave_many_qp.hip: k_bwd_wave_many_qp, K cotangents of one QP instance per wave and chunk (row of CE_BWD_WAVE_MANY_QP_VARIANTS,
+// ce_variants_bwd_wave_many_qp.h): the grid is B x ceil(w.K / KC) workgroups of 64 threads
+int ce_launch_bwd_wave_many_qp(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const BwdWaveManyQp &w);
+hipError_t ce_occupancy_bwd_wave_many_qp(int variant, size_t lds, int *blocks);
 // ce_tu_newton_wave.hip: k_newton_wave, the forward derivative (NsJvp) and one Newton refinement step (NsRefine: a.T and a.Abm alone are read) of one instance per
 // wave (row of CE_NEWTON_WAVE_VARIANTS, ce_variants_newton_wave.h): the grid is B workgroups of 64 threads
 int ce_launch_newton_wave(int variant, int B, size_t lds, hipStream_t st, const CeBwdArgs &a, const NsJvp &w);

@@ -43,6 +43,7 @@
 #include "ce_lds_newton_wave_qp.h"   // k_newton_wave_qp (ce_jvp_qp_wave, ce_refine_qp_wave): the same for the one-wave forward derivative and refinement step of a quadratic objective
 #include "ce_lds_jvp_wave_many.h"   // k_jvp_wave_many (ce_jvp_many_wave): the same for the many-tangent twin of the forward derivative
 #include "ce_lds_bwd_wave_many.h"   // k_bwd_wave_many (ce_vjp_many_wave, ce_vjp_many_params_wave): the same for its many-cotangent twin
+#include "ce_lds_bwd_wave_many_qp.h"   // k_bwd_wave_many_qp (ce_vjp_qp_many_wave, ce_vjp_qp_many_params_wave): the same for the many-cotangent twin with a quadratic objective
 
 namespace {
 // the kernels this file launches itself; every other family is instantiated in its own translation unit (ce_tu_*.hip) and reached through the launchers of ce_types.h
@@ -111,6 +112,7 @@ struct ce_engine {
     int bwd_wave_variant = -1; size_t bwd_wave_lds = 0;      // k_bwd_wave (ce_vjp_wave): row of CE_BWD_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_qp_variant = -1; size_t bwd_wave_qp_lds = 0;      // k_bwd_wave_qp (ce_vjp_qp_wave): row of CE_BWD_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int bwd_wave_many_variant = -1; size_t bwd_wave_many_lds = 0;      // k_bwd_wave_many (ce_vjp_many_wave): row of CE_BWD_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
+    int bwd_wave_many_qp_variant = -1; size_t bwd_wave_many_qp_lds = 0;      // k_bwd_wave_many_qp (ce_vjp_qp_many_wave): row of CE_BWD_WAVE_MANY_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_variant = -1; size_t newton_wave_lds = 0;      // k_newton_wave (ce_jvp_wave, ce_refine_wave): row of CE_NEWTON_WAVE_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int newton_wave_qp_variant = -1; size_t newton_wave_qp_lds = 0;      // k_newton_wave_qp (ce_jvp_qp_wave, ce_refine_qp_wave): row of CE_NEWTON_WAVE_QP_VARIANTS that serves the template (-1: none) and its dynamic LDS
     int jvp_wave_many_variant = -1; size_t jvp_wave_many_lds = 0;      // k_jvp_wave_many (ce_jvp_many_wave): row of CE_JVP_WAVE_MANY_VARIANTS that serves the template (-1: none) and its dynamic LDS
@@ -327,6 +329,8 @@ int ce_create(const ce_template *tpl, int device, ce_handle *out) {
         h->wave_qp_lds = h->wave_qp_variant >= 0 ? fwd_wave_qp_lds_bytes(h->wave_qp_variant, tpl->n, tpl->m) : 0;
         h->bwd_wave_qp_variant = bwd_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
         h->bwd_wave_qp_lds = h->bwd_wave_qp_variant >= 0 ? bwd_wave_qp_lds_bytes(h->bwd_wave_qp_variant, tpl->n, tpl->m) : 0;
+        h->bwd_wave_many_qp_variant = bwd_wave_many_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
+        h->bwd_wave_many_qp_lds = h->bwd_wave_many_qp_variant >= 0 ? bwd_wave_many_qp_lds_bytes(h->bwd_wave_many_qp_variant, tpl->n, tpl->m) : 0;
         h->newton_wave_qp_variant = newton_wave_qp_variant(tpl->n, tpl->m, tpl->z, tpl->l, tpl->nq, tpl->q, tpl->ns, tpl->nep, tpl->np, tpl->nnz_p);
         h->newton_wave_qp_lds = h->newton_wave_qp_variant >= 0 ? newton_wave_qp_lds_bytes(h->newton_wave_qp_variant, tpl->n, tpl->m) : 0;
     }
@@ -1861,7 +1865,8 @@ int ce_jvp_qp_many(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b
 // rank-deficient instance stands with status 4 for every k (as ce_jvp_qp_many and ce_vjp_qp).
 // (rec: ce_vjp_qp_many_params -- the kernel stores the pairs' factor records [K][B][rpitch] and neither dA rows nor dP; dA_vals and dP_vals are unused then)
 static int vjp_qp_many_run(ce_handle h, const char *who, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
-                           const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0) {
+                           const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream, double *rec = nullptr, long rpitch = 0,
+                           bool wave = false) {          // (wave: ce_vjp_qp_many_wave, ce_vjp_qp_many_params_wave -- k_bwd_wave_many_qp in the place of k_backward_ns<..., QP, MANY>, the same strides)
     const CePlan &P = h->plan;
     const DevT &T = h->T;
     if (B > 1 && sA_b != T.nnz_aug) { g_err = std::string(who) + ": A_vals_bm must be contiguous batch-major rows"; return CE_E_BADARG; }
@@ -1884,7 +1889,11 @@ static int vjp_qp_many_run(ce_handle h, const char *who, int B, int K, const dou
     ba.T = T; ba.T.lda = T.n; ba.Abm = A_vals_bm; ba.x = x; ba.y = y; ba.s = s; ba.dx = dx; ba.dy = dy; ba.dA = dA_vals; ba.dq = dq_vals; ba.sdqk = 1; ba.sdqb = (long)(n + 1);
     ba.adj = adj_status; ba.fix = nullptr;
     h->last_fast = -1;
-    if (ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) { g_err = "internal: no many-cotangent kernel with a quadratic objective for the planned variant"; return CE_E_BADARG; }
+    if (wave ? ce_launch_bwd_wave_many_qp(h->bwd_wave_many_qp_variant, B, h->bwd_wave_many_qp_lds, st, ba,
+                                          BwdWaveManyQp{W.K, W.sxk, W.syk, W.sAk, W.sqk, W.sak, W.rec, W.rpitch, W.srk, P_vals, W.prow, W.pcol, h->nnz_p, W.p_tri, W.dP, W.sPk})
+             : ce_launch_ns(P.qp_ns_variant, B, P.qp_ns_lds, st, ba, W)) {
+        g_err = "internal: no many-cotangent kernel with a quadratic objective for the planned variant"; return CE_E_BADARG;
+    }
     HIPCHK(hipGetLastError());
     return CE_OK;
 }
@@ -1914,6 +1923,56 @@ int ce_vjp_qp_many_params(ce_handle h, int B, int K, const double *A_vals_bm, lo
     rc = vjp_qp_many_run(h, "ce_vjp_qp_many_params", B, K, A_vals_bm, sA_b, P_vals, x, y, s, dx, dy, nullptr, dq_vals, nullptr, adj_status, stream, h->d_rec.get(), rpitch);
     if (rc) return rc;
     return pg_records_launch(h, "ce_vjp_qp_many_params", B, K, x, y, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
+}
+// k_bwd_wave_many_qp: K cotangents of a small QP, one wave per (instance, chunk of cotangents) (include/cone_engine.h).  ce_vjp_qp_many's / ce_vjp_qp_many_params'
+// arguments and the whole of their bodies (vjp_qp_many_run: the strides, the records and k_param_grad) with the wave kernel in the place of
+// k_backward_ns<..., QP, MANY>; refused, before anything is enqueued, where the handle is not served.
+int ce_bwd_wave_many_qp_variant(ce_handle h) { return h ? h->bwd_wave_many_qp_variant : -1; }
+int ce_bwd_wave_many_qp_lds(ce_handle h) { return (h && h->bwd_wave_many_qp_variant >= 0) ? (int)h->bwd_wave_many_qp_lds : 0; }
+int ce_bwd_wave_many_qp_chunk(ce_handle h) { return (h && h->bwd_wave_many_qp_variant >= 0) ? bwd_wave_many_qp_chunk(h->bwd_wave_many_qp_variant) : 0; }
+int ce_bwd_wave_many_qp_occupancy(ce_handle h) {
+    if (!h || h->bwd_wave_many_qp_variant < 0) return 0;
+    int blocks = 0;
+    if (hipSetDevice(h->device) != hipSuccess || ce_occupancy_bwd_wave_many_qp(h->bwd_wave_many_qp_variant, h->bwd_wave_many_qp_lds, &blocks) != hipSuccess) return 0;
+    return blocks;
+}
+// (refused before anything is enqueued, nothing written; `alt`: the entry that serves the call instead, `alt_lin`: the linear objective's)
+static int wave_many_qp_check(ce_handle h, const char *who, int K, const char *alt, const char *alt_lin) {
+    if (h->bwd_wave_many_qp_variant < 0) {
+        const bool in_class = bwd_wave_many_qp_variant(h->T.n, h->T.m, h->T.z, h->T.l, h->T.nq, h->q.data(), h->T.ns, h->T.nep, h->T.np, h->nnz_p) >= 0;
+        g_err = std::string(who) + ": " + (in_class ? "the template does not run P inside the kernels (ce_qp_native == 0)"
+                                                    : bwd_wave_many_qp_refusal(h->T.n, h->T.m, h->T.ns, h->T.nep, h->T.np, h->nnz_p)) +
+                "; use " + (h->nnz_p <= 0 ? alt_lin : alt);
+        return CE_E_UNSUPPORTED;
+    }
+    const int kc = bwd_wave_many_qp_chunk(h->bwd_wave_many_qp_variant);
+    if ((K + kc - 1) / kc > 65535) { g_err = std::string(who) + ": K exceeds 65535 chunks of cotangents; use " + alt; return CE_E_UNSUPPORTED; }
+    return CE_OK;
+}
+int ce_vjp_qp_many_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                        const double *dx, const double *dy, double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !dA_vals || !dq_vals || !dP_vals) {
+        g_err = "ce_vjp_qp_many_wave: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
+    }
+    { const int rc = wave_many_qp_check(h, "ce_vjp_qp_many_wave", K, "ce_vjp_qp_many", "ce_vjp_many_wave"); if (rc) return rc; }
+    return vjp_qp_many_run(h, "ce_vjp_qp_many_wave", B, K, A_vals_bm, sA_b, P_vals, x, y, s, dx, dy, dA_vals, dq_vals, dP_vals, adj_status, stream, nullptr, 0, true);
+}
+int ce_vjp_qp_many_params_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                               const double *dx, const double *dy, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                               double *g, double *dq_vals, int *adj_status, void *stream) {
+    if (!h || B <= 0 || K <= 0 || !A_vals_bm || !P_vals || !x || !y || !s || !dx || !g || !dq_vals || !adj_status) {
+        g_err = "ce_vjp_qp_many_params_wave: null argument, B <= 0 or K <= 0"; return CE_E_BADARG;
+    }
+    int rc = wave_many_qp_check(h, "ce_vjp_qp_many_params_wave", K, "ce_vjp_qp_many_params", "ce_vjp_many_params_wave");
+    if (rc) return rc;
+    rc = pg_check(h, "ce_vjp_qp_many_params_wave", rows, map_ptr, map_code, map_k, map_val, nullptr, h->bwd_wave_many_qp_variant, ": internal, the served row went away", false);
+    if (rc) return rc;
+    const long rpitch = (long)h->T.m + 1 + h->T.n;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(h->d_rec.reserve((size_t)K * B * rpitch));
+    rc = vjp_qp_many_run(h, "ce_vjp_qp_many_params_wave", B, K, A_vals_bm, sA_b, P_vals, x, y, s, dx, dy, nullptr, dq_vals, nullptr, adj_status, stream, h->d_rec.get(), rpitch, true);
+    if (rc) return rc;
+    return pg_records_launch(h, "ce_vjp_qp_many_params_wave", B, K, x, y, rows, map_ptr, map_code, map_k, map_val, g, dq_vals, adj_status, stream);
 }
 
 // `steps` launches of k_backward_ns<..., FWD, REF> (with P_vals, ce_refine_qp: <..., FWD, REF, QP>), one complete safeguarded Newton step each; the per-instance record

@@ -39,7 +39,7 @@ class ConeEngine:
         # what the most recent solve() / vjp() did (introspection: tests, bench, info[...])
         self.last_path = None                 # "per_instance" / "const_a"
         self.last_vjp_many_path = None        # "many" (one ce_vjp_many call) / "loop" (K calls of vjp): what the last vjp_many ran
-        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
+        self.last_vjp_kernel = None           # "ce_vjp_qp_many" / "ce_vjp_qp_many_wave" / "ce_vjp_many" / "ce_vjp_tri_many" / "ce_vjp_psd_many" when the last vjp_many made that one call, None when it looped over vjp
         self.last_jvp_many_path = None        # "many" (one ce_jvp_many / ce_jvp_qp_many / ce_jvp_tri_many / ce_jvp_psd_many call) / "loop" (K calls of jvp): what the last jvp_many ran
         self.last_adjoint_kernel = None       # "k_bwd_wave" when the last vjp() / vjp_params() ran the one-instance-per-wave adjoint (wave=True), "k_bwd_wave_qp" when that vjp() had P_bm, "k_bwd_wave_many" when the last vjp_many() / vjp_many_params() ran its many-cotangent twin, None otherwise
         self.last_forward_kernel = None       # "k_fwd_wave" when the last solve() ran the one-instance-per-wave kernel (solve(wave=True)), None otherwise
@@ -169,6 +169,13 @@ class ConeEngine:
         (-1: not served -- bwd_wave_plan()'s class), the launch's dynamic LDS in bytes and the cotangents one wave serves (0, 0 when not served)"""
         L = _lib.lib()
         return int(L.ce_bwd_wave_many_variant(self._h)), int(L.ce_bwd_wave_many_lds(self._h)), int(L.ce_bwd_wave_many_chunk(self._h))
+
+    def bwd_wave_many_qp_plan(self):
+        """(variant, lds, chunk) of the many-cotangent wave adjoint of a quadratic objective, k_bwd_wave_many_qp, on this template: the row of
+        csrc/ce_variants_bwd_wave_many_qp.h that serves it (-1: not served -- bwd_wave_qp_plan()'s class), the launch's dynamic LDS in bytes and the cotangents one
+        wave serves (0, 0 when not served)"""
+        L = _lib.lib()
+        return int(L.ce_bwd_wave_many_qp_variant(self._h)), int(L.ce_bwd_wave_many_qp_lds(self._h)), int(L.ce_bwd_wave_many_qp_chunk(self._h))
 
     def jvp_wave_many_plan(self):
         """(variant, lds, chunk) of the many-tangent wave forward derivative k_jvp_wave_many on this template: the row of csrc/ce_variants_jvp_wave_many.h that serves
@@ -455,7 +462,9 @@ class ConeEngine:
         triples (ce_vjp_psd_tri_many_variant >= 0) the flag makes the one call ce_vjp_psd_tri_many (last_vjp_kernel names it).
         wave: the one call is ce_vjp_many_wave (k_bwd_wave_many: one wave per instance and chunk of bwd_wave_many_plan()[2] cotangents; last_vjp_kernel names the
         entry, last_adjoint_kernel == "k_bwd_wave_many"); vjp(wave=True)'s conditions -- the per-instance path, a linear objective, q_eval given, a served engine --,
-        and a call outside them raises."""
+        and a call outside them raises.  With P_bm and qp_many the one call is ce_vjp_qp_many_wave (k_bwd_wave_many_qp: one wave per instance and chunk of
+        bwd_wave_many_qp_plan()[2] cotangents, last_adjoint_kernel == "k_bwd_wave_many_qp"; ce_vjp_qp_many's outputs and flags) where bwd_wave_many_qp_plan()[0] >= 0;
+        with P_bm and without qp_many, or on an engine that kernel does not serve, the call raises."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
@@ -463,17 +472,22 @@ class ConeEngine:
             path = self.last_path
         self.last_adjoint_kernel = None
         if wave:
-            if P_bm is not None or path != "per_instance" or force_loop:
-                raise RuntimeError(f"vjp_many(wave=True): the wave adjoint serves the per-instance path with a linear objective in one call (path {path!r})")
-        many = wave or (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
-        many_qp = (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
+            if path != "per_instance" or force_loop:
+                raise RuntimeError(f"vjp_many(wave=True): the wave adjoint serves the per-instance path in one call (path {path!r})")
+            if P_bm is not None and not qp_many:
+                raise RuntimeError("vjp_many(wave=True): with P_bm the wave adjoint is the search-free elimination's (k_bwd_wave_many_qp): pass qp_many=True")
+            if P_bm is not None and self.bwd_wave_many_qp_plan()[0] < 0:
+                raise RuntimeError("vjp_many(wave=True, qp_many=True): k_bwd_wave_many_qp does not serve this engine (bwd_wave_many_qp_plan()[0] < 0)")
+        wave_qp = wave and P_bm is not None
+        many = (wave and not wave_qp) or (not force_loop and path == "per_instance" and q_eval is not None and P_bm is None and _lib.lib().ce_vjp_many_variant(self._h) >= 0)
+        many_qp = wave_qp or (not force_loop and qp_many and P_bm is not None and path == "per_instance" and _lib.lib().ce_vjp_qp_many_variant(self._h) >= 0)
         many_tri = (not force_loop and tri_many and not many and path == "per_instance" and q_eval is not None and P_bm is None
                     and _lib.lib().ce_vjp_tri_many_variant(self._h) >= 0)
         many_psd = (not force_loop and psd_many and not many and not many_tri and path == "per_instance" and q_eval is not None and P_bm is None
                     and (_lib.lib().ce_vjp_psd_many_variant(self._h) >= 0 or _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0))
         mixed = many_psd and _lib.lib().ce_vjp_psd_tri_many_variant(self._h) >= 0          # (PSD blocks and triples: the mixed entry, the same arguments)
         self.last_vjp_many_path = "many" if (many or many_qp or many_tri or many_psd) else "loop"
-        self.last_vjp_kernel = ("ce_vjp_qp_many" if many_qp else (("ce_vjp_many_wave" if wave else "ce_vjp_many") if many else ("ce_vjp_tri_many" if many_tri else
+        self.last_vjp_kernel = (("ce_vjp_qp_many_wave" if wave_qp else "ce_vjp_qp_many") if many_qp else (("ce_vjp_many_wave" if wave else "ce_vjp_many") if many else ("ce_vjp_tri_many" if many_tri else
                                                                                              (("ce_vjp_psd_tri_many" if mixed else "ce_vjp_psd_many") if many_psd else None))))
         if B == 0 or K == 0:
             out = (torch.empty((K, B, self.nnz_aug), **f64), torch.empty((K, B, self.n + 1), **f64), torch.empty((K, B), dtype=torch.int32, device=dev))
@@ -487,9 +501,10 @@ class ConeEngine:
             dq = torch.empty((K, B, self.n + 1), **f64)
             dP = torch.empty((K, B, self.nnz_p), **f64)
             adj = torch.empty((K, B), dtype=torch.int32, device=dev)
-            rc = _lib.lib().ce_vjp_qp_many(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
-                                           None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), dP.data_ptr(), adj.data_ptr(), self._stream())
-            _lib.check(rc, "ce_vjp_qp_many")
+            rc = getattr(_lib.lib(), self.last_vjp_kernel)(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                                           None if dy is None else dy.data_ptr(), dA.data_ptr(), dq.data_ptr(), dP.data_ptr(), adj.data_ptr(), self._stream())
+            _lib.check(rc, self.last_vjp_kernel)
+            self.last_adjoint_kernel = "k_bwd_wave_many_qp" if wave_qp else None
             return dA, dq, adj, dP
         if not (many or many_tri or many_psd):
             zero_dy = torch.zeros((B, self.m), **f64) if dy is None else None
@@ -543,18 +558,19 @@ class ConeEngine:
         entry, within the terms' rounding elsewhere.  One C call (last_vjp_many_path == "many_params", last_vjp_kernel names the entry): ce_vjp_many_params, or under
         the keywords of vjp_many the entry of that kind -- qp_many with P_bm: ce_vjp_qp_many_params (maps may carry a P map; q_eval and lsqr are not read: no
         re-solve); tri_many: ce_vjp_tri_many_params; psd_many: ce_vjp_psd_many_params, on a template with triples beside the blocks ce_vjp_psd_tri_many_params.
-        wave: ce_vjp_many_params_wave (k_bwd_wave_many in the place of the many-cotangent kernel; last_adjoint_kernel == "k_bwd_wave_many"), alone of the keywords.
+        wave: ce_vjp_many_params_wave (k_bwd_wave_many in the place of the many-cotangent kernel; last_adjoint_kernel == "k_bwd_wave_many"), alone of the keywords
+        -- or beside qp_many with P_bm: ce_vjp_qp_many_params_wave (k_bwd_wave_many_qp in record mode; last_adjoint_kernel == "k_bwd_wave_many_qp").
         The keyword SELECTS the entry: a template the entry does not serve raises _lib.EngineError with the library's reason and writes nothing."""
         dev = self.device
         f64 = dict(dtype=torch.float64, device=dev)
         K, B = int(dx.shape[0]), int(A_bm.shape[0])
         if qp_many and P_bm is None:
             raise ValueError("ConeEngine.vjp_many_params: qp_many needs P_bm")
-        if sum(map(bool, (qp_many, tri_many, psd_many, wave))) > 1 or (P_bm is not None and not qp_many):
-            raise ValueError("ConeEngine.vjp_many_params: at most one of qp_many / tri_many / psd_many / wave, and P_bm with qp_many alone")
+        if sum(map(bool, (qp_many, tri_many, psd_many))) > 1 or (wave and (tri_many or psd_many)) or (P_bm is not None and not qp_many):
+            raise ValueError("ConeEngine.vjp_many_params: at most one of qp_many / tri_many / psd_many, wave alone or beside qp_many, and P_bm with qp_many alone")
         self.last_adjoint_kernel = None
         L = _lib.lib()
-        name = ("ce_vjp_qp_many_params" if qp_many else "ce_vjp_tri_many_params" if tri_many else
+        name = (("ce_vjp_qp_many_params_wave" if wave else "ce_vjp_qp_many_params") if qp_many else "ce_vjp_tri_many_params" if tri_many else
                 ("ce_vjp_psd_tri_many_params" if L.ce_vjp_psd_tri_many_variant(self._h) >= 0 else "ce_vjp_psd_many_params") if psd_many else
                 "ce_vjp_many_params_wave" if wave else "ce_vjp_many_params")
         ptr, code, kidx, val = self._param_grad_prologue(maps, lsqr, q_eval, "vjp_many_params", need_q=not qp_many)
@@ -573,14 +589,14 @@ class ConeEngine:
         map_args = (maps.rows, ptr.data_ptr(), code.data_ptr(), kidx.data_ptr(), val.data_ptr(), g.data_ptr(), dq.data_ptr(), adj.data_ptr(), self._stream())
         if qp_many:
             P_c = P_bm.detach().to(**f64).contiguous()
-            rc = L.ce_vjp_qp_many_params(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
-                                         None if dy is None else dy.data_ptr(), *map_args)
+            rc = getattr(L, name)(self._h, B, K, A_c.data_ptr(), self.nnz_aug, P_c.data_ptr(), xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
+                                  None if dy is None else dy.data_ptr(), *map_args)
         else:
             qd, q_args = self._q_args(q_eval)
             rc = getattr(L, name)(self._h, B, K, A_c.data_ptr(), self.nnz_aug, *q_args, xc.data_ptr(), yc.data_ptr(), sc_.data_ptr(), dx.data_ptr(),
                                   None if dy is None else dy.data_ptr(), *map_args)
         _lib.check(rc, name)
-        self.last_adjoint_kernel = "k_bwd_wave_many" if wave else None
+        self.last_adjoint_kernel = ("k_bwd_wave_many_qp" if qp_many else "k_bwd_wave_many") if wave else None
         return g, dq, adj
 
     def param_grad_records(self, K: int, B: int) -> torch.Tensor:

@@ -161,7 +161,7 @@ class _Saved(NamedTuple):
     nw_wave: bool = False                   # newton_kernel() == "wave" and the node is served: forward-mode AD with jvp_mode="direct" runs ce_jvp_wave, tangent_many ce_jvp_many_wave (every other route ignores it)
     adj_wave: bool = False                  # adjoint_kernel() == "wave" and the node is served: backward() / adjoint_params run k_bwd_wave, adjoint_many / adjoint_many_params k_bwd_wave_many (every other route ignores it)
     nw_wave_qp: bool = False                # newton_kernel() == "wave" on a served node with P_bm: forward-mode AD with jvp_mode="direct" runs ce_jvp_qp_wave (every other route ignores it: nw_wave stays False on such a node, tangent_many / jacobian keep ce_jvp_qp_many)
-    adj_wave_qp: bool = False               # adjoint_kernel() == "wave" on a served node with P_bm: backward() runs k_bwd_wave_qp (every other route ignores it: adj_wave stays False on such a node)
+    adj_wave_qp: bool = False               # adjoint_kernel() == "wave" on a served node with P_bm: backward() runs k_bwd_wave_qp; beside qp_adjoint == "search_free" adjoint_many / adjoint_many_params run k_bwd_wave_many_qp (every other route ignores it: adj_wave stays False on such a node)
 
 
 class _ConeLayer(torch.autograd.Function):
@@ -471,12 +471,12 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
             dx = torch.where(keep, dx, torch.zeros_like(dx)); dy = torch.where(keep, dy, torch.zeros_like(dy)) if dy is not None else None
             x = torch.where(keep, x, torch.zeros_like(x)); y = torch.where(keep, y, torch.zeros_like(y)); s = torch.where(keep, s, torch.zeros_like(s))
         out = eng.vjp_many(saved.A_bm, x, y, s, dx, dy, path=saved.path, lsqr=saved.lsqr, q_eval=saved.q_eval, P_bm=saved.P_bm, qp_many=(saved.qp_adjoint == "search_free"),
-                           tri_many=(saved.tri_adjoint == "search_free"), psd_many=saved.psd_adjoint, **({"wave": True} if saved.adj_wave else {}))
+                           tri_many=(saved.tri_adjoint == "search_free"), psd_many=saved.psd_adjoint, **({"wave": True} if (saved.adj_wave or _wave_many_qp(saved)) else {}))
         dA, dq, adj = out[:3]
         dP = out[3] if saved.P_bm is not None else None
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
-            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many", "ce_vjp_psd_tri_many", "ce_vjp_many_wave"):
+            if eng.last_vjp_kernel in ("ce_vjp_qp_many", "ce_vjp_tri_many", "ce_vjp_psd_many", "ce_vjp_psd_tri_many", "ce_vjp_many_wave", "ce_vjp_qp_many_wave"):
                 info["adjoint"]["path"] = eng.last_vjp_kernel
         if K > 0 and batch_size > 0:
             any_k = adj[0].clone()
@@ -484,6 +484,13 @@ def adjoint_many(backward_data, dprimal, ddual, info=None):
                 any_k |= adj[k]
             eng.mailbox.note_adjoint_flags(any_k, batch_size)
     return dA, dq, dP, failed
+
+
+def _wave_many_qp(saved) -> bool:
+    """adjoint_many / adjoint_many_params of this node run k_bwd_wave_many_qp: a QP node under adjoint_kernel="wave" AND qp_adjoint="search_free" (either key alone
+    keeps its route) whose engine the kernel serves"""
+    return bool(saved.adj_wave_qp and saved.qp_adjoint == "search_free" and saved.P_bm is not None and saved.path == "per_instance"
+                and saved.eng.bwd_wave_many_qp_plan()[0] >= 0)
 
 
 def param_grad_kind(backward_data):
@@ -550,7 +557,7 @@ def adjoint_many_params(backward_data, dprimal, ddual, info, maps, out=None):
         dy = ddual.to(**f64).contiguous() if ddual is not None else None
         x, y, s, (dx, dy) = _masked_point(saved, [dx, dy])
         g, dq, adj = eng.vjp_many_params(saved.A_bm, x, y, s, dx, dy, maps, lsqr=saved.lsqr, q_eval=saved.q_eval, out=out, P_bm=saved.P_bm if kind == "qp" else None,
-                                         qp_many=kind == "qp", tri_many=kind == "tri", psd_many=kind == "psd", **({"wave": True} if (saved.adj_wave and kind == "plain") else {}))
+                                         qp_many=kind == "qp", tri_many=kind == "tri", psd_many=kind == "psd", **({"wave": True} if ((saved.adj_wave and kind == "plain") or (kind == "qp" and _wave_many_qp(saved))) else {}))
         if isinstance(info, dict) and isinstance(info.get("adjoint"), dict):
             info["adjoint"]["status"] = adj
             info["adjoint"]["path"] = eng.last_vjp_kernel

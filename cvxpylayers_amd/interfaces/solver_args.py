@@ -259,6 +259,9 @@ def adjoint_kernel(merged_args: dict) -> str:
     On a node whose quadratic objective runs inside the kernels, k_bwd_wave_qp (ce_vjp_qp_wave; ConeEngine.bwd_wave_qp_plan()[0] >= 0) in the place of the
     pivoting kernel of ce_vjp_qp: the search-free elimination with P, so a rank-deficient instance keeps the dropped-variable answer with status 4 where
     ce_vjp_qp returns its own basic solution (the difference qp_adjoint="search_free" documents; no LSQR has a P term).
+    Beside qp_adjoint="search_free" on such a node the many-cotangent routes -- adjoint_many, adjoint_many_params, layer.jacobian(direction="reverse") -- run
+    k_bwd_wave_many_qp (ce_vjp_qp_many_wave / ce_vjp_qp_many_params_wave; ConeEngine.bwd_wave_many_qp_plan()[0] >= 0) in the place of ce_vjp_qp_many's kernel:
+    the same system and flags, info["adjoint"]["path"] names the entry.  Either key alone leaves those routes as they are.
     info["adjoint"]["kernel"] tells which runs ("k_bwd_wave" / "k_bwd_wave_qp" / "workgroup").  Independent of forward_kernel; composes with param_grad="factors"
     on a linear objective.
     Every other template or path -- a quadratic objective outside the kernels, a PSD / exponential / power cone, a larger template, a shared A, any mode= key (LPGD included),

@@ -697,6 +697,33 @@ int ce_bwd_wave_many_lds(ce_handle h);
 int ce_bwd_wave_many_chunk(ce_handle h);
 int ce_bwd_wave_many_occupancy(ce_handle h);
 /*
+ * K cotangents at one solution of a small quadratic program, ONE WAVE PER (INSTANCE, CHUNK OF COTANGENTS) (k_bwd_wave_many_qp, csrc/ce_backward_wave_many_qp.h;
+ * additions under ABI 17).  ce_vjp_many_wave's work split -- lanes n .. n + KC - 1 carry KC cotangents through the row elimination, the null-space transform, the Gram
+ * accumulation and the sweep -- with P inside the way ce_vjp_qp_wave adds it: the second pass of the transform over W = P Z leaves -(Z^T P x_p,k) of every
+ * cotangent of the chunk in its lane.  The system, the flags and the outputs are ce_vjp_qp_many's; the results agree with it to rounding, not bit for bit, and a
+ * cotangent's result depends neither on its position among the K nor on the instance's position in the batch.
+ *   served                       : exactly ce_vjp_qp_wave's class (ce_bwd_wave_qp_variant >= 0).
+ *   ce_vjp_qp_many_wave          : ce_vjp_qp_many's arguments, layouts and outputs (dA [K][B][nnz_aug], dq [K][B][n + 1], dP [K][B][nnz_p], adj_status [K][B]: 0 or
+ *                                  4 -- neq > n: zero outputs for every k; a dropped equality row or variable: the dropped-variable answer; bit 8 is never set).
+ *   ce_vjp_qp_many_params_wave   : ce_vjp_qp_many_params' arguments and outputs (the kernel in record mode, k_param_grad behind it; neither dA nor dP is written).
+ *                                  Both: CE_E_UNSUPPORTED, before anything is enqueued and with nothing written, on a handle that is not served (a linear objective
+ *                                  is named as such); ce_last_error names the entry and the reason.  No re-solve.  K = 1 is legal.
+ *   ce_bwd_wave_many_qp_variant  : the row of the kernel's instantiation list (csrc/ce_variants_bwd_wave_many_qp.h) that serves the handle, -1: not served, or h == NULL.
+ *   ce_bwd_wave_many_qp_lds      : the launch's dynamic LDS in bytes (0 when not served).
+ *   ce_bwd_wave_many_qp_chunk    : KC of that row, the cotangents one wave serves (0 when not served).
+ *   ce_bwd_wave_many_qp_occupancy: resident workgroups (= instance-chunks) per CU of that row at that footprint, as the runtime's occupancy query reports it.
+ */
+int ce_vjp_qp_many_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals,
+                        const double *x, const double *y, const double *s, const double *dx, const double *dy,
+                        double *dA_vals, double *dq_vals, double *dP_vals, int *adj_status, void *stream);
+int ce_vjp_qp_many_params_wave(ce_handle h, int B, int K, const double *A_vals_bm, long sA_b, const double *P_vals, const double *x, const double *y, const double *s,
+                               const double *dx, const double *dy, int rows, const int *map_ptr, const int *map_code, const int *map_k, const double *map_val,
+                               double *g, double *dq_vals, int *adj_status, void *stream);
+int ce_bwd_wave_many_qp_variant(ce_handle h);
+int ce_bwd_wave_many_qp_lds(ce_handle h);
+int ce_bwd_wave_many_qp_chunk(ce_handle h);
+int ce_bwd_wave_many_qp_occupancy(ce_handle h);
+/*
  * The forward derivative and the Newton refinement step of a small template, ONE INSTANCE PER WAVE (k_newton_wave, csrc/ce_newton_wave.h; additions under ABI 17).
  * ce_jvp and ce_refine run k_backward_ns<..., FWD> / <..., FWD, REF>: 256 threads and 52.9 KB of LDS per instance, three instances per CU.  Here a 64-thread
  * workgroup solves the forward block with ce_vjp_wave's elimination (the same H and B) between a prologue and an epilogue of its own.  Same system, rules, flags,
